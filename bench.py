@@ -23,6 +23,10 @@ forward (configs[4]), per-shape and one-block Llama lines, eigensolver phases --
 file (and to gpurun_out/bench_detail.json, which travels back from the GPU box); an earlier stdout line names it.
 Counter-derived fields (traffic, MFMA utilisation) are quoted from committed rocprofv3 PMC summaries; each carries the
 hash of the kernel source it was measured on and is marked "stale": true when the source has changed since.
+
+`--dump-outputs DIR` writes, after the timed steps, what the LAST timed step handed its caller -- the decomposed model's
+parameters and the figures of its decompose_config -- as DIR/<name>.npy (dump_outputs).  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 
 from __future__ import annotations
@@ -476,11 +480,14 @@ def llama_workload(device, blocks, dt, metric_pool=METRIC_POOL):
     with torch.no_grad():
         bt = [{"x": x, "targets": model0({"x": x}).argmax(-1)} for x in xs]
 
-    def step(trace=None):
+    def step(trace=None, keep=None):
         m = copy.deepcopy(model0)
-        return ptdeco_amd.dwain.decompose_in_place(module=m, device=device, data_iterator=itertools.cycle(bt[:12]),
-                                                   loss_fn=seq_ce, metric_iterator=itertools.cycle(bt[8:]),
-                                                   finetune_fn=lambda mm, d, n: mm, trace=trace, **kw)
+        cfg = ptdeco_amd.dwain.decompose_in_place(module=m, device=device, data_iterator=itertools.cycle(bt[:12]),
+                                                  loss_fn=seq_ce, metric_iterator=itertools.cycle(bt[8:]),
+                                                  finetune_fn=lambda mm, d, n: mm, trace=trace, **kw)
+        if keep is not None:        # (--dump-outputs: what the caller receives, the decomposed model and its config)
+            keep.update(module=m, config=cfg)
+        return cfg
     return step, kw
 
 
@@ -709,6 +716,55 @@ def roofline_from_profile(prof, device):
     return out
 
 
+DUMP_LIMIT = 64 * 10**6        # bytes of all the .npy files --dump-outputs writes
+DUMP_SEED = 2024               # the element sample of a parameter too large to be written whole
+META_FIELDS = ("proportion", "nsr_final", "ppl_final", "drop_in_params")
+
+
+def dump_outputs(out_dir: str, module: torch.nn.Module, config: dict, limit: int = DUMP_LIMIT) -> list:
+    """--dump-outputs: what the timed path hands its caller, as out_dir/<name>.npy.
+
+    * <state_dict key>.npy (float32): every parameter and buffer of the decomposed model (bf16 and f32 values are
+      exact in f32).  A tensor of more elements than its share of `limit` is written as a sample: the elements at
+      sorted seeded positions of the flattened tensor (seed DUMP_SEED + crc32 of the name, so the same positions for
+      the same name and size in every run), 1-D.
+    * config.<layer>.npy (float64): META_FIELDS of the layer's decompose_config entry, in that order.
+
+    Returns the names written.  Files of the same names are overwritten; nothing else in out_dir is touched."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    state = module.state_dict()
+    header = 128                                                 # bytes of an .npy header of these shapes
+    meta_bytes = len(config) * (header + 8 * len(META_FIELDS))
+    share = (limit - meta_bytes - len(state) * header) // (4 * max(1, len(state)))
+    if share < 1:
+        raise ValueError(f"--dump-outputs: {len(state)} tensors do not fit in {limit} bytes")
+    names, total = [], 0
+
+    def save(name, arr):
+        nonlocal total
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, arr)
+        total += os.path.getsize(path)
+        names.append(name)
+
+    for name, t in state.items():
+        t = t.detach()
+        if t.numel() > share:
+            g = torch.Generator().manual_seed(DUMP_SEED + zlib.crc32(name.encode()))
+            idx = torch.randint(t.numel(), (share,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        save(name, t.float().cpu().numpy())
+    for layer, entry in config.items():
+        meta = entry.get("__meta__", {})
+        save("config." + layer, np.array([float(meta.get(k, float("nan"))) for k in META_FIELDS], dtype=np.float64))
+    assert total <= limit, total
+    return names
+
+
 def launch_ranks(args_list, gpus) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks as CHILD processes of this one
     (python -m torch.distributed.run, rendezvous on 127.0.0.1) before anything here has touched the GPU, pass
@@ -738,7 +794,16 @@ def parse_args(argv=None):
     ap.add_argument("--workload", choices=("c4", "c2"), default="c4",
                     help="c2: time BASELINE configs[1] alone (one layer; for kernel traces); default: the Llama stack")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"))
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the decomposed model's "
+                         "parameters, a fixed seeded sample of the large ones, and its decompose_config figures) as "
+                         "DIR/<name>.npy, f32 / f64, at most 64 MB in all")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def measure(args):
@@ -772,17 +837,18 @@ def measure(args):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(one_step):
+    def timed(one_step, keep=None):
         """W untimed steps, then exactly K steps between barrier + synchronize; max over ranks.
-        Returns (seconds, last config, per-step host durations in ms)."""
+        Returns (seconds, last config, per-step host durations in ms).  `keep` (a dict) receives the decomposed model
+        and config of the LAST timed step."""
         cfg = None
         for _ in range(args.warmup):
             cfg = one_step()
         barrier()
         t0 = time.perf_counter()
         marks = []
-        for _ in range(args.steps):
-            cfg = one_step()
+        for i in range(args.steps):
+            cfg = one_step(keep=keep) if keep is not None and i == args.steps - 1 else one_step()
             marks.append(time.perf_counter())     # (no synchronisation added: a step ends on the host's last decision)
         barrier()
         dt = time.perf_counter() - t0
@@ -800,19 +866,26 @@ def measure(args):
         model.to(device)
         data, metric = with_targets(model, data, device), with_targets(model, metric, device)
 
-        def one_step():
+        def one_step(keep=None):
             m = copy.deepcopy(model)
-            return ptdeco_amd.dwain.decompose_in_place(
+            cfg = ptdeco_amd.dwain.decompose_in_place(
                 module=m, device=device, data_iterator=itertools.cycle(data), loss_fn=ce_loss,
                 metric_iterator=itertools.cycle(metric), finetune_fn=lambda mm, d, names: mm,
                 precomputing_covariance_num_splits=1, **DWAIN_KW)
+            if keep is not None:
+                keep.update(module=m, config=cfg)
+            return cfg
         return one_step
 
     c2_text = ("BASELINE configs[1]: dwain decompose_in_place of ONE nn.Linear(4096,4096) f32, precompute pass (1 split), "
                "T=4x1024 tokens/batch, D=4, M=2, 6 evaluated candidate ranks, f64 covariance+eigh")
     if args.workload == "c2":
         # profiling aid: BASELINE configs[1] alone under the same protocol (python bench.py --workload c2 --no-extras)
-        dt, cfg, marks = timed(c2_family())
+        kept_out = {} if args.dump_outputs else None
+        dt, cfg, marks = timed(c2_family(), kept_out)
+        if kept_out is not None and rank == 0:
+            dump_outputs(args.dump_outputs, kept_out["module"], kept_out["config"])
+        kept_out = None
         res = {"metric": METRIC, "value": args.steps / dt, "unit": "layers/s", "n_gpus": world, "steps": args.steps,
                "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "step_ms": marks, "higher_is_better": True,
                "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -825,7 +898,11 @@ def measure(args):
     # ---- the headline: BASELINE configs[3] at reduced depth, bf16 model, the same work at every N
     step, kw = llama_workload(device, args.blocks, torch.bfloat16)
     layers = 7 * args.blocks
-    dt, cfg, marks = timed(step)
+    kept_out = {} if args.dump_outputs else None
+    dt, cfg, marks = timed(step, kept_out)
+    if kept_out is not None and rank == 0:
+        dump_outputs(args.dump_outputs, kept_out["module"], kept_out["config"])
+    kept_out = None
     comm = ("; calibration steps and (candidate, batch) pairs dealt to the ranks, packed covariance sums reduced to the layer "
             "owners + eigenvector broadcast over RCCL") if world > 1 else ""
     med = sorted(marks)[len(marks) // 2]

@@ -92,3 +92,79 @@ def test_compact_line_never_exceeds_the_limit_even_with_absurd_blocks():
 def test_ranks_other_than_zero_print_nothing(capsys, tmp_path):
     rc = bench.main(["--gpus", "1", "--detail", str(tmp_path / "d.json")], measure_fn=lambda args: None)
     assert rc == 0 and capsys.readouterr().out == ""
+
+
+def _decomposed_toy(n_in=300, r=10, n_out=400):
+    torch = bench.torch
+    g = torch.Generator().manual_seed(5)
+    m = torch.nn.Sequential(torch.nn.Linear(n_in, 20), torch.nn.Sequential(torch.nn.Linear(20, r, bias=False),
+                                                                          torch.nn.Linear(r, n_out, bias=False)))
+    with torch.no_grad():
+        for p in m.parameters():
+            p.copy_(torch.randn(p.shape, generator=g))
+    m.to(torch.bfloat16)
+    cfg = {"1": {"type": "Sequential", "modules": {},
+                 "__meta__": {"proportion": 0.5, "nsr_final": torch.tensor(0.0123, dtype=torch.float64), "ppl_final": 1.25,
+                              "drop_in_params": 3000}}}
+    return m, cfg
+
+
+def test_dump_outputs_writes_the_decomposed_model_within_the_limit(tmp_path):
+    """--dump-outputs: every state_dict entry as <key>.npy in f32 (whole, or a seeded sample of positions when the tensor is
+    larger than its share of the limit), the decompose_config figures as config.<layer>.npy in f64, all within the limit;
+    the same model gives the same files."""
+    import numpy as np
+    torch = bench.torch
+    m, cfg = _decomposed_toy()
+    limit = 20000
+    names = bench.dump_outputs(str(tmp_path / "a"), m, cfg, limit=limit)
+    assert sorted(names) == sorted(list(m.state_dict()) + ["config.1"])
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= limit
+    sd = m.state_dict()
+    share = (limit - 1 * (128 + 32) - len(sd) * 128) // (4 * len(sd))
+    for key, t in sd.items():
+        arr = np.load(tmp_path / "a" / (key + ".npy"))
+        assert arr.dtype == np.float32
+        flat = t.float().reshape(-1).numpy()
+        if t.numel() <= share:
+            assert arr.shape == tuple(t.shape) and np.array_equal(arr.reshape(-1), flat), key
+        else:
+            assert arr.shape == (share,), key
+            # a sample: values of the tensor, in the order of their (sorted) positions
+            assert np.isin(arr, flat).all(), key
+    meta = np.load(tmp_path / "a" / "config.1.npy")
+    assert meta.dtype == np.float64 and meta.tolist() == [0.5, 0.0123, 1.25, 3000.0]
+    bench.dump_outputs(str(tmp_path / "b"), m, cfg, limit=limit)
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))), name
+    # a different model of the same shapes is told apart in the sampled tensors too
+    with torch.no_grad():
+        m[1][1].weight.mul_(2)
+    bench.dump_outputs(str(tmp_path / "c"), m, cfg, limit=limit)
+    assert not np.array_equal(np.load(tmp_path / "a" / "1.1.weight.npy"), np.load(tmp_path / "c" / "1.1.weight.npy"))
+
+
+def test_dump_outputs_under_the_default_limit_at_the_headline_shapes(tmp_path):
+    """The headline's worst case -- two Llama-3-8B-width blocks with all 14 layers replaced by pairs, + the head: 29
+    tensors, each larger than its share -- stays within 64 MB (a stand-in of 29 tensors of 600k elements)."""
+    torch = bench.torch
+    m = torch.nn.ModuleDict({f"l{i}": torch.nn.Linear(1000, 600, bias=False) for i in range(29)})
+    cfg = {f"l{i}": {"__meta__": {"proportion": 0.25, "nsr_final": 0.1, "ppl_final": 2.0, "drop_in_params": 7}}
+           for i in range(14)}
+    bench.dump_outputs(str(tmp_path), m, cfg)
+    total = sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path))
+    assert total <= 64 * 10**6 and len(os.listdir(tmp_path)) == 29 + 14
+
+
+def test_steps_and_dump_arguments():
+    args = bench.parse_args(["--steps", "3", "--warmup", "0", "--dump-outputs", "out"])
+    assert args.steps == 3 and args.warmup == 0 and args.dump_outputs == "out"
+    assert bench.parse_args([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        try:
+            bench.parse_args(bad)
+        except SystemExit as exc:
+            assert exc.code == 2
+        else:
+            raise AssertionError(bad)
