@@ -31,10 +31,11 @@
 extern "C" {
 #endif
 
-#define PTD_ABI_VERSION 4   /* 2: ptd_nsr workspaces are initialised once (ptd_nsr_workspace_init); ptd_chol_inverse
-                             * 3: ptd_stream_pair_wall_us, ptd_streams_wall_us, ptd_syrk_accumulate_multi
+#define PTD_ABI_VERSION 5   /* 2: ptd_nsr workspaces are initialised once (ptd_nsr_workspace_init); ptd_chol_inverse
+                             * 3: ptd_streams_wall_us and a two-stream form of it, ptd_syrk_accumulate_multi
                              * 4: ptd_eigh_topk_batched, ptd_eigh_factored_prepare / _finish; ptd_band_reduce and the
-                             *    two-stage reduction behind it are gone (2.2 x behind the default for three rounds) */
+                             *    two-stage reduction behind it are gone (2.2 x behind the default for three rounds)
+                             * 5: the two-stream form of ptd_streams_wall_us is gone (the same call with count = 2) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2 } ptd_dtype;
 
@@ -60,19 +61,13 @@ const char* ptd_last_error(void);
  * 10 ms wall-clock time-out after which the reduction is repeated on the blocked path. */
 int ptd_set_concurrent_chains(int chains);
 
-/* Host query (round 5, synchronous): do two streams sit on DIFFERENT hardware queues?  The ROCm runtime maps the
- * streams of a process onto 4 hardware queues per priority level; two chains of dependent launches whose streams
- * share one are executed one packet after the other (measured: the seven eigendecompositions of a Llama block on four
- * streams take 187 ms when the four queues are distinct and 226-300 ms when two chains share one).  Launches one
- * single-wave kernel that holds its queue for `spin_us` microseconds on each stream and returns the wall time of the
- * pair in *wall_us: about spin_us when they ran side by side, about 2 x spin_us when they were serialised.  Both
- * streams are synchronised before and after.  No reference counterpart (torch.linalg.eigh calls are serial,
- * dwain.py:155-163); used by ptdeco_amd._engine.chain_streams to pick the streams of concurrent eigendecompositions. */
-int ptd_stream_pair_wall_us(void* stream_a, void* stream_b, int spin_us, double* wall_us);
-/* The same for `count` streams at once (a HOST array of hipStream_t): one kernel of `spin_us` on each; about spin_us when
- * all of them ran side by side, a multiple when some were serialised.  run_concurrently re-checks its streams with it at
- * every call (0.2 ms): which streams share a hardware queue was seen to CHANGE within a process (bench.py: four streams
- * verified distinct early on, two of them serialised a minute later). */
+/* Host diagnostic (synchronous): do these streams overlap?  The ROCm runtime maps the streams of a process onto 4
+ * hardware queues per priority level, and two chains of dependent launches whose streams share one are executed one
+ * packet after the other.  Launches one single-wave kernel that holds its queue for `spin_us` microseconds on each of
+ * `count` streams (a HOST array of hipStream_t) and returns the wall time in *wall_us: about spin_us when all of them
+ * ran side by side, a multiple when some were serialised.  Every stream is synchronised before and after.  No reference
+ * counterpart (torch.linalg.eigh calls are serial, dwain.py:155-163); the tests check the dedicated streams below
+ * with it. */
 int ptd_streams_wall_us(void* const* streams, int count, int spin_us, double* wall_us);
 
 /* A HIP stream with a hardware queue OF ITS OWN (ABI 4): hipExtStreamCreateWithCUMask over CUs [cu_first, cu_first +
@@ -176,7 +171,7 @@ int ptd_eigh_topk_f32(const float* A, int64_t lda, int64_t n, int64_t k, int all
  * serves all of them (blockIdx.y = matrix) -- one host thread, one stream, one host synchronisation for the batch,
  * where round 5 ran one thread and one stream per layer.  Requests the filtered route serves (see above) and single
  * matrices are solved one after the other exactly as ptd_eigh_topk would; two matrices are batched from n = 512 on
- * (PTD_EIGH_BATCH_MIN_N), three or more always; PTD_EIGH_BATCHED=0: never.  `all_values` is a set of flags: bit 0 = every
+ * (PTD_EIGH_BATCH_MIN_N), three or more always.  `all_values` is a set of flags: bit 0 = every
  * eigenvalue is wanted (as in ptd_eigh_topk), bit 1 (PTD_EIGH_FLAG_DIRECT) = take the direct reduction also where the
  * filtered route would serve the request, so that the matrices are batched: for a caller whose pass already runs
  * latency-bound reductions of this order on other streams, beside which the filter's f64 products only share the matrix

@@ -13,6 +13,7 @@ allocation, views, dtype casts of slices and the user's own model forward.
 
 from __future__ import annotations
 
+import threading
 from typing import Optional
 
 import torch
@@ -944,7 +945,7 @@ class StepBatch:
             StepBatch.held_bytes -= self._held[0]
             self._held[0] = 0
         ops.syrk_accumulate_multi(self.E, ys, 1.0 / ys[0].shape[0])
-        # (a flush from a worker thread of run_concurrently runs on that thread's side stream while the matrices were
+        # (a flush from a lane thread of run_lanes runs on that lane's stream while the matrices were
         # allocated on the caller's: the allocator must not hand their memory out again before this stream is done
         # with it.  The drivers flush on the caller's stream before the concurrent section -- SharedInputPool.finalize,
         # the reductions -- so this is the safety net, not the rule.)
@@ -1240,10 +1241,8 @@ def solve_eigenproblems(posers: list, orders: list, device: torch.device, costs:
     if timeline:
         t_begin = torch.cuda.Event(enable_timing=True)
         t_begin.record()
-    if len(lanes) == 1:
-        lane(lanes[0])()
-    else:
-        run_concurrently([lane(r) for r in lanes], device, max_streams=len(lanes))
+    run_lanes([lane(r) for r in lanes], device)
+    if len(lanes) > 1:
         cur = torch.cuda.current_stream(device)
         for t in out:       # (allocated on a lane's stream, used from here on under the caller's)
             if isinstance(t, torch.Tensor) and t.is_cuda:
@@ -1518,40 +1517,30 @@ def eigh_cost_hint(cov, n_out: int, top_k: Optional[int]) -> float:
     return cost
 
 
-_DEDICATED_STREAMS: dict = {}  # (device index, CU split) -> streams with hardware queues of their own
+_DEDICATED_STREAMS: dict = {}  # device index -> streams with hardware queues of their own
+_DEDICATED_LOCK = threading.Lock()     # guards the creation of dedicated streams (_DEDICATED_STREAMS, _DEDICATED_RAW)
+CHAIN_STREAM_STATS = {"calls": 0, "selections": 0, "rechecks_failed": 0}    # (bench.py reports it; all 0 since ABI 5)
 
 
 def dedicated_streams(device: torch.device, want: int) -> list:
     """`want` HIP streams of `device` that each own a hardware queue (ptd_stream_create_dedicated:
-    hipExtStreamCreateWithCUMask), created once per device and kept for the life of the process.  Round 5 took streams
-    from torch's pool and MEASURED which of them shared one of the runtime's four hardware queues (chain_streams below,
-    still there behind PTD_LANE_STREAMS=pool): two chains on one queue run packet by packet, and which streams share
-    depends on the creation order of every stream in the process.  A stream created with a CU mask is given a queue no
-    other stream uses: the lanes overlap by construction, nothing to probe, nothing that can change mid-process.
-    PTD_LANE_CUS = "a,b,c" gives lane i a contiguous range of that many CUs (experiments); default: every lane sees the
-    whole chip."""
+    hipExtStreamCreateWithCUMask over every CU), created once per device and kept for the life of the process.  The
+    runtime multiplexes ordinary streams onto four hardware queues; two chains on one queue run packet by packet, and
+    which streams share one depends on the creation order of every stream in the process (round 5 measured and
+    re-checked pool streams for it; removed at ABI 5).  A stream created with a CU mask is given a queue no other
+    stream uses: the lanes overlap by construction, nothing to probe, nothing that can change mid-process."""
     import ctypes
-    import os
-    import threading
 
     from . import _hip
 
-    global _CHAIN_STREAMS_LOCK
-    if _CHAIN_STREAMS_LOCK is None:
-        _CHAIN_STREAMS_LOCK = threading.Lock()
     index = device.index if device.index is not None else torch.cuda.current_device()
-    split = os.environ.get("PTD_LANE_CUS", "")
-    counts = [int(c) for c in split.split(",") if c.strip()] if split else []
-    with _CHAIN_STREAMS_LOCK:
-        have = _DEDICATED_STREAMS.setdefault((index, split), [])
+    with _DEDICATED_LOCK:
+        have = _DEDICATED_STREAMS.setdefault(index, [])
         lib = _hip.load()
         with torch.cuda.device(index):
             while len(have) < want:
-                i = len(have)
-                first = sum(counts[:i]) if i < len(counts) else 0
-                count = counts[i] if i < len(counts) else 0
                 ptr = ctypes.c_void_p(0)
-                _hip.check(lib.ptd_stream_create_dedicated(first, count, ctypes.byref(ptr)), "ptd_stream_create_dedicated")
+                _hip.check(lib.ptd_stream_create_dedicated(0, 0, ctypes.byref(ptr)), "ptd_stream_create_dedicated")
                 if not _DEDICATED_RAW:
                     import atexit
 
@@ -1581,201 +1570,46 @@ def _destroy_dedicated_streams() -> None:
     _DEDICATED_STREAMS.clear()
 
 
-_CHAIN_STREAMS: dict = {}      # device index -> (streams on pairwise distinct hardware queues, candidates exhausted?)
-CHAIN_STREAM_STATS = {"calls": 0, "selections": 0, "rechecks_failed": 0}     # (bench.py reports them)
-_CHAIN_STREAMS_LOCK = None
+def run_lanes(lanes, device: torch.device) -> list:
+    """Run independent device-side lanes (callables) side by side and return their results in order: lane i runs from
+    host thread i on dedicated stream i (`dedicated_streams`), under torch.no_grad().
 
-
-def chain_streams(device: torch.device, want: int) -> list:
-    """Up to `want` HIP streams of `device` that sit on pairwise DIFFERENT hardware queues, for chains of dependent
-    launches that are meant to interleave on the GPU (run_concurrently).
-
-    The ROCm runtime multiplexes the streams of a process onto 4 hardware queues per priority level
-    (tools/probes/launch_rate_probe.hip: of eight streams created in a row, 0/7, 1/6, 2/5 and 3/4 share a queue; the
-    high-priority streams have four queues of their own) and two chains on one queue are executed packet by packet, in
-    turn.  Which streams share is a fact of the process (creation order of every stream in it, torch's pools included),
-    so it is MEASURED, once per device: candidates from torch's high-priority pool, then from the normal one, are tested
-    pairwise with ptd_stream_pair_wall_us (two single-wave kernels that hold their queue for 400 us: side by side
-    ~0.42 ms, serialised ~0.82 ms) and taken greedily while they overlap with every stream taken before.  The streams
-    are kept for the life of the process (the mapping of an existing stream does not change: the probe's matrix is
-    identical before and after use).  Fewer than `want` distinct queues -> fewer streams are returned.
-    PTD_CHAIN_STREAMS_VERIFY=0 skips the measurement (pool streams as they come, the round-4 behaviour)."""
-    import os
-    import threading
-    import ctypes
-
+    One eigendecomposition is a chain of thousands of short dependent launches that leaves most of the GPU idle; chains
+    on different hardware queues interleave on the device.  The C ABI keeps no shared mutable state and releases the
+    GIL, so the host side is plain threads.  Stream order: every lane stream first waits for the caller's stream
+    (inputs), the caller's stream waits for all of them at the end (outputs); what a lane allocates belongs to its
+    stream, so a caller that keeps it calls record_stream (solve_eigenproblems does).  The first lane exception is
+    raised on the caller's thread once every thread has joined.  One lane, or a CPU device: the lanes run in order on
+    the caller's thread and stream."""
+    lanes = list(lanes)
+    device = torch.device(device)
+    if len(lanes) <= 1 or device.type != "cuda":
+        return [lane() for lane in lanes]
     from . import _hip
 
-    global _CHAIN_STREAMS_LOCK
-    if _CHAIN_STREAMS_LOCK is None:
-        _CHAIN_STREAMS_LOCK = threading.Lock()
-    device = torch.device(device)
     index = device.index if device.index is not None else torch.cuda.current_device()
     device = torch.device("cuda", index)
-    want = max(1, int(want))
-    if os.environ.get("PTD_LANE_STREAMS", "dedicated") != "pool":
-        return dedicated_streams(device, want)
-    if os.environ.get("PTD_CHAIN_STREAMS_VERIFY", "1") == "0":
-        return [torch.cuda.Stream(device=device) for _ in range(want)]
-    with _CHAIN_STREAMS_LOCK:
-        have, exhausted = _CHAIN_STREAMS.get(index, ([], False))
-        lib = _hip.load()
-        # (400 us per kernel: a serialised pair shows as +400 us, far above what a descheduled host thread or a slow
-        # launch adds -- at 150 us a 65-us hiccup of the host read as "serialised" and set off a re-selection: bench.py on a
-        # busy box, bf16 stack 388 -> 509 ms per step)
-        spin_us = 400
-        wall = ctypes.c_double(0.0)
-        CHAIN_STREAM_STATS["calls"] += 1
-        if have and (len(have) >= want or exhausted):
-            # Re-check the kept streams, all at once (one 150-us kernel on each: 0.2 ms): the mapping of streams onto
-            # hardware queues was seen to change within a process -- bench.py: four streams verified distinct at the first
-            # call, two of them serialised a minute later (B_eigh 243 instead of 187 ms, one chain ending at 390 ms) --
-            # so a verdict is only good for the call it was measured in.
-            group = have[:want]
-            arr = (ctypes.c_void_p * len(group))(*[h.cuda_stream for h in group])
-            with torch.cuda.device(device):
-                for attempt in range(2):       # (a failed check is repeated once before it counts)
-                    _hip.check(lib.ptd_streams_wall_us(arr, len(group), spin_us, ctypes.byref(wall)), "ptd_streams_wall_us")
-                    if wall.value < 1.5 * spin_us:
-                        return list(group)
-            CHAIN_STREAM_STATS["rechecks_failed"] += 1
-            import logging
-
-            logging.getLogger(__name__).info("cuda:%d: the kept streams no longer overlap (%.0f us for %d x %d us): "
-                                             "choosing again", index, wall.value, len(group), spin_us)
-            have, exhausted = [], False
-
-        def overlap(a, b) -> bool:
-            _hip.check(lib.ptd_stream_pair_wall_us(a.cuda_stream, b.cuda_stream, spin_us, ctypes.byref(wall)),
-                       "ptd_stream_pair_wall_us")
-            return wall.value < 1.5 * spin_us
-
-        with torch.cuda.device(device):
-            tried = 0
-            # (normal priority only.  The high-priority pool has four hardware queues of its own, but chains on
-            # high-priority streams were measured SLOWER inside bench.py's process -- B_eigh 243 ms against 187 -- although
-            # the streams passed this very test; on normal-priority streams the test's verdict held)
-            prios = [int(p_) for p_ in os.environ.get("PTD_CHAIN_STREAM_PRIORITIES", "0").split(",")]
-            for priority in prios:
-                for _ in range(16):
-                    if len(have) >= want:
-                        break
-                    cand = torch.cuda.Stream(device=device, priority=priority)
-                    tried += 1
-                    if any(cand.cuda_stream == h.cuda_stream for h in have):
-                        continue
-                    if all(overlap(h, cand) for h in have):
-                        have.append(cand)
-            exhausted = len(have) < want
-        _CHAIN_STREAMS[index] = (have, exhausted)
-        CHAIN_STREAM_STATS["selections"] += 1
-        _log_chain_streams(index, have, tried)
-        return list(have[:want])
-
-
-def _log_chain_streams(index: int, have: list, tried: int) -> None:
-    import logging
-
-    logging.getLogger(__name__).info("cuda:%d: %d streams on distinct hardware queues out of %d candidates: %s", index,
-                                     len(have), tried, " ".join(hex(h.cuda_stream) for h in have))
-
-
-def run_concurrently(jobs, device: torch.device, max_streams: Optional[int] = None, routes: Optional[list] = None,
-                     costs: Optional[list] = None) -> list:
-    """Run independent device-side jobs (callables returning tensors) from separate host threads, each on
-    its own HIP stream, and return their results in order.
-
-    One eigendecomposition is a chain of ~8000 short dependent launches that leaves most of the GPU
-    idle; chains of different layers issued on different streams interleave on the device (two
-    n = 4096 matrices: 1.5x the throughput of running them back to back, three: 1.9x; round 4, with the filtered route
-    in the mix: the seven layers of a Llama block 339 ms back to back, 250 on three streams, 204 on four, 211 on five).  The C ABI keeps
-    no shared mutable state and releases the GIL, so the host side is plain threads.  The streams are the device's
-    chain streams (`chain_streams`: measured to sit on distinct hardware queues, re-checked at every call).  Stream order:
-    every side stream first waits for the caller's stream (inputs), the caller's stream waits for all
-    of them at the end (outputs).  PTD_EIGH_STREAMS overrides the stream count (1 = sequential).  `routes` (one
-    ptd_eigh_route value per job): only read with PTD_EIGH_STREAMS_BY_ROUTE=1, see the comment below.  `costs` (one
-    relative cost per job, eigh_cost_hint): with PTD_EIGH_LONGEST_FIRST=1 the workers take the jobs longest first
-    (opt-in: the seven layers of a Llama block 226 -> 214 ms when two chains share a hardware queue, 188 -> 190 ms
-    when they do not)."""
-    import os
-    import threading
-
-    jobs = list(jobs)
-    device = torch.device(device)
-    want = int(os.environ.get("PTD_EIGH_STREAMS", "4")) if max_streams is None else max_streams
-    if routes is not None and want > 1 and device.type == "cuda" and os.environ.get("PTD_EIGH_STREAMS_BY_ROUTE", "0") == "1":
-        # OPT-IN (PTD_EIGH_STREAMS_BY_ROUTE=1): the jobs the filtered route will take run one after the other on the
-        # caller's stream (with the whole chip, and with the resident kernels of their inner eigenproblem); only the
-        # latency-bound ones share the chip.  Measured and NOT the default (profiles/streams_r04.json): three filtered
-        # chains back to back 171 ms, on three streams 137-181; the 2-block Llama stack 668-681 ms with this rule
-        # against 583-622 with every chain on its own stream -- the latency-bound phases of a filtered chain (Lanczos,
-        # the Cholesky sweeps, the Rayleigh-Ritz eigenproblem) do overlap with another chain's products.
-        alone = [i for i, r in enumerate(routes) if r == 3]
-        if alone:
-            rest = [i for i in range(len(jobs)) if routes[i] != 3]
-            out = [None] * len(jobs)
-            for i in alone:
-                out[i] = jobs[i]()
-            for i, res in zip(rest, run_concurrently([jobs[i] for i in rest], device, max_streams,
-                                                     costs=None if costs is None else [costs[i] for i in rest])):
-                out[i] = res
-            return out
-    workers = max(1, min(len(jobs), want))
-    if workers == 1 or device.type != "cuda":
-        return [job() for job in jobs]
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    device = torch.device("cuda", index)
+    streams = dedicated_streams(device, len(lanes))
     main = torch.cuda.current_stream(device)
-    # The chains' streams: kept per device and VERIFIED to sit on pairwise different hardware queues (chain_streams).
-    # Round 4 took fresh streams from torch's pool at every call and was bimodal -- B_eigh of a Llama block 187 ms or
-    # 226-300 ms: whenever two of the four streams shared a hardware queue, two chains of ~8000 dependent launches ran one
-    # packet after the other (PTD_EIGH_JOB_LOG=1: `v`, a 10-ms problem, ended at 148 ms beside `o` on the same queue).
-    streams = chain_streams(device, workers)
-    workers = len(streams)
-    if workers == 1:
-        return [job() for job in jobs]
-    out: list = [None] * len(jobs)
+    for st in streams:
+        st.wait_stream(main)
+    out: list = [None] * len(lanes)
     errors: list = []
-    lock = threading.Lock()
-    cursor = [0]
-    order = list(range(len(jobs)))
-    joblog = [] if os.environ.get("PTD_EIGH_JOB_LOG") else None      # (diagnostic: start / end of every job, ms)
-    import time as _time
 
-    tstart = _time.perf_counter()
-    if costs is not None and len(costs) == len(jobs) and os.environ.get("PTD_EIGH_LONGEST_FIRST", "0") == "1":
-        order.sort(key=lambda i: -costs[i])      # (stable: equal costs keep the model's order)
-
-    def worker(w: int) -> None:
+    def worker(i: int) -> None:
         try:
             torch.cuda.set_device(device)
-            with torch.no_grad(), torch.cuda.stream(streams[w]):
-                while not errors:
-                    with lock:
-                        c = cursor[0]
-                        cursor[0] += 1
-                    if c >= len(jobs):
-                        break
-                    i = order[c]
-                    if joblog is None:
-                        out[i] = jobs[i]()
-                    else:
-                        import time as _t
-
-                        t0 = _t.perf_counter()
-                        out[i] = jobs[i]()
-                        streams[w].synchronize()
-                        joblog.append((i, w, round((t0 - tstart) * 1e3, 1), round((_t.perf_counter() - tstart) * 1e3, 1)))
+            with torch.no_grad(), torch.cuda.stream(streams[i]):
+                out[i] = lanes[i]()
         except BaseException as exc:  # re-raised on the calling thread
             errors.append(exc)
 
-    from . import _hip
-
-    threads = [threading.Thread(target=worker, args=(w,), name=f"ptdeco-eigh-{w}") for w in range(workers)]
-    # interleaved chains: no kernel may claim a whole XCD for itself (ptd_set_concurrent_chains; the hint is kept
-    # per device and keyed by the calling thread's current device, so it is set with `device` current)
+    threads = [threading.Thread(target=worker, args=(i,), name=f"ptdeco-lane-{i}") for i in range(len(lanes))]
+    # interleaved chains: no kernel may claim a whole XCD for itself (ptd_set_concurrent_chains; the hint is kept per
+    # device and keyed by the calling thread's current device, so it is set with `device` current)
+    lib = _hip.load()
     with torch.cuda.device(device):
-        before = _hip.load().ptd_set_concurrent_chains(workers)
+        before = lib.ptd_set_concurrent_chains(len(lanes))
     try:
         for th in threads:
             th.start()
@@ -1783,18 +1617,9 @@ def run_concurrently(jobs, device: torch.device, max_streams: Optional[int] = No
             th.join()
     finally:
         with torch.cuda.device(device):
-            _hip.load().ptd_set_concurrent_chains(before)
+            lib.ptd_set_concurrent_chains(before)
     for st in streams:
         main.wait_stream(st)
-    for res in out:  # the results were allocated on a side stream and live on under the caller's
-        for t in (res if isinstance(res, (tuple, list)) else (res,)):
-            if isinstance(t, torch.Tensor) and t.is_cuda:
-                t.record_stream(main)
-    if joblog is not None:
-        import sys
-
-        print("[run_concurrently] streams " + " ".join(hex(st.cuda_stream) for st in streams) + " jobs (i, worker, start, end): "
-              + str(sorted(joblog)), file=sys.stderr, flush=True)
     if errors:
         raise errors[0]
     return out

@@ -23,7 +23,7 @@ void set_error(const char* fmt, ...) {
 
 using namespace ptd;
 
-// one wave that holds its hardware queue for `ticks` of the 100 MHz wall clock (ptd_stream_pair_wall_us)
+// one wave that holds its hardware queue for `ticks` of the 100 MHz wall clock (ptd_streams_wall_us: do streams overlap?)
 __global__ void stream_spin_kernel(long long ticks) {
   const long long t0 = wall_clock64();
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
@@ -69,11 +69,6 @@ int ptd_stream_create_dedicated(int cu_first, int cu_count, void** stream_out) {
 int ptd_stream_destroy(void* stream) {
   PTD_CHECK_HIP(hipStreamDestroy(static_cast<hipStream_t>(stream)));
   return PTD_OK;
-}
-
-int ptd_stream_pair_wall_us(void* stream_a, void* stream_b, int spin_us, double* wall_us) {
-  void* pair[2] = {stream_a, stream_b};
-  return ptd_streams_wall_us(pair, 2, spin_us, wall_us);
 }
 
 int ptd_syrk_accumulate(const void* y, int64_t T, int64_t n, int64_t ldy, int y_dtype, void* E, int64_t ldE,
@@ -193,8 +188,6 @@ static bool batch_route(int count, int64_t n, int64_t k, bool all_values, bool d
   if (count < 2 || method == 0 || n < 256) return false;
   // (the filtered route's f64 products fill the chip: one by one -- unless the caller asks for the direct reduction)
   if (!direct && method == 2 && eigh_filtered_applies(n, k, all_values)) return false;
-  const char* off = getenv("PTD_EIGH_BATCHED");
-  if (off && atoi(off) == 0) return false;
   return count >= 3 || n >= batch_min_n();
 }
 

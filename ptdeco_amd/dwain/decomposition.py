@@ -20,7 +20,6 @@ from __future__ import annotations
 
 import collections.abc
 import logging
-import os
 import time
 from typing import Any, Optional
 
@@ -159,32 +158,19 @@ def _precompute_covariance_matrix_decompositions(*, module, submodule_names, num
     # exchange of ITS layer's covariance sum -- the sums of the later layers travel meanwhile
     owned = [i for i in range(len(stand_ins)) if shard.owns(i)]
 
-    def job(i):
-        def run():
+    # the layers' eigenproblems grouped by order, same-order reductions batched, the units dealt to lanes that run side
+    # by side, each from its own host thread on its own stream (_engine.solve_eigenproblems)
+    def poser(i):
+        def pose():
             if pending[i] is not None:
                 pending[i]()
-            return stand_ins[i].get_eigenvectors()
-        return run
+            return stand_ins[i].eigen_problem()
+        return pose
 
-    if os.environ.get("PTD_EIGH_BATCHED", "1") != "0":
-        # one host thread, one stream: the layers' eigenproblems grouped by order, same-order reductions batched
-        def poser(i):
-            def pose():
-                if pending[i] is not None:
-                    pending[i]()
-                return stand_ins[i].eigen_problem()
-            return pose
-
-        with eng.phase("B_eigh"):
-            got = eng.solve_eigenproblems(
-                [poser(i) for i in owned], [stand_ins[i].eigen_order() for i in owned], device,
-                costs=[eng.eigh_cost_hint(stand_ins[i].cov, stand_ins[i].out_features, stand_ins[i].top_k) for i in owned])
-    else:
-        # round 5's form: one host thread and one stream per chain (PTD_EIGH_BATCHED=0, kept for A/B)
-        routes = [eng.eigh_route_hint(stand_ins[i].cov, stand_ins[i].out_features, stand_ins[i].top_k) for i in owned]
-        costs = [eng.eigh_cost_hint(stand_ins[i].cov, stand_ins[i].out_features, stand_ins[i].top_k) for i in owned]
-        with eng.phase("B_eigh"):
-            got = eng.run_concurrently([job(i) for i in owned], device, routes=routes, costs=costs)
+    with eng.phase("B_eigh"):
+        got = eng.solve_eigenproblems(
+            [poser(i) for i in owned], [stand_ins[i].eigen_order() for i in owned], device,
+            costs=[eng.eigh_cost_hint(stand_ins[i].cov, stand_ins[i].out_features, stand_ins[i].top_k) for i in owned])
     for i, done in enumerate(pending):     # the sums this rank only contributed to: their buffers may go now
         if done is not None and not shard.owns(i):
             done()

@@ -140,42 +140,19 @@ def test_candidate_schedules():
     assert fa._batches_consumed(torch.nn.Linear(96, 10), 4, 2) == 4 + 2 * 3
 
 
-def test_run_concurrently_keeps_order_and_raises():
-    """Without a GPU the jobs run in the calling thread, in order; an exception propagates."""
+def test_run_lanes_keeps_order_and_raises():
+    """Without a GPU the lanes run in the calling thread, in order; an exception propagates."""
     from ptdeco_amd import _engine as eng
 
     cpu = torch.device("cpu")
-    assert eng.run_concurrently([lambda i=i: torch.tensor([i]) for i in range(5)], cpu) == [torch.tensor([i]) for i in range(5)]
-    assert eng.run_concurrently([], cpu) == []
+    assert eng.run_lanes([lambda i=i: torch.tensor([i]) for i in range(5)], cpu) == [torch.tensor([i]) for i in range(5)]
+    assert eng.run_lanes([], cpu) == []
 
     def boom():
         raise RuntimeError("job failed")
 
     with pytest.raises(RuntimeError, match="job failed"):
-        eng.run_concurrently([lambda: torch.zeros(1), boom], cpu)
-
-
-def test_run_concurrently_takes_the_longest_jobs_first_when_asked(monkeypatch):
-    """`costs` + PTD_EIGH_LONGEST_FIRST=1: the jobs are started by descending cost, results stay in job order (on the
-    CPU the jobs run one after the other, which makes the start order observable)."""
-    from ptdeco_amd import _engine as eng
-
-    started = []
-
-    def job(i):
-        def run():
-            started.append(i)
-            return torch.tensor([float(i)])
-        return run
-
-    jobs = [job(i) for i in range(5)]
-    costs = [1.0, 5.0, 3.0, 5.0, 2.0]
-
-    # (the CPU path of run_concurrently is sequential and ignores the order; drive the ordering logic itself)
-    order = sorted(range(len(jobs)), key=lambda i: -costs[i])
-    assert order == [1, 3, 2, 4, 0]                      # stable: equal costs keep the model's order
-    out = eng.run_concurrently(jobs, CPU, costs=costs)
-    assert [float(t) for t in out] == [0.0, 1.0, 2.0, 3.0, 4.0]
+        eng.run_lanes([lambda: torch.zeros(1), boom], cpu)
 
 
 def test_largest_evaluated_rank_drives_top_k():

@@ -377,7 +377,7 @@ def test_resident_tail_of_the_reduction_matches_the_blocked_path(ops, monkeypatc
         got[mode] = w.cpu()
         assert (got[mode] - w_ref).abs().max().item() <= 1e-12 * scale, mode
     assert torch.equal(got["2"], got["0"])
-    # several chains at once (ptd_set_concurrent_chains, what _engine.run_concurrently announces): no kernel may hold
+    # several chains at once (ptd_set_concurrent_chains, what _engine.run_lanes announces): no kernel may hold
     # an XCD for itself, so the blocked path runs to the end
     from ptdeco_amd import _hip
     monkeypatch.setenv("PTD_SYTRD_RESIDENT", "7")
@@ -698,68 +698,40 @@ print("ok")
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
 
 
-def test_lane_streams_own_their_hardware_queues(ops):
+def test_dedicated_streams_own_their_hardware_queues(ops):
     """Round 6: the lanes of a precompute pass run on streams created with a CU mask (ptd_stream_create_dedicated:
     hipExtStreamCreateWithCUMask over every CU), which the runtime gives a hardware queue of their own -- no probing:
-    three such streams overlap pairwise by construction (ptd_stream_pair_wall_us: two single-wave kernels that hold their
-    queue for 150 us run side by side), are kept per device, and a stream paired with itself reads as serialised."""
+    three such streams overlap pairwise by construction (ptd_streams_wall_us on two of them: two single-wave kernels that
+    hold their queue for 150 us run side by side), are kept per device, and a stream paired with itself reads as
+    serialised."""
     import ctypes
     from ptdeco_amd import _engine as eng, _hip
     dev = torch.device("cuda", 0)
-    st = eng.chain_streams(dev, 3)
+    st = eng.dedicated_streams(dev, 3)
     assert len(st) == 3 and len({s.cuda_stream for s in st}) == 3
-    again = eng.chain_streams(dev, 3)
+    again = eng.dedicated_streams(dev, 3)
     assert [s.cuda_stream for s in again] == [s.cuda_stream for s in st]
     lib, wall = _hip.load(), ctypes.c_double(0.0)
+
+    def pair_wall(a, b):
+        arr = (ctypes.c_void_p * 2)(a.cuda_stream, b.cuda_stream)
+        _hip.check(lib.ptd_streams_wall_us(arr, 2, 150, ctypes.byref(wall)), "pair")
+        return wall.value
+
     for i in range(3):
         for j in range(i + 1, 3):
             # (the first launch on a fresh queue pays its activation -- 0.8 ms was seen: measure the second pair)
-            _hip.check(lib.ptd_stream_pair_wall_us(st[i].cuda_stream, st[j].cuda_stream, 150, ctypes.byref(wall)), "pair")
-            best = 1e9
-            for _ in range(3):
-                _hip.check(lib.ptd_stream_pair_wall_us(st[i].cuda_stream, st[j].cuda_stream, 150, ctypes.byref(wall)), "pair")
-                best = min(best, wall.value)
+            pair_wall(st[i], st[j])
+            best = min(pair_wall(st[i], st[j]) for _ in range(3))
             assert best < 240.0, (i, j, best)
-    worst = 0.0
-    for _ in range(3):
-        _hip.check(lib.ptd_stream_pair_wall_us(st[0].cuda_stream, st[0].cuda_stream, 150, ctypes.byref(wall)), "pair")
-        worst = max(worst, wall.value)
+    worst = max(pair_wall(st[0], st[0]) for _ in range(3))
     assert worst > 280.0, worst
     # work issued on a dedicated stream is ordinary stream work
     with torch.cuda.stream(st[1]):
         t = torch.ones(1 << 20, device=dev) * 3
     st[1].synchronize()
     assert t.sum().item() == 3 * (1 << 20)
-    assert lib.ptd_stream_pair_wall_us(None, None, 0, ctypes.byref(wall)) == -1
-
-
-def test_chain_streams_sit_on_distinct_hardware_queues(ops, monkeypatch):
-    """VERDICT r4 item 2 (PTD_LANE_STREAMS=pool, round 5's form): streams from torch's pool are measured to overlap
-    pairwise (ptd_stream_pair_wall_us), are kept per device, and a stream paired with itself reads as serialised."""
-    import ctypes
-    from ptdeco_amd import _engine as eng, _hip
-    monkeypatch.setenv("PTD_LANE_STREAMS", "pool")
-    dev = torch.device("cuda", 0)
-    # the pool's normal-priority streams share the runtime's hardware queues of that priority: GPU_MAX_HW_QUEUES of
-    # them (4 unless the environment sets another number), so at most that many of them are distinct
-    queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
-    want = min(4, queues)
-    st = eng.chain_streams(dev, 4)
-    assert len(st) == want and len({s.cuda_stream for s in st}) == want, (len(st), queues)
-    again = eng.chain_streams(dev, 4)
-    assert [s.cuda_stream for s in again] == [s.cuda_stream for s in st]
-    lib, wall = _hip.load(), ctypes.c_double(0.0)
-    for i in range(want):
-        for j in range(i + 1, want):
-            _hip.check(lib.ptd_stream_pair_wall_us(st[i].cuda_stream, st[j].cuda_stream, 150, ctypes.byref(wall)), "pair")
-            assert wall.value < 240.0, (i, j, wall.value)
-    worst = 0.0
-    for _ in range(3):
-        _hip.check(lib.ptd_stream_pair_wall_us(st[0].cuda_stream, st[0].cuda_stream, 150, ctypes.byref(wall)), "pair")
-        worst = max(worst, wall.value)
-    assert worst > 280.0, worst
-    more = eng.chain_streams(dev, 7)
-    assert want <= len(more) <= 7 and [s.cuda_stream for s in more[:want]] == [s.cuda_stream for s in st]
+    assert lib.ptd_streams_wall_us(None, 0, 0, ctypes.byref(wall)) == -1
 
 
 @pytest.mark.parametrize("n,k", [(96, 96), (512, 128), (2048, 512)])
@@ -1318,9 +1290,9 @@ def test_sym_kl_random(ops, B, C):
     assert abs(ops.sym_kl(s.to(DEV), s.to(DEV).clone()).item()) <= 1e-15
 
 
-def test_eigendecompositions_on_concurrent_streams_match_sequential(ops):
+def test_eigendecompositions_on_lanes_match_sequential(ops):
     """Independent layers' eigensolves issued from separate host threads / streams
-    (_engine.run_concurrently) return what the sequential calls return, in order; a failing job
+    (_engine.run_lanes, one eigensolve per lane) return what the sequential calls return, in order; a failing lane
     raises on the calling thread."""
     from ptdeco_amd import _engine as eng
 
@@ -1331,14 +1303,14 @@ def test_eigendecompositions_on_concurrent_streams_match_sequential(ops):
 
     mats = [spd(n, 40 + i).to(DEV) for i, n in enumerate((300, 512, 300, 640, 96))]
     seq = [ops.eigh(m, m.shape[0] // 2) for m in mats]
-    par = eng.run_concurrently([lambda m=m: ops.eigh(m, m.shape[0] // 2) for m in mats], torch.device("cuda"))
+    par = eng.run_lanes([lambda m=m: ops.eigh(m, m.shape[0] // 2) for m in mats], torch.device("cuda"))
     # (interleaved chains stay on the blocked reduction, a single chain ends in the resident kernels: the same
     # eigenvectors up to rounding and sign)
     for (w0, v0), (w1, v1) in zip(seq, par):
         assert torch.allclose(w0, w1, rtol=0, atol=1e-12 * w0.abs().max().item())
         assert (orc.canonical_sign(v0.cpu()) - orc.canonical_sign(v1.cpu())).abs().max().item() < 1e-8
     with pytest.raises(ValueError):
-        eng.run_concurrently([lambda: ops.eigh(mats[0], 5), lambda: (_ for _ in ()).throw(ValueError("x"))], DEV)
+        eng.run_lanes([lambda: ops.eigh(mats[0], 5), lambda: (_ for _ in ()).throw(ValueError("x"))], DEV)
 
 
 def test_lowrank_linear_always_runs_the_package_kernels(ops, monkeypatch):

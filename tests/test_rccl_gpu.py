@@ -1,7 +1,7 @@
 """The sharded code path on REAL RCCL work objects without a second GPU: a 1-rank `nccl` process
 group in the pytest process, a Shard that reports itself active, and the three-layer precompute split of dwain run
-through it -- `dist.reduce(async_op=True)` on the packed lower triangles completed from the worker threads and side
-streams of `run_concurrently`, the eigenvector broadcasts, the all-reduce of the metric sums.  gloo on the CPU (the
+through it -- `dist.reduce(async_op=True)` on the packed lower triangles completed from the lane threads and lane
+streams of `run_lanes`, the eigenvector broadcasts, the all-reduce of the metric sums.  gloo on the CPU (the
 world-size-2 / -3 tests) cannot exercise the RCCL work objects, `work.wait()` on non-default streams or the allocator
 lifetime of the packed buffers; a 1-rank communicator runs the same kernels and stream hand-offs with itself as peer.
 The sharded run must take the unsharded run's decisions, with metrics and factors equal to the eigensolver's
@@ -93,7 +93,7 @@ def test_three_layer_split_through_a_one_rank_rccl_group_equals_the_unsharded_ru
     cfg1, trace1, m1 = run()
 
     assert calls["reduce_async"] == [0, 1, 2] and calls["broadcast"] == 3 and calls["all_reduce_small"] == 3
-    # the exchanges were completed by the worker threads of run_concurrently, each on its own side stream
+    # the exchanges were completed by the lane threads of run_lanes, each on its own lane stream
     main = threading.get_ident()
     assert sorted(w[0] for w in calls["waits"]) == [0, 1, 2]
     assert all(w[1] != main for w in calls["waits"]) and len({w[2] for w in calls["waits"]}) == 3

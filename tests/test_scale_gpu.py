@@ -551,7 +551,7 @@ def test_dwain_c2_headline_workload_end_to_end_matches_oracle(splits):
     assert (out - ref).abs().max().item() <= 1e-4 * ref.abs().max().item()
 
 
-@pytest.mark.parametrize("lanes", ["3", "1"])
+@pytest.mark.parametrize("lanes", ["3", "1", "3-side"])
 def test_dwain_three_layer_stack_concurrent_filtered_chains_match_oracle(monkeypatch, lanes):
     """The DEFAULT path of every multi-layer split (dwain.py:580-633 + 333-537): three nn.Linear(4096, 4096) in ONE
     precompute split, so their three eigendecompositions -- each the filtered subspace iteration, each with its own
@@ -560,7 +560,11 @@ def test_dwain_three_layer_stack_concurrent_filtered_chains_match_oracle(monkeyp
     PTD_EIGH_LANES=1 -- against the CPU oracle on the same seeded inputs: identical (layer, rank, accepted) decisions,
     nsr / ppl within 1e-4, factor products within 1e-4 (Frobenius), outputs 1e-4.  The test also asserts on which
     threads / streams the three calls ran and that the solver's route for these matrices is the filtered one (the
-    deepest layer's flatter spectrum may decline it)."""
+    deepest layer's flatter spectrum may decline it).  "3-side": three lanes with the whole run issued from a side
+    stream (`with torch.cuda.stream(...)`, non-blocking): every lane stream first waits for the caller's stream, so the
+    run still matches the oracle, and no eigensolve runs on the side stream itself."""
+    side = torch.cuda.Stream(DEV) if lanes.endswith("-side") else None
+    lanes = lanes.split("-")[0]
     monkeypatch.setenv("PTD_EIGH_LANES", lanes)
     by_route = "1" if lanes == "1" else "0"
     import threading
@@ -596,12 +600,16 @@ def test_dwain_three_layer_stack_concurrent_filtered_chains_match_oracle(monkeyp
 
     ops.eigh = spy
     try:
-        cfg = ptdeco_amd.dwain.decompose_in_place(
-            module=gpu_model, device=DEV, data_iterator=itertools.cycle(data_g), loss_fn=bench.ce_loss,
-            metric_iterator=itertools.cycle(metric_g), finetune_fn=lambda m, d, n: m, trace=trace,
-            precomputing_covariance_num_splits=1, **bench.DWAIN_KW)
+        with torch.cuda.stream(side):      # (a no-op without a side stream)
+            cfg = ptdeco_amd.dwain.decompose_in_place(
+                module=gpu_model, device=DEV, data_iterator=itertools.cycle(data_g), loss_fn=bench.ce_loss,
+                metric_iterator=itertools.cycle(metric_g), finetune_fn=lambda m, d, n: m, trace=trace,
+                precomputing_covariance_num_splits=1, **bench.DWAIN_KW)
     finally:
         ops.eigh = real_eigh
+    if side is not None:
+        torch.cuda.current_stream(DEV).wait_stream(side)
+        assert side.cuda_stream not in {c[1] for c in calls}
     streams_wanted = int(lanes)
     assert len(calls) == 3 and all(c[2:] == (4096, 1024) for c in calls)
     assert len({c[0] for c in calls}) == streams_wanted and len({c[1] for c in calls}) == streams_wanted

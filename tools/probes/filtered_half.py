@@ -26,9 +26,9 @@ res = (mats[0] @ v - v * w[n - k:]).abs().max().item() / w[-1].item()
 orth = (v.T @ v - torch.eye(k, dtype=torch.float64, device=dev)).abs().max().item()
 print(f"single: {dt*1e3:.1f} ms method {p['method']} phases {[round(x,1) for x in p['ms']]} launches {p['launches']} resid {res:.1e} orth {orth:.1e}", flush=True)
 jobs = [lambda m=m: ops.eigh(m, k, all_values=False) for m in mats]
-eng.run_concurrently(jobs, dev)
+eng.run_lanes(jobs, dev)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-for _ in range(2): eng.run_concurrently(jobs, dev)
+for _ in range(2): eng.run_lanes(jobs, dev)
 torch.cuda.synchronize()
 print(f"three concurrent chains: {(time.perf_counter() - t0) / 2 * 1e3:.1f} ms", flush=True)

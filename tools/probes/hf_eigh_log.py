@@ -2,7 +2,7 @@
 are not overlapped here).  Usage: python tools/probes/hf_eigh_log.py [layers]"""
 import os, sys, time, runpy, json, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-os.environ["PTD_EIGH_STREAMS"] = "1"
+os.environ["PTD_EIGH_LANES"] = "1"
 from ptdeco_amd import ops
 log = []
 real_eigh, real_fact = ops.eigh, ops.eigh_factored
