@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: dwain layers decomposed per second on MI355X (BASELINE.json `metric`).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W            # the headline alone
+    python bench.py --gpus N --steps K --warmup W --full     # + every side measurement below
 
 ONE fixed workload at every N (strong scaling): BASELINE configs[3] at reduced depth -- dwain.decompose_in_place
 (reference src/ptdeco/dwain/decomposition.py:677-800) of a stack of TWO Llama-3-8B-width blocks (q, k, v, o, gate, up,
@@ -13,10 +14,15 @@ resident in HBM; `value` = 14 layers x K / time.  With N ranks: calibration step
 the ranks, packed covariance sums reduced to the layer owners over RCCL, eigenvectors broadcast (sharding.py).
 `python bench.py --gpus N` starts its own N ranks when no launcher did (children, before any GPU call).
 
+A plain run does only what `value` needs: it builds the workload, runs the W warm-up and K timed steps, writes
+--dump-outputs if asked and prints the line (the contract keys, `spread` and `step_ms`); it writes no detail file.
+Everything else runs with --full only, after the timed steps, and is what the next paragraph describes.
+
 Output: the LAST stdout line is ONE compact JSON object (<= 4096 bytes: the driver keeps the tail of stdout) with the
-contract keys, `roofline` (the dominant package kernel of the headline step, measured live with HIP events) and
-`cpu_baseline` (the CPU oracle on one layer of the stack's shapes, host cores of this box), plus scalars for the
-other BASELINE configs: c2_* (configs[1]: ONE nn.Linear(4096, 4096), D = 4, M = 2), c3_* (configs[2]: falor on a
+contract keys.  With --full it also carries `roofline` (the dominant package kernel of the headline step, measured live
+with HIP events), `phases_ms` (one more, untimed step with the phase spans) and `cpu_baseline` (the CPU oracle on one
+layer of the stack's shapes, host cores of this box), plus scalars for the other BASELINE configs: c2_* (configs[1]:
+ONE nn.Linear(4096, 4096), D = 4, M = 2), c3_* (configs[2]: falor on a
 ViT-B/16-shaped clone, depth 12, batch 8, D = 5, M = 5, use_mean=False, use_damping=True), c1_cpu_s (configs[0]: the
 CPU oracle's falor on the resnet18-shaped clone, one batch).  Everything else -- per-kernel lines, the decomposed
 forward (configs[4]), per-shape and one-block Llama lines, eigensolver phases -- goes to bench_detail.json beside this
@@ -785,15 +791,22 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-full", action="store_true", help="cpu_baseline: time the gate/up shape live too (+65 s)")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed headline (+ C2 at N = 1): no side measurements")
-    ap.add_argument("--no-c3", action="store_true", help="skip BASELINE configs[2] (falor ViT-B/16 clone) and configs[0]")
-    ap.add_argument("--no-c4", action="store_true", help="skip the per-shape / one-block Llama detail lines")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every side measurement too (phases and roofline of one more step, "
+                         "configs[1], the other configs, kernel lines, CPU baselines) and write the detail file; "
+                         "without it the run times the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--cpu-full", action="store_true",
+                    help="with --full: time the gate/up shape of cpu_baseline live too (+65 s)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: only the timed headline (+ C2 at N = 1): no side measurements")
+    ap.add_argument("--no-c3", action="store_true",
+                    help="with --full: skip BASELINE configs[2] (falor ViT-B/16 clone) and configs[0]")
+    ap.add_argument("--no-c4", action="store_true", help="with --full: skip the per-shape / one-block Llama detail lines")
     ap.add_argument("--blocks", type=int, default=HEADLINE_BLOCKS, help="Llama blocks of the headline stack")
     ap.add_argument("--workload", choices=("c4", "c2"), default="c4",
                     help="c2: time BASELINE configs[1] alone (one layer; for kernel traces); default: the Llama stack")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"))
+    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="the detail file of a --full run")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (the decomposed model's "
                          "parameters, a fixed seeded sample of the large ones, and its decompose_config figures) as "
@@ -915,6 +928,15 @@ def measure(args):
                    "parallelism": f"dp{world}" if world > 1 else "single"},
         "spread": (max(marks) - min(marks)) / med,
     }
+    if not args.full:
+        # a plain run: the headline alone -- no further step, side measurement or detail file
+        result["step_ms"] = marks
+        del step
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return result if rank == 0 else None
+
     detail = {"step_ms": marks, "replaced": kept(cfg),
               "metric_forwards": "every (candidate, batch) pair runs the stack twice as the reference does; the second run "
                                  "reuses the layer outputs ahead of the analysed layer that the first run of the SAME pair just "

@@ -89,6 +89,30 @@ def test_compact_line_never_exceeds_the_limit_even_with_absurd_blocks():
     assert isinstance(line["roofline"], dict) and isinstance(line["cpu_baseline"], dict)
 
 
+def test_plain_run_prints_the_headline_line_and_writes_no_detail_file(capsys, tmp_path):
+    """A plain run (no --full) hands main() the headline alone: the line carries the contract keys and no detail file
+    is written."""
+    res = {k: v for k, v in _fat_result().items() if k in bench.CONTRACT_KEYS + ("spread",)}
+    res["step_ms"] = [780.1, 779.4, 781.0]
+    detail = tmp_path / "bench_detail.json"
+    seen = []
+    rc = bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--detail", str(detail)],
+                    measure_fn=lambda args: seen.append(args.full) or res)
+    assert rc == 0 and seen == [False]
+    line = json.loads(capsys.readouterr().out.rstrip("\n").split("\n")[-1])
+    for key in bench.CONTRACT_KEYS:
+        assert key in line, key
+    for key in ("value", "ms_per_step"):            # (the line keeps six significant digits)
+        assert abs(line[key] - res[key]) <= 1e-5 * res[key], key
+    assert line["detail"] is None and not detail.exists()
+
+
+def test_full_is_off_by_default():
+    assert bench.parse_args([]).full is False
+    args = bench.parse_args(["--full", "--steps", "2", "--warmup", "0", "--no-cpu-baseline"])
+    assert args.full and args.steps == 2 and args.warmup == 0 and args.no_cpu_baseline
+
+
 def test_ranks_other_than_zero_print_nothing(capsys, tmp_path):
     rc = bench.main(["--gpus", "1", "--detail", str(tmp_path / "d.json")], measure_fn=lambda args: None)
     assert rc == 0 and capsys.readouterr().out == ""

@@ -39,7 +39,7 @@ def split_note(kernel):
 
 
 o = [f"# profiles -- round {int(rnd)} (one MI355X, ROCm 7.2, gpurun box)\n\n", "Files:\n\n",
-     f"* `bench_r{rnd}.json` -- `python bench.py --steps 5 --warmup 1` (the driver's contract line plus roofline / eigh / kernels / cpu_baseline / decomposed_fwd)\n",
+     f"* `bench_r{rnd}.json` -- `python bench.py --full --steps 5 --warmup 1` (the driver's contract line plus roofline / eigh / kernels / cpu_baseline / decomposed_fwd)\n",
      f"* `rocprofv3_kernel_stats_r{rnd}.csv` -- `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-extras` (4 decompositions)\n",
      f"* `c4_shapes_f32_r{rnd}.json` -- `python tools/c4_shapes.py`: dwain on one layer of each Llama-3-8B shape (BASELINE configs[3]), 224-layer figure extrapolated\n",
      f"* `c4_shapes_bf16_r{rnd}.json`, `c4_stack_2blocks_r{rnd}.json` -- the same in bf16; `python tools/c4_stack.py 2 [bf16]` end to end on a 2-block full-width stack\n",
@@ -50,7 +50,7 @@ o = [f"# profiles -- round {int(rnd)} (one MI355X, ROCm 7.2, gpurun box)\n\n", "
      f"* `filtered_probe_r{rnd}.json`, `f64_gemm_probe_r{rnd}.json` -- `tools/filtered_probe.py` (filtered vs direct route vs LAPACK), `tools/chefsi_probe.py` (f64 product rates at the route's shapes, beside torch / rocBLAS)\n",
      f"* `c4_stack_32blocks_bf16_r{rnd}.json` -- `PTD_PHASES=1 python tools/c4_stack.py 32 bf16`: BASELINE configs[3] at full depth on one GPU\n",
      f"* `c4_shapes_cpu_r{rnd}.json` -- `python tools/c4_shapes_cpu.py`: the CPU oracle on one layer of each Llama-3-8B shape, host cores of the GPU box\n",
-     f"* `bench_r{rnd}_rehearsal_2ranks_1gpu.json` -- `PTD_BENCH_REHEARSE=1 python bench.py --gpus 2` (self-launched; two ranks sharing the one GPU over gloo: a functional check of the N > 1 path, not a measurement)\n",
+     f"* `bench_r{rnd}_rehearsal_2ranks_1gpu.json` -- `PTD_BENCH_REHEARSE=1 python bench.py --full --gpus 2` (self-launched; two ranks sharing the one GPU over gloo: a functional check of the N > 1 path, not a measurement)\n",
      f"* `gpu_tests_r{rnd}.log` -- `python -m pytest tests -q -m gpu` on the same box\n",
      "* `tools/refresh_profiles.sh` reruns the first four on a GPU box\n\n", "## Headline\n\n"]
 cb = b.get("cpu_baseline")

@@ -2,7 +2,8 @@
 # Regenerates the measurements under profiles/ on a GPU box:  bash tools/refresh_profiles.sh <round, e.g. 02> [part]
 # part: all (default) | main (tests + bench + kernel stats) | c4 (= c4gpu + c4cpu) | pmc.  Outputs land in gpurun_out/ and are
 # condensed / copied into profiles/ afterwards in the build container (tools/pmc_summary.py, pmc_mfma_summary.py,
-# make_profiles_readme.py).
+# make_profiles_readme.py).  The bench part writes the bench line, its detail file and the rocprofv3 summary of the
+# full bench command to $OUT, the folder the caller collects the outputs from (OUT=<dir> bash tools/refresh_profiles.sh ...).
 set -o pipefail
 R=${1:-02}; PART=${2:-all}
 cd $GRAFT_REPO_ROOT
@@ -10,9 +11,11 @@ if [ "$PART" = all ] || [ "$PART" = main ]; then
   timeout -k 10 1100 python -m pytest tests -q -m gpu > gpurun_out/gpu_tests_r$R.log 2>&1; echo "tests rc=$?"; tail -2 gpurun_out/gpu_tests_r$R.log
 fi
 if [ "$PART" = all ] || [ "$PART" = main ] || [ "$PART" = bench ]; then
-  timeout -k 10 500 python bench.py --steps 5 --warmup 1 > gpurun_out/bench_r$R.txt 2> gpurun_out/bench_r$R.err; echo "bench rc=$?"
-  tail -1 gpurun_out/bench_r$R.txt > gpurun_out/bench_r$R.json; cp bench_detail.json gpurun_out/bench_detail_r$R.json
-  cut -c1-200 gpurun_out/bench_r$R.json
+  : "${OUT:?set OUT to the folder the outputs are collected in}"; mkdir -p "$OUT"; OUT=$(cd "$OUT" && pwd); TREE=$PWD
+  # --full: the line with every side figure, and bench_detail.json with every side block
+  timeout -k 10 500 python bench.py --full --steps 5 --warmup 1 > $OUT/bench_r$R.txt 2> $OUT/bench_r$R.err; echo "bench rc=$?"
+  tail -1 $OUT/bench_r$R.txt > $OUT/bench_r$R.json; cp bench_detail.json $OUT/bench_detail_r$R.json
+  cut -c1-200 $OUT/bench_r$R.json
   rm -rf $GRAFT_REPO_ROOT/gpurun_out/prof_r$R   # (earlier runs leave PID-named files beside the new ones)
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_r$R -- python3 $GRAFT_REPO_ROOT/bench.py --workload c2 --steps 3 --warmup 1 --no-extras > $GRAFT_REPO_ROOT/gpurun_out/prof_r$R.log 2>&1); echo "rocprof rc=$?"
   # the dominant kernel's launches split by duration (the long C X products / the shorter X W ones), then drop the raw
@@ -32,11 +35,11 @@ if f:
               open("gpurun_out/roofline_kernel_split_r$R.json", "w"), indent=1)
 PY
   rm -f gpurun_out/prof_r$R/*/*kernel_trace.csv
-  # the same for the DEFAULT command the driver runs (the fixed stack as `value`, every side block; the CPU baseline, which
-  # launches no kernels, left out): which kernels the whole bench spends its device time in
-  rm -rf $GRAFT_REPO_ROOT/gpurun_out/prof_default_r$R
-  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_default_r$R -- python3 $GRAFT_REPO_ROOT/bench.py --gpus 1 --steps 5 --warmup 1 --no-cpu-baseline > $GRAFT_REPO_ROOT/gpurun_out/prof_default_r$R.log 2>&1); echo "rocprof default rc=$?"
-  rm -f gpurun_out/prof_default_r$R/*/*kernel_trace.csv
+  # the same for the full bench command (the fixed stack as `value`, every side block; the CPU baseline, which launches
+  # no kernels, left out): which kernels the whole bench spends its device time in
+  rm -rf $OUT/prof_default_r$R
+  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_default_r$R -- python3 $TREE/bench.py --full --gpus 1 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof_default_r$R.log 2>&1); echo "rocprof default rc=$?"
+  rm -f $OUT/prof_default_r$R/*/*kernel_trace.csv
 fi
 if [ "$PART" = all ] || [ "$PART" = c4 ] || [ "$PART" = c4gpu ]; then
   timeout -k 10 300 python tools/c4_shapes.py > gpurun_out/c4_f32_r$R.json 2> gpurun_out/c4_f32.err; echo "c4 f32 rc=$?"
