@@ -31,13 +31,14 @@
 extern "C" {
 #endif
 
-#define PTD_ABI_VERSION 5   /* 2: ptd_nsr workspaces are initialised once (ptd_nsr_workspace_init); ptd_chol_inverse
+#define PTD_ABI_VERSION 6   /* 2: ptd_nsr workspaces are initialised once (ptd_nsr_workspace_init); ptd_chol_inverse
                              * 3: ptd_streams_wall_us and a two-stream form of it, ptd_syrk_accumulate_multi
                              * 4: ptd_eigh_topk_batched, ptd_eigh_factored_prepare / _finish; ptd_band_reduce and the
                              *    two-stage reduction behind it are gone (2.2 x behind the default for three rounds)
-                             * 5: the two-stream form of ptd_streams_wall_us is gone (the same call with count = 2) */
+                             * 5: the two-stream form of ptd_streams_wall_us is gone (the same call with count = 2)
+                             * 6: PTD_F16 (IEEE half) wherever PTD_BF16 is accepted, same shapes, workspaces and codes */
 
-typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2 } ptd_dtype;
+typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
 typedef enum {
   PTD_OK = 0,
@@ -83,7 +84,7 @@ int ptd_stream_destroy(void* stream);
 /* ---- covariance accumulation ------------------------------------------- */
 
 /* E[i][j] += scale * sum_t Y[t][i] * Y[t][j]  for i >= j  (LOWER triangle only;
- * ptd_cov_finalize mirrors it).  Y is [T, n] (f32 or bf16), E is [n, n] (f64 or f32).
+ * ptd_cov_finalize mirrors it).  Y is [T, n] (f32, bf16 or f16), E is [n, n] (f64 or f32).
  * The product is accumulated in f32 on the matrix cores and promoted on the add.
  * Replaces `Eyyt += einsum("bp,bq->pq", y, y) / T`: dwain.py:147-152, falor.py:160. */
 int ptd_syrk_accumulate(const void* y, int64_t T, int64_t n, int64_t ldy, int y_dtype,
@@ -95,12 +96,12 @@ int ptd_syrk_accumulate(const void* y, int64_t T, int64_t n, int64_t ldy, int y_
  * called once per calibration step (D times per layer) and each call reads and writes the live triangle of the f64
  * accumulator: 8 n (n + 1) bytes against 2 T n of bf16 activations -- at n = 4096, T = 2048 that traffic, not the
  * matrix cores, bounds the call.  Here a tile's f64 sum stays in registers across the steps (each step's f32 product
- * is promoted at its end, in step order) and E is read and written once.  bf16: one launch per 8 steps; f32 (bound by
+ * is promoted at its end, in step order) and E is read and written once.  bf16 / f16: one launch per 8 steps; f32 (bound by
  * the matrix cores): step by step, identical to `steps` calls of ptd_syrk_accumulate. */
 int ptd_syrk_accumulate_multi(const void* const* ys, int steps, int64_t T, int64_t n, int64_t ldy, int y_dtype,
                               void* E, int64_t ldE, int E_dtype, double scale, void* stream);
 
-/* ey[j] += scale * sum_t Y[t][j].   Replaces `Ey += y.mean(dim=0)`: falor.py:161. */
+/* ey[j] += scale * sum_t Y[t][j], Y f32, bf16 or f16.   Replaces `Ey += y.mean(dim=0)`: falor.py:161. */
 int ptd_colsum_accumulate(const void* y, int64_t T, int64_t n, int64_t ldy, int y_dtype,
                           void* ey, int ey_dtype, double scale, void* stream);
 
@@ -200,7 +201,7 @@ void ptd_eigh_forget_declines(void);
 int ptd_eigh_route(int64_t n, int64_t k, int all_values);
 
 /* Top-k eigenpairs of C = W Ex W^T without forming C, for a layer that widens its input
- * (n_o > n_i; Llama gate / up: 4096 -> 14336): W [n_o, n_i] (f32, bf16 or f64, ld ldw),
+ * (n_o > n_i; Llama gate / up: 4096 -> 14336): W [n_o, n_i] (f32, bf16, f16 or f64, ld ldw),
  * Ex [n_i, n_i] f64 full symmetric = sum over steps of x^T x / T / steps (the INPUT second
  * moment; C is then exactly the feature covariance the reference accumulates, dwain.py:147-152,
  * since y = x W^T).  U [n_o, k] f64 gets the eigenvectors of the k largest eigenvalues
@@ -271,11 +272,12 @@ int ptd_chol_inverse(double* G, int64_t m, double* Wt, void* ws, size_t ws_bytes
 
 /* ---- dense products (layer output, factor construction) ----------------- */
 
-/* C[M,N] = alpha * sum_k A(m,k) * B(k,n) (+ bias[n]),  f32 or bf16 operands,
+/* C[M,N] = alpha * sum_k A(m,k) * B(k,n) (+ bias[n]),  f32, bf16 or f16 operands,
  * f32 accumulation on the matrix cores.  Operands are addressed with explicit
  * element strides: A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn]; exactly
  * one stride of each operand must be 1.  C is row-major [M, N] with ld ldc, of
- * dtype c_dtype (f32, or bf16 when the inputs are bf16; f64 x f64 -> f64 without bias
+ * dtype c_dtype (f32, or the operands' type when they are bf16 or f16 -- bias of that type too, 16-bit results rounded
+ * to nearest even, f16 beyond +-65504 to +-inf; f64 x f64 -> f64 without bias
  * is also available, it is what the eigensolver uses internally).
  * Replaces `x @ weight.T` (dwain.py:194, 239; falor.py:159), `orig_weight.T @ uk`
  * and `(U @ V).T` (dwain.py:427-429, 511; falor.py:347-348). */
@@ -293,7 +295,7 @@ int ptd_gemm_ws(const void* A, int64_t sam, int64_t sak, const void* B, int64_t 
                 void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int ab_dtype, int c_dtype,
                 double alpha, const void* bias, void* ws, size_t ws_bytes, void* stream);
 
-/* y[T,n_o] = (x[T,n_i] @ A[r,n_i]^T) @ B[n_o,r]^T (+ bias[n_o]).  The workspace holds the
+/* y[T,n_o] = (x[T,n_i] @ A[r,n_i]^T) @ B[n_o,r]^T (+ bias[n_o]), dtype f32, bf16 or f16.  The workspace holds the
  * [T, r] intermediate of the operand dtype and, for f32 operands with a small rank, the partial
  * tiles of the first product's K split (added in a fixed order: results do not depend on
  * scheduling).  The decomposed layer's forward: dwain.py:74-85 / falor.py:84-95 (two nn.Linear),
@@ -315,7 +317,7 @@ int ptd_lowrank_forward_nchw(const void* x, int64_t batch, int64_t n_i, int64_t 
 
 /* ---- rank-selection metrics ------------------------------------------------ */
 
-/* out[0] (f64) = mean_c( mean_r (x-y)^2 / (var_r(y) + eps) ), x,y viewed as [R, C],
+/* out[0] (f64) = mean_c( mean_r (x-y)^2 / (var_r(y) + eps) ), x,y (f32, f64, bf16 or f16) viewed as [R, C],
  * var unbiased.  Replaces calc_per_channel_noise_to_signal_ratio (losses.py:10-22)
  * for non_channel_dim = all leading dims. */
 /* (ABI 2) The workspace carries the arrival counters of the one-launch reduction: initialise it ONCE with
@@ -327,13 +329,13 @@ int ptd_nsr(const void* x, const void* y, int64_t R, int64_t C, int dtype, doubl
             void* ws, size_t ws_bytes, void* stream);
 
 /* out[0] (f64) = mean_b max(KL(t_b || s_b), KL(s_b || t_b)) over softmax(dim=-1) of
- * logits s, t [B, C].  Replaces calc_kl_loss (losses.py:48-63). */
+ * logits s, t [B, C] (f32, bf16 or f16).  Replaces calc_kl_loss (losses.py:48-63). */
 size_t ptd_sym_kl_workspace_bytes(int64_t B);
 int ptd_sym_kl(const void* s, const void* t, int64_t B, int64_t C, int dtype, double* out, void* ws,
                size_t ws_bytes, void* stream);
 
 /* rows[b] (f64) = KL(p_b || q_b) = sum_c p log(p / q) over softmax(dim=-1) of logits q, p [B, C].
- * Replaces calc_kl_divergence(q_logits, p_logits) (losses.py:48-54). */
+ * f32, bf16 or f16.  Replaces calc_kl_divergence(q_logits, p_logits) (losses.py:48-54). */
 int ptd_kl_rows(const void* q, const void* p, int64_t B, int64_t C, int dtype, double* rows, void* stream);
 
 #ifdef __cplusplus

@@ -807,11 +807,11 @@ class LayerTap:
     # falor.py:223-227).  The same two functions are evaluated here without touching the
     # weight: the candidate through its rank-r pair (x U) uk^T + b -- exactly what will be
     # deployed, 2 T r (n_in + n_out) instead of 2 T n_in n_out flops and no W~ product -- and
-    # the original through the f32/bf16 MFMA GEMM.  Only plain Linear / stride-1 1x1 conv
-    # layers in f32 or bf16 qualify; anything else keeps the module's own forward.
+    # the original through the f32/bf16/f16 MFMA GEMM.  Only plain Linear / stride-1 1x1 conv
+    # layers in f32, bf16 or f16 qualify; anything else keeps the module's own forward.
     def _plain(self) -> bool:
         l = self.layer
-        if l.weight.dtype not in (torch.float32, torch.bfloat16) or not l.weight.is_cuda:
+        if l.weight.dtype not in (torch.float32, torch.bfloat16, torch.float16) or not l.weight.is_cuda:
             return False
         if self.is_conv:
             return (tuple(l.stride) == (1, 1) and tuple(l.dilation) == (1, 1) and l.padding_mode == "zeros"
@@ -882,7 +882,7 @@ def _input_route_wanted(n_out: int, n_in: int, top_k: Optional[int]) -> bool:
 
 
 class StepBatch:
-    """The bf16 activation matrices of up to PTD_SYRK_STEPS (default 8) calibration steps, held back so that their
+    """The 16-bit (bf16 / f16) activation matrices of up to PTD_SYRK_STEPS (default 8) calibration steps, held back so that their
     covariance sums reach the f64 accumulator in ONE pass (ops.syrk_accumulate_multi): dwain.py:147-152 runs once per
     step and every call reads and writes the live triangle of E -- 134 MB at n = 4096 against 17 MB of activations at
     2048 tokens -- which, not the matrix cores, bounds it.  A matrix the caller may still write to
@@ -918,9 +918,9 @@ class StepBatch:
 
     @staticmethod
     def holdable(y: torch.Tensor) -> bool:
-        """bf16 matrices on the device: their covariance product is bound by the accumulator's traffic (f32 ones by
-        the matrix cores: nothing to gain from holding them)."""
-        return y.dtype == torch.bfloat16 and y.is_cuda and y.dim() == 2
+        """bf16 / f16 matrices on the device: their covariance product is bound by the accumulator's traffic (f32
+        ones by the matrix cores: nothing to gain from holding them)."""
+        return y.dtype in (torch.bfloat16, torch.float16) and y.is_cuda and y.dim() == 2
 
     def add(self, y: torch.Tensor, private: bool = False) -> None:
         nbytes = y.numel() * y.element_size()
@@ -1350,7 +1350,8 @@ class SharedInputPool:
             raise ValueError(f"PTD_SHARE_INPUT_COVARIANCE={self.mode!r}: expected off, all or auto")
         self.num_data_steps, self.float64, self.device = num_data_steps, float64, device
         forced = os.environ.get("PTD_SHARE_RATE_SYRK_TFLOPS")
-        self.rate_syrk = {torch.bfloat16: float(forced) * 1e12 if forced else self.RATE_BF16}
+        rate16 = float(forced) * 1e12 if forced else self.RATE_BF16   # (f16 runs the bf16 schedule: same MFMA rate)
+        self.rate_syrk = {torch.bfloat16: rate16, torch.float16: rate16}
         self.rate_syrk_default = float(forced) * 1e12 if forced else self.RATE_F32
         self.rate_f64 = float(os.environ.get("PTD_SHARE_RATE_F64_TFLOPS", self.RATE_F64 / 1e12)) * 1e12
         self.members: list = []

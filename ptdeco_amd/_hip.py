@@ -13,8 +13,8 @@ from ctypes import c_char_p, c_double, c_int, c_int64, c_size_t, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libptdeco_hip.so")
 
-F32, F64, BF16 = 0, 1, 2
-ABI_VERSION = 5
+F32, F64, BF16, F16 = 0, 1, 2, 3
+ABI_VERSION = 6
 
 # name -> (restype, argtypes); must list every symbol include/ptdeco_hip.h declares
 SIGNATURES = {

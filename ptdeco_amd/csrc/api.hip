@@ -83,7 +83,9 @@ int ptd_syrk_accumulate(const void* y, int64_t T, int64_t n, int64_t ldy, int y_
     return syrk_f32(static_cast<const float*>(y), T, n, ldy, E, ldE, E_dtype == PTD_F64, scale, st);
   if (y_dtype == PTD_BF16)
     return syrk_bf16(static_cast<const unsigned short*>(y), T, n, ldy, E, ldE, E_dtype == PTD_F64, scale, st);
-  set_error("ptd_syrk_accumulate: y dtype must be f32 or bf16");
+  if (y_dtype == PTD_F16)
+    return syrk_f16(static_cast<const unsigned short*>(y), T, n, ldy, E, ldE, E_dtype == PTD_F64, scale, st);
+  set_error("ptd_syrk_accumulate: y dtype must be f32, bf16 or f16");
   return PTD_ERR_UNSUPPORTED;
 }
 
@@ -99,6 +101,9 @@ int ptd_syrk_accumulate_multi(const void* const* ys, int steps, int64_t T, int64
   if (y_dtype == PTD_BF16)
     return syrk_bf16_multi(reinterpret_cast<const unsigned short* const*>(ys), steps, T, n, ldy, E, ldE,
                            E_dtype == PTD_F64, scale, st);
+  if (y_dtype == PTD_F16)
+    return syrk_f16_multi(reinterpret_cast<const unsigned short* const*>(ys), steps, T, n, ldy, E, ldE,
+                          E_dtype == PTD_F64, scale, st);
   if (y_dtype == PTD_F32) {
     // the f32 product is bound by the matrix cores, not by the accumulator's read-modify-write: step by step
     for (int s = 0; s < steps; ++s) {
@@ -107,7 +112,7 @@ int ptd_syrk_accumulate_multi(const void* const* ys, int steps, int64_t T, int64
     }
     return PTD_OK;
   }
-  set_error("ptd_syrk_accumulate_multi: y dtype must be f32 or bf16");
+  set_error("ptd_syrk_accumulate_multi: y dtype must be f32, bf16 or f16");
   return PTD_ERR_UNSUPPORTED;
 }
 
@@ -329,7 +334,8 @@ int ptd_tridiagonalize(const double* A, int64_t lda, int64_t n, double* d, doubl
 
 size_t ptd_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int ab_dtype, int c_dtype) {
   if (ab_dtype == PTD_F32 && c_dtype == PTD_F32) return gemm_f32_workspace_bytes(M, N, K);
-  if (ab_dtype == PTD_BF16 && (c_dtype == PTD_BF16 || c_dtype == PTD_F32)) return gemm_bf16_workspace_bytes(M, N, K);
+  if ((ab_dtype == PTD_BF16 || ab_dtype == PTD_F16) && (c_dtype == ab_dtype || c_dtype == PTD_F32))
+    return gemm_bf16_workspace_bytes(M, N, K);
   return 0;
 }
 
@@ -354,6 +360,10 @@ int ptd_gemm_ws(const void* A, int64_t sam, int64_t sak, const void* B, int64_t 
     return gemm_bf16(static_cast<const unsigned short*>(A), sam, sak, static_cast<const unsigned short*>(B), sbk,
                      sbn, C, ldc, M, N, K, c_dtype == PTD_BF16, alpha, static_cast<const unsigned short*>(bias),
                      ws, ws_bytes, st);
+  if (ab_dtype == PTD_F16 && (c_dtype == PTD_F16 || c_dtype == PTD_F32))
+    return gemm_f16(static_cast<const unsigned short*>(A), sam, sak, static_cast<const unsigned short*>(B), sbk,
+                    sbn, C, ldc, M, N, K, c_dtype == PTD_F16, alpha, static_cast<const unsigned short*>(bias),
+                    ws, ws_bytes, st);
   if (ab_dtype == PTD_F64 && c_dtype == PTD_F64 && !bias)
     return gemm_f64(static_cast<const double*>(A), sam, sak, static_cast<const double*>(B), sbk, sbn,
                     static_cast<double*>(C), ldc, M, N, K, alpha, false, 1, st);
@@ -363,7 +373,10 @@ int ptd_gemm_ws(const void* A, int64_t sam, int64_t sak, const void* B, int64_t 
 
 static size_t elt_bytes(int dtype) { return dtype == PTD_F32 ? 4 : 2; }
 
-// bf16 ranks that are not a multiple of 128 (a dwain search ends at 32 .. 96 on wide layers: Llama gate / up): the first
+// the 16-bit products of an operand dtype (bf16 or f16: the same kernels, see gemm_bf16.hip)
+static decltype(&gemm_bf16) gemm16_of(int dtype) { return dtype == PTD_F16 ? gemm_f16 : gemm_bf16; }
+
+// 16-bit ranks that are not a multiple of 128 (a dwain search ends at 32 .. 96 on wide layers: Llama gate / up): the first
 // product's output would have fewer than 128 columns -- a handful of 128-row tiles for the whole chip (x A^T at
 // T = 2048, r = 32: 98 us on 16 workgroups, the library 20) -- and K = r of the second product no whole 64-deep step.
 // The pair then runs on the rank padded with zeros: A's rows to a multiple of 128 (a copy in the workspace: the first
@@ -372,7 +385,7 @@ static size_t elt_bytes(int dtype) { return dtype == PTD_F32 ? 4 : 2; }
 // row's start, h is zero there).  The results are those of the unpadded products: the padding adds exact zeros.
 static int64_t lowrank_pad128(int64_t r, int dtype) {
   static const bool off = getenv("PTD_LOWRANK_PAD") && atoi(getenv("PTD_LOWRANK_PAD")) == 0;
-  if (off || dtype != PTD_BF16 || r % 8 != 0 || r % 128 == 0 || r > 1024) return r;
+  if (off || (dtype != PTD_BF16 && dtype != PTD_F16) || r % 8 != 0 || r % 128 == 0 || r > 1024) return r;
   return r <= 64 ? 64 : (int64_t)align_up((size_t)r, 128);     // (one column of 128 x 64 tiles serves a rank up to 64)
 }
 
@@ -390,12 +403,13 @@ int ptd_lowrank_forward(const void* x, int64_t ldx, int64_t T, int64_t n_i, cons
                         size_t ws_bytes, int dtype, void* stream) {
   PTD_REQUIRE(x && A && B && y && ws, "ptd_lowrank_forward: null pointer");
   PTD_REQUIRE(ldx >= n_i && lda >= n_i && ldb >= r && ldy >= n_o, "ptd_lowrank_forward: bad leading dimension");
-  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16, "ptd_lowrank_forward: dtype must be f32 or bf16");
+  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16 || dtype == PTD_F16, "ptd_lowrank_forward: dtype must be f32, bf16 or f16");
   const int64_t rp = lowrank_pad128(r, dtype);
   if (rp != r && n_i % 8 == 0 && lda % 8 == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
       ws_bytes >= ptd_lowrank_forward_workspace_bytes(T, n_i, r, dtype)) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     typedef unsigned short u16;
+    const auto gemm16 = gemm16_of(dtype);
     const size_t hp_bytes = align_up((size_t)T * (size_t)rp * 2, 256), ap_bytes = align_up((size_t)rp * (size_t)n_i * 2, 256);
     u16* hp = static_cast<u16*>(ws);
     u16* Ap = reinterpret_cast<u16*>(static_cast<char*>(ws) + hp_bytes);
@@ -403,20 +417,20 @@ int ptd_lowrank_forward(const void* x, int64_t ldx, int64_t T, int64_t n_i, cons
     // the first product on the padded rank: A read in place -- its rows behind r are fetched from row 0 and the columns
     // they would produce are written as zeros (GemmBf16Args::nvalid); where no LDS-DMA kernel serves the shape, on a
     // zero-padded copy of A
-    int rc = gemm_bf16(static_cast<const u16*>(x), ldx, 1, static_cast<const u16*>(A), 1, lda, hp, rp, T, rp, n_i, true, 1.0,
+    int rc = gemm16(static_cast<const u16*>(x), ldx, 1, static_cast<const u16*>(A), 1, lda, hp, rp, T, rp, n_i, true, 1.0,
                        nullptr, rest, ws_bytes - hp_bytes - ap_bytes, st, 0, r);
     if (rc == PTD_ERR_UNSUPPORTED) {
       rc = pad_rows_bf16(static_cast<const u16*>(A), lda, r, n_i, Ap, rp, st);
       if (rc != PTD_OK) return rc;
-      rc = gemm_bf16(static_cast<const u16*>(x), ldx, 1, Ap, 1, n_i, hp, rp, T, rp, n_i, true, 1.0, nullptr, rest,
-                     ws_bytes - hp_bytes - ap_bytes, st);
+      rc = gemm16(static_cast<const u16*>(x), ldx, 1, Ap, 1, n_i, hp, rp, T, rp, n_i, true, 1.0, nullptr, rest,
+                  ws_bytes - hp_bytes - ap_bytes, st, 0, 0);
     }
     if (rc != PTD_OK) return rc;
     // y = h B^T + bias with K padded to whole 64-deep steps where a short-K kernel serves the shape, else with K = r
     const int64_t k64 = (int64_t)align_up((size_t)r, 64);
     if (k64 != r && k64 <= 256) {
-      rc = gemm_bf16(hp, rp, 1, static_cast<const u16*>(B), 1, ldb, y, ldy, T, n_o, k64, true, 1.0,
-                     static_cast<const u16*>(bias), nullptr, 0, st, r);
+      rc = gemm16(hp, rp, 1, static_cast<const u16*>(B), 1, ldb, y, ldy, T, n_o, k64, true, 1.0,
+                  static_cast<const u16*>(bias), nullptr, 0, st, r, 0);
       if (rc != PTD_ERR_UNSUPPORTED) return rc;
     }
     return ptd_gemm(hp, rp, 1, B, 1, ldb, y, ldy, T, n_o, r, dtype, dtype, 1.0, bias, stream);
@@ -436,9 +450,9 @@ int ptd_lowrank_forward(const void* x, int64_t ldx, int64_t T, int64_t n_i, cons
                   T, r, n_i, 1.0, nullptr, static_cast<char*>(ws) + h_bytes, ws_bytes - h_bytes,
                   static_cast<hipStream_t>(stream));
   } else {
-    rc = gemm_bf16(static_cast<const unsigned short*>(x), ldx, 1, static_cast<const unsigned short*>(A), 1, lda, h, r,
-                   T, r, n_i, true, 1.0, nullptr, static_cast<char*>(ws) + h_bytes, ws_bytes - h_bytes,
-                   static_cast<hipStream_t>(stream));
+    rc = gemm16_of(dtype)(static_cast<const unsigned short*>(x), ldx, 1, static_cast<const unsigned short*>(A), 1, lda,
+                          h, r, T, r, n_i, true, 1.0, nullptr, static_cast<char*>(ws) + h_bytes, ws_bytes - h_bytes,
+                          static_cast<hipStream_t>(stream), 0, 0);
   }
   if (rc != PTD_OK) return rc;
   return ptd_gemm(h, r, 1, B, 1, ldb, y, ldy, T, n_o, r, dtype, dtype, 1.0, bias, stream);
@@ -454,7 +468,8 @@ int ptd_lowrank_forward_nchw(const void* x, int64_t batch, int64_t n_i, int64_t 
   PTD_REQUIRE(x && A && B && y && ws, "ptd_lowrank_forward_nchw: null pointer");
   PTD_REQUIRE(batch >= 0 && n_i >= 1 && hw >= 1 && r >= 1 && n_o >= 1 && lda >= n_i && ldb >= r,
               "ptd_lowrank_forward_nchw: bad shape");
-  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16, "ptd_lowrank_forward_nchw: dtype must be f32 or bf16");
+  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16 || dtype == PTD_F16,
+              "ptd_lowrank_forward_nchw: dtype must be f32, bf16 or f16");
   if (ws_bytes < ptd_lowrank_forward_nchw_workspace_bytes(batch, hw, r, dtype)) {
     set_error("ptd_lowrank_forward_nchw: workspace too small");
     return PTD_ERR_WORKSPACE;
@@ -470,12 +485,13 @@ int ptd_lowrank_forward_nchw(const void* x, int64_t batch, int64_t n_i, int64_t 
                             static_cast<const float*>(bias), st);
   }
   typedef unsigned short u16;
-  int rc = gemm_bf16_batched(static_cast<const u16*>(A), lda, 1, 0, static_cast<const u16*>(x), hw, 1, n_i * hw,
+  const auto gemm16_batched = dtype == PTD_F16 ? gemm_f16_batched : gemm_bf16_batched;
+  int rc = gemm16_batched(static_cast<const u16*>(A), lda, 1, 0, static_cast<const u16*>(x), hw, 1, n_i * hw,
                              static_cast<u16*>(ws), hw, r * hw, r, hw, n_i, batch, 1.0, nullptr, st);
   if (rc != PTD_OK) return rc;
-  return gemm_bf16_batched(static_cast<const u16*>(B), ldb, 1, 0, static_cast<const u16*>(ws), hw, 1, r * hw,
-                           static_cast<u16*>(y), hw, n_o * hw, n_o, hw, r, batch, 1.0, static_cast<const u16*>(bias),
-                           st);
+  return gemm16_batched(static_cast<const u16*>(B), ldb, 1, 0, static_cast<const u16*>(ws), hw, 1, r * hw,
+                        static_cast<u16*>(y), hw, n_o * hw, n_o, hw, r, batch, 1.0, static_cast<const u16*>(bias),
+                        st);
 }
 
 size_t ptd_nsr_workspace_bytes(int64_t R, int64_t C) { return nsr_workspace_bytes(R, C); }

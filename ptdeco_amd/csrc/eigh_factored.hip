@@ -34,6 +34,8 @@ template <>
 __device__ __forceinline__ double to_f64<double>(double v) { return v; }
 template <>
 __device__ __forceinline__ double to_f64<unsigned short>(unsigned short v) { return (double)bf16_to_f32(v); }
+template <>
+__device__ __forceinline__ double to_f64<_Float16>(_Float16 v) { return (double)v; }
 
 // D[r][c] = (r < rows && c < cols) ? S[r][c] : (r == c ? diag_pad : 0)
 template <typename T>
@@ -243,6 +245,9 @@ int eigh_factored_prepare(const void* W, int64_t ldw, int w_dtype, int64_t n_o, 
   else if (w_dtype == PTD_BF16)
     hipLaunchKernelGGL((widen_pad_kernel<unsigned short>), dim3(4096), dim3(256), 0, st, (const unsigned short*)W,
                        ldw, (int)n_o, (int)n_i, W64, (int64_t)np, (int)n_o, np, 0.0);
+  else if (w_dtype == PTD_F16)
+    hipLaunchKernelGGL((widen_pad_kernel<_Float16>), dim3(4096), dim3(256), 0, st, (const _Float16*)W, ldw, (int)n_o,
+                       (int)n_i, W64, (int64_t)np, (int)n_o, np, 0.0);
   else if (w_dtype == PTD_F64)
     hipLaunchKernelGGL((widen_pad_kernel<double>), dim3(4096), dim3(256), 0, st, (const double*)W, ldw, (int)n_o,
                        (int)n_i, W64, (int64_t)np, (int)n_o, np, 0.0);

@@ -16,12 +16,17 @@ int gemm_f32_batched(const float* A, int64_t sam, int64_t sak, int64_t zsa, cons
 int syrk_f32(const float* Y, int64_t T, int64_t n, int64_t ldy, void* E, int64_t ldE, bool e_f64, double scale,
              hipStream_t st);
 
-// gemm_bf16.hip
+// gemm_bf16.hip: the 16-bit products.  Every entry has an f16 twin of the same signature (IEEE half operands, raw
+// 16-bit words like the bf16 ones; `c_bf16` / `c_f16` = the output has the operands' type): same kernels, same dispatch
 int gemm_bf16(const unsigned short* A, int64_t sam, int64_t sak, const unsigned short* B, int64_t sbk, int64_t sbn,
               void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, bool c_bf16, double alpha,
               const unsigned short* bias, void* ws, size_t ws_bytes, hipStream_t st, int64_t b_kvalid = 0,
               int64_t b_nvalid = 0);
-size_t gemm_bf16_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int gemm_f16(const unsigned short* A, int64_t sam, int64_t sak, const unsigned short* B, int64_t sbk, int64_t sbn,
+             void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, bool c_f16, double alpha,
+             const unsigned short* bias, void* ws, size_t ws_bytes, hipStream_t st, int64_t b_kvalid = 0,
+             int64_t b_nvalid = 0);
+size_t gemm_bf16_workspace_bytes(int64_t M, int64_t N, int64_t K);   // (either element type)
 // [rows_out][cols] <- the first `rows` rows of src (row pitch ld), zero rows behind them
 int pad_rows_bf16(const unsigned short* src, int64_t ld, int64_t rows, int64_t cols, unsigned short* dst, int64_t rows_out,
                   hipStream_t st);
@@ -29,10 +34,18 @@ int gemm_bf16_batched(const unsigned short* A, int64_t sam, int64_t sak, int64_t
                       int64_t sbk, int64_t sbn, int64_t zsb, unsigned short* C, int64_t ldc, int64_t zsc, int64_t M,
                       int64_t N, int64_t K, int64_t batch, double alpha, const unsigned short* bias_rows,
                       hipStream_t st);
+int gemm_f16_batched(const unsigned short* A, int64_t sam, int64_t sak, int64_t zsa, const unsigned short* B,
+                     int64_t sbk, int64_t sbn, int64_t zsb, unsigned short* C, int64_t ldc, int64_t zsc, int64_t M,
+                     int64_t N, int64_t K, int64_t batch, double alpha, const unsigned short* bias_rows,
+                     hipStream_t st);
 int syrk_bf16(const unsigned short* Y, int64_t T, int64_t n, int64_t ldy, void* E, int64_t ldE, bool e_f64,
               double scale, hipStream_t st);
 int syrk_bf16_multi(const unsigned short* const* Ys, int steps, int64_t T, int64_t n, int64_t ldy, void* E, int64_t ldE,
                     bool e_f64, double scale, hipStream_t st);
+int syrk_f16(const unsigned short* Y, int64_t T, int64_t n, int64_t ldy, void* E, int64_t ldE, bool e_f64,
+             double scale, hipStream_t st);
+int syrk_f16_multi(const unsigned short* const* Ys, int steps, int64_t T, int64_t n, int64_t ldy, void* E, int64_t ldE,
+                   bool e_f64, double scale, hipStream_t st);
 
 // eigh_jacobi.hip
 size_t eigh_workspace_bytes(int64_t n);

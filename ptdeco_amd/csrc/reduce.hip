@@ -3,7 +3,8 @@
 //   colsum         ey += scale * column sums of Y                         (falor Ey)
 //   nsr            per-channel noise-to-signal ratio, one pass over x and y
 //   sym_kl         symmetric-max KL of two logit matrices, one wave per row
-// All accumulate in f64; inputs are f32 or bf16 and are read once, coalesced.
+// All accumulate in f64; inputs are f32, bf16 or f16 and are read once, coalesced.  bf16 travels as unsigned short
+// (raw bits), f16 as _Float16.
 #include <algorithm>
 #include <cstdlib>
 
@@ -23,6 +24,8 @@ template <>
 __device__ __forceinline__ double ld<unsigned short>(const unsigned short* p, int64_t i) {
   return (double)bf16_to_f32(p[i]);
 }
+template <>
+__device__ __forceinline__ double ld<_Float16>(const _Float16* p, int64_t i) { return (double)p[i]; }
 
 __device__ __forceinline__ double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -160,6 +163,13 @@ __device__ __forceinline__ void nsr_unpack<unsigned short, 8>(const uint4& q, do
   v[2] = (double)__uint_as_float(q.y << 16); v[3] = (double)__uint_as_float(q.y & 0xFFFF0000u);
   v[4] = (double)__uint_as_float(q.z << 16); v[5] = (double)__uint_as_float(q.z & 0xFFFF0000u);
   v[6] = (double)__uint_as_float(q.w << 16); v[7] = (double)__uint_as_float(q.w & 0xFFFF0000u);
+}
+template <>
+__device__ __forceinline__ void nsr_unpack<_Float16, 8>(const uint4& q, double (&v)[8]) {
+  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+  const h8 h = __builtin_bit_cast(h8, q);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = (double)h[i];
 }
 
 template <typename T, int V>
@@ -443,6 +453,8 @@ int colsum_accumulate(const void* y, int64_t T, int64_t n, int64_t ldy, int y_dt
     return colsum_t((const unsigned short*)y, T, n, ldy, (double*)ey, scale, st);
   if (y_dtype == PTD_BF16 && ey_dtype == PTD_F32)
     return colsum_t((const unsigned short*)y, T, n, ldy, (float*)ey, scale, st);
+  if (y_dtype == PTD_F16 && ey_dtype == PTD_F64) return colsum_t((const _Float16*)y, T, n, ldy, (double*)ey, scale, st);
+  if (y_dtype == PTD_F16 && ey_dtype == PTD_F32) return colsum_t((const _Float16*)y, T, n, ldy, (float*)ey, scale, st);
   set_error("ptd_colsum_accumulate: unsupported dtype combination");
   return PTD_ERR_UNSUPPORTED;
 }
@@ -471,7 +483,7 @@ int nsr(const void* x, const void* y, int64_t R, int64_t C, int dtype, double ep
     return PTD_ERR_WORKSPACE;
   }
   NsrPlan p = nsr_plan(R, C);
-  const int vec = dtype == PTD_F32 ? 4 : (dtype == PTD_BF16 ? 8 : 0);
+  const int vec = dtype == PTD_F32 ? 4 : ((dtype == PTD_BF16 || dtype == PTD_F16) ? 8 : 0);
   const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
   const bool use_vec = vec && C % vec == 0 && C >= 64 && aligned;
   if (use_vec) p = nsr_plan_vec(R, C, vec);
@@ -484,15 +496,21 @@ int nsr(const void* x, const void* y, int64_t R, int64_t C, int dtype, double ep
     if (dtype == PTD_F32)
       hipLaunchKernelGGL((nsr_partial_vec_kernel<float, 4>), grid, dim3(256), 0, st, (const float*)x, (const float*)y, R,
                          C, p.rows_per_chunk, part, out);
-    else
+    else if (dtype == PTD_BF16)
       hipLaunchKernelGGL((nsr_partial_vec_kernel<unsigned short, 8>), grid, dim3(256), 0, st, (const unsigned short*)x,
                          (const unsigned short*)y, R, C, p.rows_per_chunk, part, out);
+    else
+      hipLaunchKernelGGL((nsr_partial_vec_kernel<_Float16, 8>), grid, dim3(256), 0, st, (const _Float16*)x,
+                         (const _Float16*)y, R, C, p.rows_per_chunk, part, out);
   } else if (dtype == PTD_F32) {
     hipLaunchKernelGGL((nsr_partial_kernel<float>), grid, dim3(256), 0, st, (const float*)x, (const float*)y, R, C,
                        p.Ct, p.Rt, p.rows_per_chunk, part, out);
   } else if (dtype == PTD_BF16) {
     hipLaunchKernelGGL((nsr_partial_kernel<unsigned short>), grid, dim3(256), 0, st, (const unsigned short*)x,
                        (const unsigned short*)y, R, C, p.Ct, p.Rt, p.rows_per_chunk, part, out);
+  } else if (dtype == PTD_F16) {
+    hipLaunchKernelGGL((nsr_partial_kernel<_Float16>), grid, dim3(256), 0, st, (const _Float16*)x, (const _Float16*)y, R,
+                       C, p.Ct, p.Rt, p.rows_per_chunk, part, out);
   } else if (dtype == PTD_F64) {
     hipLaunchKernelGGL((nsr_partial_kernel<double>), grid, dim3(256), 0, st, (const double*)x, (const double*)y, R,
                        C, p.Ct, p.Rt, p.rows_per_chunk, part, out);
@@ -554,6 +572,9 @@ int sym_kl(const void* s, const void* t, int64_t B, int64_t C, int dtype, double
   else if (dtype == PTD_BF16)
     hipLaunchKernelGGL((sym_kl_rows_kernel<unsigned short, true>), dim3(grid), dim3(256), 0, st,
                        (const unsigned short*)s, (const unsigned short*)t, B, C, rows);
+  else if (dtype == PTD_F16)
+    hipLaunchKernelGGL((sym_kl_rows_kernel<_Float16, true>), dim3(grid), dim3(256), 0, st, (const _Float16*)s,
+                       (const _Float16*)t, B, C, rows);
   else {
     set_error("ptd_sym_kl: unsupported dtype");
     return PTD_ERR_UNSUPPORTED;
@@ -572,6 +593,9 @@ int kl_rows(const void* q, const void* p, int64_t B, int64_t C, int dtype, doubl
   else if (dtype == PTD_BF16)
     hipLaunchKernelGGL((sym_kl_rows_kernel<unsigned short, false>), dim3(grid), dim3(256), 0, st,
                        (const unsigned short*)q, (const unsigned short*)p, B, C, rows);
+  else if (dtype == PTD_F16)
+    hipLaunchKernelGGL((sym_kl_rows_kernel<_Float16, false>), dim3(grid), dim3(256), 0, st, (const _Float16*)q,
+                       (const _Float16*)p, B, C, rows);
   else {
     set_error("ptd_kl_rows: unsupported dtype");
     return PTD_ERR_UNSUPPORTED;

@@ -11,7 +11,7 @@ import torch
 
 from . import _hip
 
-_DT = {torch.float32: _hip.F32, torch.float64: _hip.F64, torch.bfloat16: _hip.BF16}
+_DT = {torch.float32: _hip.F32, torch.float64: _hip.F64, torch.bfloat16: _hip.BF16, torch.float16: _hip.F16}
 
 
 def _code(t: torch.Tensor) -> int:
