@@ -4,6 +4,7 @@ path behind ptdeco's own API (``dwain.decompose_in_place``, ``falor.decompose_in
 hand-written gfx950 kernels (libptdeco_hip.so, C ABI in include/ptdeco_hip.h); there is
 no CPU fallback."""
 
+from . import _torch_ops  # noqa: F401  (torch.ops.ptdeco_amd.*: the pair as custom operators)
 from . import dwain  # noqa: F401
 from . import falor  # noqa: F401
 from . import utils  # noqa: F401

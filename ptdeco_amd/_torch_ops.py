@@ -1,0 +1,93 @@
+"""The low-rank pair as PyTorch custom operators (namespace ``ptdeco_amd``): what torch.compile, torch.export,
+FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed layer.
+
+    lowrank_forward(Tensor x2d, Tensor A, Tensor B, Tensor? bias) -> Tensor              ops.lowrank_forward
+    lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
+    lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
+        -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
+
+Each body looks ``ops.<name>`` up when it runs, not when it is registered (tests swap the functions of ``ops``), and
+registering loads no library: ``_hip.load()`` runs at the first real call.  The schema has no optional returns, so a
+gradient that ``needs`` does not ask for (and dbias without a bias) comes back from ``lowrank_backward`` as an empty
+tensor (numel 0) of dy's dtype; the autograd formula of ``lowrank_forward`` hands it on as None.
+"""
+
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from . import ops
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward", mutates_args=())
+def lowrank_forward(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """(x2d @ A^T) @ B^T + bias with x2d [T, n_i], A [r, n_i], B [n_o, r]; y [T, n_o] contiguous."""
+    return ops.lowrank_forward(x2d, A, B, bias)
+
+
+@lowrank_forward.register_fake
+def _(x2d, A, B, bias):
+    torch._check(x2d.dim() == 2 and A.dim() == 2 and B.dim() == 2, lambda: "lowrank_forward: 2-D operands")
+    torch._check(A.shape[1] == x2d.shape[1] and B.shape[1] == A.shape[0], lambda: "lowrank_forward: shape mismatch")
+    torch._check(x2d.dtype == A.dtype == B.dtype, lambda: "lowrank_forward: x2d, A and B must share a dtype")
+    torch._check(bias is None or tuple(bias.shape) == (B.shape[0],), lambda: "lowrank_forward: bias must be [n_o]")
+    return x2d.new_empty((x2d.shape[0], B.shape[0]))
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_nchw", mutates_args=())
+def lowrank_forward_nchw(x: torch.Tensor, A: torch.Tensor, B: torch.Tensor,
+                         bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The 1x1-convolution pair on a contiguous NCHW x [b, n_i, h, w]: y [b, n_o, h, w] contiguous NCHW."""
+    return ops.lowrank_forward_nchw(x, A, B, bias)
+
+
+@lowrank_forward_nchw.register_fake
+def _(x, A, B, bias):
+    torch._check(x.dim() == 4 and A.dim() == 2 and B.dim() == 2, lambda: "lowrank_forward_nchw: x 4-D, A and B 2-D")
+    torch._check(A.shape[1] == x.shape[1] and B.shape[1] == A.shape[0], lambda: "lowrank_forward_nchw: shape mismatch")
+    torch._check(x.dtype == A.dtype == B.dtype, lambda: "lowrank_forward_nchw: x, A and B must share a dtype")
+    torch._check(x.is_contiguous(), lambda: "lowrank_forward_nchw: x must be contiguous NCHW")
+    torch._check(bias is None or tuple(bias.shape) == (B.shape[0],), lambda: "lowrank_forward_nchw: bias must be [n_o]")
+    return x.new_empty((x.shape[0], B.shape[0], x.shape[2], x.shape[3]))
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_backward", mutates_args=())
+def lowrank_backward(dy: torch.Tensor, x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, has_bias: bool,
+                     needs: list[bool]) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """dh = dy B,  dx = dh A,  dA = dh^T x2d,  dB = dy^T h,  dbias = sum_t dy, every product on ptd_gemm; h = x2d A^T
+    is recomputed (one [T, r] product instead of keeping it alive between forward and backward).  needs = which of
+    (dx, dA, dB, dbias) to form."""
+    dy = dy.contiguous()
+    need_x, need_a, need_b, need_bias = needs
+    dh = ops.matmul(dy, B) if (need_x or need_a) else None
+    dx = ops.matmul(dh, A) if need_x else dy.new_empty(0)
+    da = ops.matmul(dh.T, x2d) if need_a else dy.new_empty(0)
+    db = ops.matmul(dy.T, ops.matmul(x2d, A.T)) if need_b else dy.new_empty(0)
+    dbias = dy.sum(dim=0) if need_bias and has_bias else dy.new_empty(0)
+    return dx, da, db, dbias
+
+
+@lowrank_backward.register_fake
+def _(dy, x2d, A, B, has_bias, needs):
+    need_x, need_a, need_b, need_bias = needs
+    (T, n_i), r, n_o = x2d.shape, A.shape[0], B.shape[0]
+    return (dy.new_empty((T, n_i) if need_x else (0,)), dy.new_empty((r, n_i) if need_a else (0,)),
+            dy.new_empty((n_o, r) if need_b else (0,)), dy.new_empty((n_o,) if need_bias and has_bias else (0,)))
+
+
+def _setup_context(ctx, inputs, output):
+    x2d, A, B, bias = inputs
+    ctx.save_for_backward(x2d, A, B)
+    ctx.has_bias = bias is not None
+
+
+def _backward(ctx, dy):
+    x2d, A, B = ctx.saved_tensors
+    needs = list(ctx.needs_input_grad)
+    grads = torch.ops.ptdeco_amd.lowrank_backward(dy, x2d, A, B, ctx.has_bias, needs)
+    return tuple(g if need else None for g, need in zip(grads, needs))
+
+
+lowrank_forward.register_autograd(_backward, setup_context=_setup_context)

@@ -5,9 +5,11 @@ Both classes ARE ``torch.nn.Sequential`` containers of two ``nn.Linear`` / 1x1
 ``nn.Conv2d`` children, exactly what the reference builds (dwain.py:69-85, 121-144;
 falor.py:79-95, 131-153), so ``get_module_config``, ``state_dict`` keys
 ('0.weight' [r, n_in], '1.weight' [n_out, r], '1.bias') and ``load_state_dict`` are
-unchanged.  Only ``forward`` differs: on a ROCm device it calls the HIP kernels, also when
-autograd is recording (a user ``finetune_fn``, dwain.py:779-786): ``_LowRankFunction`` forms
-dx, dA, dB with the same strided GEMM entry (``ptd_gemm``), so fine-tuning trains the fused
+unchanged.  Only ``forward`` differs: on a ROCm device it calls the HIP kernels through the custom
+operators ``torch.ops.ptdeco_amd.lowrank_forward`` / ``lowrank_forward_nchw`` (``_torch_ops``), so the
+layer traces under torch.compile / torch.export and captures into CUDA graphs.  Also when autograd is
+recording (a user ``finetune_fn``, dwain.py:779-786): the autograd formula of ``lowrank_forward``
+forms dx, dA, dB with the same strided GEMM entry (``ptd_gemm``), so fine-tuning trains the fused
 pair.
 """
 
@@ -17,7 +19,10 @@ import logging
 
 import torch
 
-from . import ops
+from . import _torch_ops  # noqa: F401  (registers torch.ops.ptdeco_amd.*)
+
+_lowrank_forward = torch.ops.ptdeco_amd.lowrank_forward.default
+_lowrank_forward_nchw = torch.ops.ptdeco_amd.lowrank_forward_nchw.default
 
 logger = logging.getLogger(__name__)
 
@@ -44,50 +49,13 @@ def _use_hip(x: torch.Tensor, w: torch.Tensor, who: str) -> bool:
     return False
 
 
-class _LowRankFunction(torch.autograd.Function):
-    """y = (x A^T) B^T + bias with x [T, n_i], A [r, n_i], B [n_o, r]; every product on ptd_gemm.
-
-    backward:  dh = dy B,  dx = dh A,  dB = dy^T h,  dA = dh^T x,  dbias = sum_t dy   (h = x A^T is
-    recomputed: one [T, r] product instead of keeping it alive between forward and backward)."""
-
-    @staticmethod
-    def forward(ctx, x2d, a, b, bias):
-        ctx.save_for_backward(x2d, a, b)
-        ctx.has_bias = bias is not None
-        return ops.lowrank_forward(x2d, a, b, bias)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2d, a, b = ctx.saved_tensors
-        dy = dy.contiguous()
-        need_x, need_a, need_b, need_bias = ctx.needs_input_grad
-        dx = da = db = dbias = None
-        dh = ops.matmul(dy, b) if (need_x or need_a) else None
-        if need_x:
-            dx = ops.matmul(dh, a)
-        if need_a:
-            da = ops.matmul(dh.T, x2d)
-        if need_b:
-            db = ops.matmul(dy.T, ops.matmul(x2d, a.T))
-        if need_bias and ctx.has_bias:
-            dbias = dy.sum(dim=0)
-        return dx, da, db, dbias
-
-
-def _pair_forward(x2d: torch.Tensor, a: torch.Tensor, b: torch.Tensor, bias) -> torch.Tensor:
-    if torch.is_grad_enabled() and (x2d.requires_grad or a.requires_grad or b.requires_grad
-                                    or (bias is not None and bias.requires_grad)):
-        return _LowRankFunction.apply(x2d, a, b, bias)
-    return ops.lowrank_forward(x2d, a, b, bias)
-
-
 class LowRankLinear(torch.nn.Sequential):
     def forward(self, x: torch.Tensor) -> torch.Tensor:  # type: ignore[override]
         first, second = self[0], self[1]
         if not _use_hip(x, first.weight, "LowRankLinear"):
             return second(first(x))
         x2d = x.reshape(-1, first.in_features)
-        y = _pair_forward(x2d, first.weight, second.weight, second.bias)
+        y = _lowrank_forward(x2d, first.weight, second.weight, second.bias)
         return y.reshape(*x.shape[:-1], second.out_features)
 
 
@@ -103,9 +71,9 @@ class LowRankConv1x1(torch.nn.Sequential):
         if x.is_contiguous() and not needs_grad and h * w > 1:
             # NCHW as it lies: per image x_b is a [C, H W] matrix with the pixels contiguous, y_b = B (A x_b) + bias
             # goes straight into NCHW -- no NHWC copy (the reference's permute, dwain.py:116)
-            return ops.lowrank_forward_nchw(x, wa, wb, bias)
+            return _lowrank_forward_nchw(x, wa, wb, bias)
         rows = x.permute(0, 2, 3, 1).reshape(-1, c)  # NHWC rows: a view for channels_last inputs
-        y = _pair_forward(rows, wa, wb, bias)
+        y = _lowrank_forward(rows, wa, wb, bias)
         return y.reshape(b, h, w, second.out_channels).permute(0, 3, 1, 2)
 
 
