@@ -36,7 +36,8 @@ extern "C" {
                              * 4: ptd_eigh_topk_batched, ptd_eigh_factored_prepare / _finish; ptd_band_reduce and the
                              *    two-stage reduction behind it are gone (2.2 x behind the default for three rounds)
                              * 5: the two-stream form of ptd_streams_wall_us is gone (the same call with count = 2)
-                             * 6: PTD_F16 (IEEE half) wherever PTD_BF16 is accepted, same shapes, workspaces and codes */
+                             * 6: PTD_F16 (IEEE half) wherever PTD_BF16 is accepted, same shapes, workspaces and codes
+                             *    (added since, no entry changed: ptd_lowrank_decode_workspace_bytes, ptd_lowrank_decode) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -304,6 +305,19 @@ size_t ptd_lowrank_forward_workspace_bytes(int64_t T, int64_t n_i, int64_t r, in
 int ptd_lowrank_forward(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda,
                         int64_t r, const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y,
                         int64_t ldy, void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* The same pair for 1 <= T <= 16 tokens (token-by-token generation): two weight-streaming kernels on the caller's
+ * stream that read every factor element once (arguments as ptd_lowrank_forward; same rounding points: f32 sums, h
+ * rounded once to the operand dtype, y once).  Row t of y depends on row t of x alone, bit for bit, whatever T is.
+ * Served: dtype f32 / bf16 / f16, 1 <= T <= 16, r >= 8, n_i, r and the leading dimensions ldx, lda, ldb multiples of 8
+ * (f32: 4), x, A and B 16-byte aligned, any n_o >= 1, bias optional.  Anything else returns PTD_ERR_UNSUPPORTED
+ * before a kernel is launched (the caller then takes ptd_lowrank_forward); null pointers, a leading dimension below
+ * its row length or a misaligned workspace PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  The workspace holds
+ * the f32 partial sums of the first product's K split, added in a fixed order. */
+size_t ptd_lowrank_decode_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int ptd_lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r,
+                       const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy,
+                       void* ws, size_t ws_bytes, int dtype, void* stream);
 
 /* The same pair for a 1x1-convolution input in NCHW layout, without the NHWC copy the reference makes
  * (`permute(0,2,3,1).reshape(-1,C)`, dwain.py:116; falor.py:126): per image b, x_b = x + b*n_i*hw is an

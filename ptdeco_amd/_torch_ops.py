@@ -1,7 +1,8 @@
 """The low-rank pair as PyTorch custom operators (namespace ``ptdeco_amd``): what torch.compile, torch.export,
 FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed layer.
 
-    lowrank_forward(Tensor x2d, Tensor A, Tensor B, Tensor? bias) -> Tensor              ops.lowrank_forward
+    lowrank_forward(Tensor x2d, Tensor A, Tensor B, Tensor? bias) -> Tensor              ops.lowrank_forward, or
+                                                             ops.lowrank_decode where ops.lowrank_decode_serves (T <= 16)
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -23,7 +24,10 @@ from . import ops
 
 @torch.library.custom_op("ptdeco_amd::lowrank_forward", mutates_args=())
 def lowrank_forward(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """(x2d @ A^T) @ B^T + bias with x2d [T, n_i], A [r, n_i], B [n_o, r]; y [T, n_o] contiguous."""
+    """(x2d @ A^T) @ B^T + bias with x2d [T, n_i], A [r, n_i], B [n_o, r]; y [T, n_o] contiguous.  At decode shapes
+    (1 <= T <= 16, aligned operands: ops.lowrank_decode_serves) on the weight-streaming kernels of ptd_lowrank_decode."""
+    if ops.lowrank_decode_serves(x2d, A, B, bias):
+        return ops.lowrank_decode(x2d, A, B, bias)
     return ops.lowrank_forward(x2d, A, B, bias)
 
 

@@ -47,6 +47,13 @@ int syrk_f16(const unsigned short* Y, int64_t T, int64_t n, int64_t ldy, void* E
 int syrk_f16_multi(const unsigned short* const* Ys, int steps, int64_t T, int64_t n, int64_t ldy, void* E, int64_t ldE,
                    bool e_f64, double scale, hipStream_t st);
 
+// lowrank_decode.hip: the pair at 1 <= T <= 16 tokens as two weight-streaming products (ptd_lowrank_decode)
+bool lowrank_decode_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, const void* x, int64_t ldx,
+                           const void* A, int64_t lda, const void* B, int64_t ldb);
+size_t lowrank_decode_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r, const void* B,
+                   int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
+
 // eigh_jacobi.hip
 size_t eigh_workspace_bytes(int64_t n);
 int eigh_jacobi(const double* A, int64_t lda, int64_t n, int64_t k, double* evals, double* evecs, int64_t ldv,
