@@ -37,7 +37,8 @@ extern "C" {
                              *    two-stage reduction behind it are gone (2.2 x behind the default for three rounds)
                              * 5: the two-stream form of ptd_streams_wall_us is gone (the same call with count = 2)
                              * 6: PTD_F16 (IEEE half) wherever PTD_BF16 is accepted, same shapes, workspaces and codes
-                             *    (added since, no entry changed: ptd_lowrank_decode_workspace_bytes, ptd_lowrank_decode) */
+                             *    (added since, no entry changed: ptd_lowrank_decode_workspace_bytes, ptd_lowrank_decode,
+                             *    ptd_lowrank_skinny_workspace_bytes, ptd_lowrank_skinny) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -316,6 +317,20 @@ int ptd_lowrank_forward(const void* x, int64_t ldx, int64_t T, int64_t n_i, cons
  * the f32 partial sums of the first product's K split, added in a fixed order. */
 size_t ptd_lowrank_decode_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
 int ptd_lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r,
+                       const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy,
+                       void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* The same pair for 32 <= T <= 96 tokens (continuous batching, speculative verification, short prompt chunks) in
+ * bf16 / f16: skinny products on the caller's stream in which the first product's K range is split into f32 slabs,
+ * added in a fixed order and rounded once to h (arguments as ptd_lowrank_forward; same rounding points: f32 sums, h
+ * rounded once to the operand dtype, the bias added in f32, y rounded once).  The split depends on (n_i, r) alone: row
+ * t of y depends on row t of x alone, bit for bit, whatever T is.  Served: dtype bf16 / f16, 32 <= T <= 96, r >= 8,
+ * n_i, r and the leading dimensions ldx, lda, ldb multiples of 8, x, A and B 16-byte aligned, any n_o >= 1, bias
+ * optional.  Anything else (f32 included) returns PTD_ERR_UNSUPPORTED before a kernel is launched (the caller then
+ * takes ptd_lowrank_forward); null pointers, a leading dimension below its row length or a misaligned workspace
+ * PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  The workspace holds the slabs and h. */
+size_t ptd_lowrank_skinny_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int ptd_lowrank_skinny(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r,
                        const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy,
                        void* ws, size_t ws_bytes, int dtype, void* stream);
 

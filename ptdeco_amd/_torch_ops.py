@@ -2,7 +2,8 @@
 FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed layer.
 
     lowrank_forward(Tensor x2d, Tensor A, Tensor B, Tensor? bias) -> Tensor              ops.lowrank_forward, or
-                                                             ops.lowrank_decode where ops.lowrank_decode_serves (T <= 16)
+                                                             ops.lowrank_decode where ops.lowrank_decode_serves (T <= 16),
+                                                             ops.lowrank_skinny where ops.lowrank_skinny_serves (32 ... 96)
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -25,9 +26,12 @@ from . import ops
 @torch.library.custom_op("ptdeco_amd::lowrank_forward", mutates_args=())
 def lowrank_forward(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
     """(x2d @ A^T) @ B^T + bias with x2d [T, n_i], A [r, n_i], B [n_o, r]; y [T, n_o] contiguous.  At decode shapes
-    (1 <= T <= 16, aligned operands: ops.lowrank_decode_serves) on the weight-streaming kernels of ptd_lowrank_decode."""
+    (1 <= T <= 16, aligned operands: ops.lowrank_decode_serves) on the weight-streaming kernels of ptd_lowrank_decode,
+    at small batches (32 <= T <= 96, bf16 / f16: ops.lowrank_skinny_serves) on the skinny products of ptd_lowrank_skinny."""
     if ops.lowrank_decode_serves(x2d, A, B, bias):
         return ops.lowrank_decode(x2d, A, B, bias)
+    if ops.lowrank_skinny_serves(x2d, A, B, bias):
+        return ops.lowrank_skinny(x2d, A, B, bias)
     return ops.lowrank_forward(x2d, A, B, bias)
 
 

@@ -484,6 +484,32 @@ int ptd_lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const
   return lowrank_decode(x, ldx, T, n_i, A, lda, r, B, ldb, n_o, bias, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
 }
 
+size_t ptd_lowrank_skinny_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
+  return lowrank_skinny_workspace_bytes(T, n_i, r, dtype);
+}
+
+int ptd_lowrank_skinny(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r,
+                       const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws,
+                       size_t ws_bytes, int dtype, void* stream) {
+  PTD_REQUIRE(x && A && B && y && ws, "ptd_lowrank_skinny: null pointer");
+  PTD_REQUIRE(ldx >= n_i && lda >= n_i && ldb >= r && ldy >= n_o, "ptd_lowrank_skinny: bad leading dimension");
+  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16 || dtype == PTD_F16, "ptd_lowrank_skinny: dtype must be f32, bf16 or f16");
+  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_skinny: the workspace must be 16-byte aligned");
+  // (nothing is launched for a shape the skinny kernels do not serve: the caller takes ptd_lowrank_forward)
+  if (!lowrank_skinny_serves(T, n_i, r, n_o, dtype, x, ldx, A, lda, B, ldb)) {
+    set_error("ptd_lowrank_skinny: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d: bf16 or f16, 32 <= T <= 96, "
+              "r >= 8, n_i and r multiples of 8, 16-byte aligned rows)", (long long)T, (long long)n_i, (long long)r,
+              (long long)n_o, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  if (ws_bytes < lowrank_skinny_workspace_bytes(T, n_i, r, dtype)) {
+    set_error("ptd_lowrank_skinny: workspace %zu < required %zu bytes", ws_bytes,
+              lowrank_skinny_workspace_bytes(T, n_i, r, dtype));
+    return PTD_ERR_WORKSPACE;
+  }
+  return lowrank_skinny(x, ldx, T, n_i, A, lda, r, B, ldb, n_o, bias, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
+}
+
 size_t ptd_lowrank_forward_nchw_workspace_bytes(int64_t batch, int64_t hw, int64_t r, int dtype) {
   return align_up((size_t)batch * (size_t)r * (size_t)hw * elt_bytes(dtype), 256);
 }

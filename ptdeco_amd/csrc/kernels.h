@@ -54,6 +54,13 @@ size_t lowrank_decode_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dty
 int lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r, const void* B,
                    int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_skinny.hip: the pair at 32 <= T <= 96 tokens (bf16 / f16) as skinny products with a K split (ptd_lowrank_skinny)
+bool lowrank_skinny_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, const void* x, int64_t ldx,
+                           const void* A, int64_t lda, const void* B, int64_t ldb);
+size_t lowrank_skinny_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int lowrank_skinny(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r, const void* B,
+                   int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
+
 // eigh_jacobi.hip
 size_t eigh_workspace_bytes(int64_t n);
 int eigh_jacobi(const double* A, int64_t lda, int64_t n, int64_t k, double* evals, double* evecs, int64_t ldv,

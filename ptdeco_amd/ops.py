@@ -404,6 +404,66 @@ def lowrank_decode(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Op
     return y
 
 
+# The pair at small batches (32 <= T <= _SKINNY_MAX_T tokens, bf16 / f16) runs on ptd_lowrank_skinny: skinny products
+# with a K split that depends on the layer alone.  PTD_LOWRANK_SKINNY=0 sends these shapes through lowrank_forward again.
+# (T = 17 ... 31 stays on the tile path: lowering _SKINNY_MIN_T is all a later change needs here.  The cap is measured,
+# profiles/pair_skinny.json: the largest T of the probe's list up to which every bf16 cell beats the tile path -- at
+# T = 128 the tile path's own 128-row tiles win the 4096 -> 1024 -> 14336 cell.)
+_SKINNY = os.environ.get("PTD_LOWRANK_SKINNY", "1") != "0"
+_SKINNY_MIN_T = 32
+_SKINNY_MAX_T = 96
+
+
+def lowrank_skinny_serves(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``lowrank_skinny`` takes these operands as they lie (the rule of ptd_lowrank_skinny, without loading the
+    library): real tensors on a ROCm device, bf16 / f16, _SKINNY_MIN_T <= T <= _SKINNY_MAX_T, r >= 8, n_i, r and the row
+    pitches multiples of 8 elements, unit inner strides, 16-byte aligned data."""
+    if not _SKINNY:
+        return False
+    ts = (x2d, A, B) if bias is None else (x2d, A, B, bias)
+    for t in ts:
+        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
+            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
+    if x2d.dim() != 2 or A.dim() != 2 or B.dim() != 2 or not (x2d.dtype == A.dtype == B.dtype):
+        return False
+    if x2d.dtype not in (torch.bfloat16, torch.float16):
+        return False
+    (T, n_i), r, n_o = x2d.shape, A.shape[0], B.shape[0]
+    if A.shape[1] != n_i or B.shape[1] != r or not _SKINNY_MIN_T <= T <= _SKINNY_MAX_T:
+        return False
+    if n_o < 1 or r < 8 or n_i < 8 or n_i % 8 or r % 8:
+        return False
+    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o):
+        return False
+    for t in (x2d, A, B):
+        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % 8 or t.data_ptr() % 16:
+            return False
+    return True
+
+
+def lowrank_skinny(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """(x2d @ A^T) @ B^T + bias for 32 <= T <= _SKINNY_MAX_T rows of x2d, A [r, n_i], B [n_o, r], bf16 / f16:
+    ptd_lowrank_skinny.  A shape the entry does not serve (``lowrank_skinny_serves``) raises; row t of the result
+    depends on row t of x2d alone."""
+    _dev(x2d, A, B, bias)
+    x2d, A, B = _rows2d(x2d), _rows2d(A), _rows2d(B)
+    T, n_i = x2d.shape
+    r, n_o = A.shape[0], B.shape[0]
+    assert A.shape[1] == n_i and B.shape[1] == r and x2d.dtype == A.dtype == B.dtype
+    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
+    lib = _hip.load()
+    ws_bytes = lib.ptd_lowrank_skinny_workspace_bytes(T, n_i, r, _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+    if bias is not None:
+        bias = bias.to(x2d.dtype).contiguous()
+    with torch.cuda.device(x2d.device):
+        rc = lib.ptd_lowrank_skinny(x2d.data_ptr(), x2d.stride(0), T, n_i, A.data_ptr(), A.stride(0), r,
+                                    B.data_ptr(), B.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o,
+                                    ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
+    _hip.check(rc, "ptd_lowrank_skinny")
+    return y
+
+
 def lowrank_forward_nchw(x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
     """The rank-r 1x1-convolution pair on a contiguous NCHW input, no layout copy: per image
     y_b = B (A x_b) + bias[:, None] with x_b viewed [n_i, H W]; y is contiguous NCHW."""
