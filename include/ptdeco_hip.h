@@ -38,7 +38,8 @@ extern "C" {
                              * 5: the two-stream form of ptd_streams_wall_us is gone (the same call with count = 2)
                              * 6: PTD_F16 (IEEE half) wherever PTD_BF16 is accepted, same shapes, workspaces and codes
                              *    (added since, no entry changed: ptd_lowrank_decode_workspace_bytes, ptd_lowrank_decode,
-                             *    ptd_lowrank_skinny_workspace_bytes, ptd_lowrank_skinny) */
+                             *    ptd_lowrank_skinny_workspace_bytes, ptd_lowrank_skinny,
+                             *    ptd_launch_trace_begin, ptd_launch_trace_end) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -53,6 +54,18 @@ typedef enum {
 
 int ptd_version(void);
 const char* ptd_last_error(void);
+
+/* Host diagnostic for tests: which kernels did a call launch?  Every launch site of the library names its kernel family
+ * in a label ("gemm_bf16 (short K)", "gemm_f32 (split K)", ...; one label may stand for two launches that always go
+ * together, such as a split-K product and its reduction).  ptd_launch_trace_begin clears the trace of the CALLING
+ * THREAD and switches it on; from then on each successful launch of that thread appends its label: 32 are kept, further
+ * ones are only counted.  ptd_launch_trace_end switches the trace off and writes the kept labels in launch order,
+ * joined by '\n', NUL-terminated and truncated to `cap` bytes (buf may be NULL when cap is 0); it returns the number of
+ * labels recorded since begin (not of kernels: see above), those beyond 32 included, and 0 with an empty string without a begin.  Host state only: no
+ * device code, no allocation, no environment variable; switched off (the default) a launch pays one thread-local flag
+ * test.  No reference counterpart. */
+void ptd_launch_trace_begin(void);
+int ptd_launch_trace_end(char* buf, size_t cap);
 
 /* Hint: the caller is about to run `chains` independent eigendecompositions at once, each on its own stream
  * (the reference has no counterpart: torch.linalg.eigh calls are serial, dwain.py:155-163).  With chains > 1 the

@@ -20,6 +20,8 @@ ABI_VERSION = 6
 SIGNATURES = {
     "ptd_version": (c_int, []),
     "ptd_last_error": (c_char_p, []),
+    "ptd_launch_trace_begin": (None, []),
+    "ptd_launch_trace_end": (c_int, [c_void_p, c_size_t]),
     "ptd_set_concurrent_chains": (c_int, [c_int]),
     "ptd_streams_wall_us": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_double)]),
     "ptd_stream_create_dedicated": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p)]),

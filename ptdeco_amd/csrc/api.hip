@@ -19,6 +19,8 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+__thread LaunchTrace g_launch_trace = {false, 0, {nullptr}};
+
 }  // namespace ptd
 
 using namespace ptd;
@@ -34,6 +36,27 @@ extern "C" {
 int ptd_version(void) { return PTD_ABI_VERSION; }
 
 const char* ptd_last_error(void) { return g_err; }
+
+void ptd_launch_trace_begin(void) {
+  g_launch_trace.count = 0;
+  g_launch_trace.on = true;
+}
+
+int ptd_launch_trace_end(char* buf, size_t cap) {
+  LaunchTrace& t = g_launch_trace;
+  const int count = t.on ? t.count : 0;
+  t.on = false;
+  t.count = 0;
+  if (buf && cap) {
+    size_t pos = 0;
+    for (int i = 0; i < std::min(count, 32); ++i) {
+      if (i && pos + 1 < cap) buf[pos++] = '\n';
+      for (const char* s = t.what[i]; *s && pos + 1 < cap; ++s) buf[pos++] = *s;
+    }
+    buf[pos] = '\0';
+  }
+  return count;
+}
 
 int ptd_set_concurrent_chains(int chains) { return concurrent_chains_exchange(chains < 1 ? 1 : chains); }
 

@@ -19,6 +19,22 @@ void set_error(const char* fmt, ...);
     }                                   \
   } while (0)
 
+// Host-side launch trace (ptd_launch_trace_begin / _end): while it is switched on for the calling thread, every
+// successful PTD_CHECK_LAUNCH records its label -- a string literal -- so that a test can tell which kernel family a
+// call ended in.  32 slots; further launches are counted, not stored.  Off (the default) it costs one flag test.
+struct LaunchTrace {
+  bool on;
+  int count;
+  const char* what[32];
+};
+extern __thread LaunchTrace g_launch_trace;
+
+static inline void launch_trace_record(const char* what) {
+  LaunchTrace& t = g_launch_trace;
+  if (t.count < 32) t.what[t.count] = what;
+  ++t.count;
+}
+
 #define PTD_CHECK_LAUNCH(what)                                              \
   do {                                                                      \
     hipError_t e_ = hipGetLastError();                                      \
@@ -26,6 +42,7 @@ void set_error(const char* fmt, ...);
       ptd::set_error("%s: %s", what, hipGetErrorString(e_));                \
       return PTD_ERR_LAUNCH;                                                \
     }                                                                       \
+    if (ptd::g_launch_trace.on) ptd::launch_trace_record(what);             \
   } while (0)
 
 #define PTD_CHECK_HIP(expr)                                                 \

@@ -2797,11 +2797,17 @@ static int gemm16(const unsigned short* A, int64_t sam, int64_t sak, const unsig
     if (grid.x <= 256 && K >= 4 * BK && !no_deep) {  // at most one workgroup per CU: deep prefetch
       if (c_bf16) hipLaunchKernelGGL((gemm_bf16_nt_glds_kernel<EL, EPI_STORE_BF16, 4>), grid, dim3(256), 0, st, a);
       else hipLaunchKernelGGL((gemm_bf16_nt_glds_kernel<EL, EPI_STORE_F32, 4>), grid, dim3(256), 0, st, a);
-    } else if (c_bf16) hipLaunchKernelGGL((gemm_bf16_nt_glds_kernel<EL, EPI_STORE_BF16, 2>), grid, dim3(256), 0, st, a);
+      PTD_CHECK_LAUNCH("gemm_bf16 (LDS-DMA, 4 buffers)");
+      return PTD_OK;
+    }
+    if (c_bf16) hipLaunchKernelGGL((gemm_bf16_nt_glds_kernel<EL, EPI_STORE_BF16, 2>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((gemm_bf16_nt_glds_kernel<EL, EPI_STORE_F32, 2>), grid, dim3(256), 0, st, a);
-  } else if (c_bf16) launch_bf16<EL, EPI_STORE_BF16>(a, akc, bkc, grid, st);
+    PTD_CHECK_LAUNCH("gemm_bf16 (LDS-DMA, 2 buffers)");
+    return PTD_OK;
+  }
+  if (c_bf16) launch_bf16<EL, EPI_STORE_BF16>(a, akc, bkc, grid, st);
   else launch_bf16<EL, EPI_STORE_F32>(a, akc, bkc, grid, st);
-  PTD_CHECK_LAUNCH("gemm_bf16");
+  PTD_CHECK_LAUNCH("gemm_bf16 (generic)");
   return PTD_OK;
 }
 

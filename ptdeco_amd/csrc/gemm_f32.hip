@@ -529,10 +529,11 @@ int gemm_f32(const float* A, int64_t sam, int64_t sak, const float* B, int64_t s
     const int64_t quads = M * ceil_div(N, 4);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)ceil_div(quads, 256)), dim3(256), 0, st,
                        static_cast<const float*>(ws), ksplit, a.cslab, (int)M, (int)N, (float)alpha, bias, C, ldc);
-  } else {
-    launch_f32<EPI_STORE>(a, akc, bkc, dim3((unsigned)tiles, 1), st);
+    PTD_CHECK_LAUNCH("gemm_f32 (split K)");
+    return PTD_OK;
   }
-  PTD_CHECK_LAUNCH("gemm_f32");
+  launch_f32<EPI_STORE>(a, akc, bkc, dim3((unsigned)tiles, 1), st);
+  PTD_CHECK_LAUNCH("gemm_f32 (generic)");
   return PTD_OK;
 }
 

@@ -3,6 +3,7 @@ PyTorch-ROCm; all arithmetic happens in libptdeco_hip.so)."""
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import Optional
@@ -51,6 +52,29 @@ def _strides(t: torch.Tensor) -> tuple[torch.Tensor, int, int]:
         if s1 != 1:  # shape (k, 1) contiguous has strides (1, 1)
             s0, s1 = t.shape[1], 1
     return t, s0, s1
+
+
+@contextlib.contextmanager
+def launch_trace():
+    """Context manager that yields a list; on exit it holds the labels of the kernel launches the calling thread made
+    through the library inside the block, in order (ptd_launch_trace_begin / _end: at most 32 labels are kept, and
+    `.launches` of the list is the number of labels recorded, those beyond 32 included; a label may stand for two
+    kernels that always go together, such as a split-K product and its reduction).  For tests that must know which
+    kernel family a call reached."""
+    lib = _hip.load()
+
+    class _Labels(list):
+        launches = 0
+
+    labels = _Labels()
+    lib.ptd_launch_trace_begin()
+    try:
+        yield labels
+    finally:
+        buf = ctypes.create_string_buffer(4096)
+        labels.launches = lib.ptd_launch_trace_end(buf, len(buf))
+        text = buf.value.decode()
+        labels.extend(text.split("\n") if text else [])
 
 
 def syrk_accumulate(E: torch.Tensor, y: torch.Tensor, scale: float) -> None:

@@ -85,19 +85,28 @@ def _operand(rows, cols, trans, lo, hi, seed):
     return t.T if trans else t
 
 
-# (M, N, K) and the kernel the bf16 dispatcher picks for an NT product of that shape
-PATH_SHAPES = [
-    (2048, 768, 4096),     # 128 x 64 tiles
-    (1536, 768, 3072),     # split K into f32 slabs + the reduction kernel
-    (1024, 1024, 512),     # LDS-DMA, 4-deep
-    (2560, 2560, 128),     # LDS-DMA, 2 buffers (many tiles)
-    (4096, 4096, 512),     # 256 x 256, 8-phase (persistent form for f16 out)
-    (4096, 2048, 1024),    # 128 x 256, 6-phase
-    (4096, 1024, 256),     # short K, epilogue interleaved (no bias, alpha 1) / B panel resident
-    (4096, 1024, 128),     # short K, 256-column B panel resident
-    (1024, 640, 192),      # short K, 128-column B panel resident
-    (1024, 320, 384),      # short K, persistent over N
-]
+# (M, N, K) and the launch label ("gemm_bf16 (<label>)": the f16 kernels are instantiations of the bf16 ones and share
+# their labels) an NT product of that shape ends in, with f16 and with f32 output.  The test asserts them under
+# ops.launch_trace(): two entries were listed as LDS-DMA products and are short-K ones -- (1024, 1024, 512): M >= 1024,
+# 64 | N, K <= 512; (2560, 2560, 128): 256 | N, M >= 2048, K <= 256, both asked about earlier in the router -- they
+# stay under the label they reach, and the last two entries reach the LDS-DMA kernels they were meant for.
+# (f16 output, f32 output)
+PATH_LABELS = {
+    (2048, 768, 4096): ("128 x 64 tiles", "128 x 64 tiles"),
+    (1536, 768, 3072): ("split K", "split K"),     # f32 slabs + the reduction kernel
+    (1024, 1024, 512): ("short K", "short K"),
+    (2560, 2560, 128): ("short K, 256-column B panel resident", "short K, 256-column B panel resident"),
+    (4096, 4096, 512): ("256x256, persistent", "256x256"),
+    (4096, 2048, 1024): ("128x256", "LDS-DMA, 2 buffers"),    # (the 128 x 256 kernel stores 16-bit output only)
+    # f16 output without bias at alpha 1: "short K, epilogue interleaved" (see the test)
+    (4096, 1024, 256): ("short K, 256-column B panel resident", "short K, 256-column B panel resident"),
+    (4096, 1024, 128): ("short K, 256-column B panel resident", "short K, 256-column B panel resident"),
+    (1024, 640, 192): ("short K, B panel resident", "short K, B panel resident"),
+    (1024, 320, 384): ("short K", "short K"),      # persistent over N
+    (896, 896, 1088): ("LDS-DMA, 4 buffers", "LDS-DMA, 4 buffers"),     # 49 tiles, 17 K steps
+    (2176, 2048, 576): ("LDS-DMA, 2 buffers", "LDS-DMA, 2 buffers"),    # 272 tiles: more than one per CU
+}
+PATH_SHAPES = list(PATH_LABELS)
 
 
 @pytest.mark.parametrize("M,N,K", PATH_SHAPES)
@@ -105,18 +114,25 @@ PATH_SHAPES = [
 def test_gemm_f16_paths_round_like_torch_half(ops, M, N, K, alpha, with_bias):
     """Entries in -64 .. 64: every f32 sum is exact (< 2^24) and most are not f16 numbers -- the stored f16 must be the
     round-to-nearest-even of the exact value, bit for bit, and with alpha = 8 many exceed 65504: +-inf, as `.half()`.
-    The f32 output is the exact sum itself."""
+    The f32 output is the exact sum itself.  The launch trace proves the kernel family of both products."""
     a = _ints((M, K), -64, 64, M + K).to(DEV)
     b = _ints((N, K), -64, 64, N + 3 * K).to(DEV)
     bias = _ints((N,), -40, 40, N).to(DEV) if with_bias else None
     ref = alpha * (a.float() @ b.float().T) + (bias.float() if with_bias else 0.0)
-    got16 = ops.matmul(a, b.T, bias=bias, alpha=alpha)
+    label16, label32 = PATH_LABELS[(M, N, K)]
+    if (M, N, K) == (4096, 1024, 256) and not with_bias and alpha == 1.0:
+        label16 = "short K, epilogue interleaved"
+    with ops.launch_trace() as labels:
+        got16 = ops.matmul(a, b.T, bias=bias, alpha=alpha)
+    assert labels == [f"gemm_bf16 ({label16})"]
     assert got16.dtype == H
     want16 = ref.half()
     assert torch.equal(got16.view(torch.int16), want16.view(torch.int16)), (M, N, K)
     if alpha == 8.0:
         assert torch.isinf(want16).any() and not torch.isinf(want16).all()
-    got32 = ops.matmul(a, b.T, bias=bias, alpha=alpha, out_dtype=torch.float32)
+    with ops.launch_trace() as labels:
+        got32 = ops.matmul(a, b.T, bias=bias, alpha=alpha, out_dtype=torch.float32)
+    assert labels == [f"gemm_bf16 ({label32})"]
     assert torch.equal(got32, ref)
 
 

@@ -899,6 +899,23 @@ def test_twisted_factorisation_eigenvectors_match_inverse_iteration(ops, monkeyp
 LAYOUTS = ["nn", "nt", "tn", "tt"]
 
 
+def _traced(ops, label, fn, *args, **kw):
+    """fn(*args, **kw) under ops.launch_trace(): the call must end in exactly the launches `label` names (one label, or
+    a list for a call of several products), so a retuned router cannot quietly turn a kernel family's test into a
+    second test of another family."""
+    with ops.launch_trace() as labels:
+        out = fn(*args, **kw)
+    assert labels == ([label] if isinstance(label, str) else label), (labels, label, [tuple(getattr(a, "shape", ())) for a in args])
+    return out
+
+
+GLDS2, GLDS4 = "gemm_bf16 (LDS-DMA, 2 buffers)", "gemm_bf16 (LDS-DMA, 4 buffers)"
+SHORTK, SHORTK2 = "gemm_bf16 (short K)", "gemm_bf16 (short K, B panel resident)"
+SHORTK3, SHORTK4 = "gemm_bf16 (short K, 256-column B panel resident)", "gemm_bf16 (short K, epilogue interleaved)"
+T64, SPLITK = "gemm_bf16 (128 x 64 tiles)", "gemm_bf16 (split K)"
+T8PH, P8PH, T6PH = "gemm_bf16 (256x256)", "gemm_bf16 (256x256, persistent)", "gemm_bf16 (128x256)"
+
+
 def _operands(M, N, K, layout, dtype, seed):
     a = _rand((M, K) if layout[0] == "n" else (K, M), seed, dtype, 0.5)
     b = _rand((K, N) if layout[1] == "n" else (N, K), seed + 1, dtype, 0.5)
@@ -945,17 +962,22 @@ def test_gemm_bf16_f32_out_is_exact_products(ops):
 
 def test_gemm_bf16_direct_to_lds_path_exact(ops):
     """Tile-aligned nn.Linear layout takes the LDS-DMA kernel with the XOR-swizzled image: exact
-    integer products catch any mistake in the source / read swizzle pair or the XCD tile remap."""
+    integer products catch any mistake in the source / read swizzle pair or the XCD tile remap.  The launch trace
+    proves the kernel per shape (both products of a shape take the same one)."""
     g = torch.Generator().manual_seed(7)
     # K >= 256 on a grid of <= 256 tiles takes the 4-buffer variant (three K steps in flight, counted vmcnt)
-    for (M, N, K) in [(128, 128, 64), (256, 384, 192), (1024, 640, 512), (256, 256, 256), (384, 128, 320), (128, 256, 384),
-                      (256, 128, 448), (2048, 2048, 4096), (16384, 256, 4096)]:
+    # ((1024, 640, 512) is a short-K product: M >= 1024, 64 | N, N >= 256, K <= 512 is tested earlier in the router;
+    # (2176, 2048, 576) is the 2-buffer kernel on more than 256 tiles, (896, 896, 1088) the 4-buffer one on 49)
+    for (M, N, K, label) in [(128, 128, 64, GLDS2), (256, 384, 192, GLDS2), (1024, 640, 512, SHORTK), (256, 256, 256, GLDS4),
+                             (384, 128, 320, GLDS4), (128, 256, 384, GLDS4), (256, 128, 448, GLDS4),
+                             (2048, 2048, 4096, GLDS4), (16384, 256, 4096, GLDS4), (2176, 2048, 576, GLDS2),
+                             (896, 896, 1088, GLDS4)]:
         a = torch.randint(-4, 5, (M, K), generator=g).to(torch.bfloat16)
         b = torch.randint(-4, 5, (N, K), generator=g).to(torch.bfloat16)
         bias = torch.randint(-3, 4, (N,), generator=g).to(torch.bfloat16)
-        got = ops.matmul(a.to(DEV), b.to(DEV).T, bias=bias.to(DEV), out_dtype=torch.float32).cpu()
+        got = _traced(ops, label, ops.matmul, a.to(DEV), b.to(DEV).T, bias=bias.to(DEV), out_dtype=torch.float32).cpu()
         assert torch.equal(got, a.float() @ b.float().T + bias.float()), (M, N, K)
-        got16 = ops.matmul(a.to(DEV), b.to(DEV).T).cpu()
+        got16 = _traced(ops, label, ops.matmul, a.to(DEV), b.to(DEV).T).cpu()
         assert torch.equal(got16.float(), (a.float() @ b.float().T).to(torch.bfloat16).float()), (M, N, K)
 
 
@@ -971,38 +993,43 @@ def test_gemm_bf16_128x64_tile_path_exact(ops):
         b = torch.randint(-3, 4, (N, K), generator=g).to(torch.bfloat16)
         bias = torch.randint(-3, 4, (N,), generator=g).to(torch.bfloat16)
         ref = a.float() @ b.float().T
-        got = ops.matmul(a.to(DEV), b.to(DEV).T, bias=bias.to(DEV), out_dtype=torch.float32).cpu()
+        got = _traced(ops, T64, ops.matmul, a.to(DEV), b.to(DEV).T, bias=bias.to(DEV), out_dtype=torch.float32).cpu()
         assert torch.equal(got, ref + bias.float()), (M, N, K)
         for _ in range(2):
-            got16 = ops.matmul(a.to(DEV), b.to(DEV).T).cpu()
+            got16 = _traced(ops, T64, ops.matmul, a.to(DEV), b.to(DEV).T).cpu()
             assert torch.equal(got16.float(), ref.to(torch.bfloat16).float()), (M, N, K)
 
 
 def test_gemm_bf16_short_k_persistent_path_exact(ops):
     """K <= 512 with M >= 1024: the persistent-over-N kernel (A panel as register fragments, B tiles
     streamed through the swizzled LDS-DMA image, N cut into ranges).  Exact integer products for every
-    K / 64 instantiation, ragged range ends and a leading dimension larger than N."""
+    K / 64 instantiation, ragged range ends and a leading dimension larger than N.  Each shape names the short-K kernel
+    it reaches (launch trace): `k` the persistent-over-N one, `k2` the B panel resident, `k3` the 256-column panel; with
+    K = 256 on the latter the plain bf16 product (no bias, alpha 1) takes the interleaved epilogue, `k4`."""
     g = torch.Generator().manual_seed(8)
+    k, k2, k3, k4 = SHORTK, SHORTK2, SHORTK3, SHORTK4
     # (K <= 256 with N % 128 == 0 takes the form with the B panel resident and the workgroup persistent over M)
-    for (M, N, K) in [(1024, 256, 64), (1024, 320, 128), (1152, 4096, 256), (2048, 448, 192), (1024, 1024, 320),
-                      (1024, 256, 384), (1280, 576, 448), (2048, 256, 512), (16384, 4096, 256), (1088, 384, 192),
-                      (1024, 128, 128), (4160, 1152, 256),
-                      # N % 256 == 0, M >= 2048: 8-wave form, 1 .. 16 steps per workgroup (prologue / tail wait counts)
-                      (2048, 256, 64), (2112, 512, 128), (4160, 1024, 192), (2048, 4096, 256), (3072, 4096, 256),
-                      (4096, 4096, 256), (8192, 4096, 256), (6144, 8192, 128), (5120, 4096, 192)]:
+    for (M, N, K, with_bias, plain) in [
+            (1024, 256, 64, k2, k2), (1024, 320, 128, k, k), (1152, 4096, 256, k2, k2), (2048, 448, 192, k, k),
+            (1024, 1024, 320, k, k), (1024, 256, 384, k, k), (1280, 576, 448, k, k), (2048, 256, 512, k, k),
+            (16384, 4096, 256, k3, k4), (1088, 384, 192, k2, k2), (1024, 128, 128, k2, k2), (4160, 1152, 256, k2, k2),
+            # N % 256 == 0, M >= 2048: 8-wave form, 1 .. 16 steps per workgroup (prologue / tail wait counts)
+            (2048, 256, 64, k3, k3), (2112, 512, 128, k3, k3), (4160, 1024, 192, k3, k3), (2048, 4096, 256, k3, k4),
+            (3072, 4096, 256, k3, k4), (4096, 4096, 256, k3, k4), (8192, 4096, 256, k3, k4), (6144, 8192, 128, k3, k3),
+            (5120, 4096, 192, k3, k3)]:
         a = torch.randint(-4, 5, (M, K), generator=g).to(torch.bfloat16)
         b = torch.randint(-4, 5, (N, K), generator=g).to(torch.bfloat16)
         bias = torch.randint(-3, 4, (N,), generator=g).to(torch.bfloat16)
         ref = a.float() @ b.float().T
-        got = ops.matmul(a.to(DEV), b.to(DEV).T, bias=bias.to(DEV), out_dtype=torch.float32).cpu()
+        got = _traced(ops, with_bias, ops.matmul, a.to(DEV), b.to(DEV).T, bias=bias.to(DEV), out_dtype=torch.float32).cpu()
         assert torch.equal(got, ref + bias.float()), (M, N, K)
-        got16 = ops.matmul(a.to(DEV), b.to(DEV).T).cpu()
+        got16 = _traced(ops, plain, ops.matmul, a.to(DEV), b.to(DEV).T).cpu()
         assert torch.equal(got16.float(), ref.to(torch.bfloat16).float()), (M, N, K)
     # the pair forward takes it for its second product
     x = torch.randint(-2, 3, (2048, 512), generator=g).to(torch.bfloat16)
     a1 = torch.randint(-2, 3, (128, 512), generator=g).to(torch.bfloat16)
     b1 = torch.randint(-1, 2, (384, 128), generator=g).to(torch.bfloat16)
-    y = ops.lowrank_forward(x.to(DEV), a1.to(DEV), b1.to(DEV), None).cpu().float()
+    y = _traced(ops, [GLDS4, SHORTK2], ops.lowrank_forward, x.to(DEV), a1.to(DEV), b1.to(DEV), None).cpu().float()
     h = (x.float() @ a1.float().T).to(torch.bfloat16).float()
     assert torch.equal(y, (h @ b1.float().T).to(torch.bfloat16).float())
 
@@ -1011,19 +1038,23 @@ def test_gemm_bf16_256_tile_deep_pipeline_exact_and_repeatable(ops):
     """M, N multiples of 256, K of 128 and >= 192 tiles: the 256 x 256 / 8-wave kernel whose LDS-DMA
     stays in flight across raw barriers (counted vmcnt).  Exact integer products over whole tiles catch a
     half tile read before it landed or restaged before its last read; repeats screen for races that
-    only show under a different arrival order.  The reference is the f32 product of the same integers."""
+    only show under a different arrival order.  The reference is the f32 product of the same integers.  Launch trace:
+    the f32 output takes the one-tile-per-workgroup kernel, the bf16 output its persistent form -- except K = 256, which
+    the router hands to the 256-column-panel short-K kernels before it asks about 256 x 256 tiles (the shape stays, under
+    the label it reaches; K = 384 is the shortest K of the 256 x 256 kernels)."""
     g = torch.Generator().manual_seed(9)
     for (M, N, K) in [(4096, 4096, 256), (3584, 4096, 384), (4096, 3584, 1024), (16384, 1024, 4096), (4096, 4096, 4096)]:
+        label32, label16 = (SHORTK3, SHORTK4) if K == 256 else (T8PH, P8PH)
         a = torch.randint(-2, 3, (M, K), generator=g).to(torch.bfloat16)
         b = torch.randint(-2, 3, (N, K), generator=g).to(torch.bfloat16)
         bias = torch.randint(-3, 4, (N,), generator=g).to(torch.bfloat16)
         ad, bd, biasd = a.to(DEV), b.to(DEV), bias.to(DEV)
         ref = (ad.float() @ bd.float().T)  # exact: |sum| <= 4 K < 2^24
-        got = ops.matmul(ad, bd.T, bias=biasd, out_dtype=torch.float32)
+        got = _traced(ops, label32, ops.matmul, ad, bd.T, bias=biasd, out_dtype=torch.float32)
         assert torch.equal(got, ref + biasd.float()), (M, N, K)
         want16 = ref.to(torch.bfloat16)
         for rep in range(6):
-            got16 = ops.matmul(ad, bd.T)
+            got16 = _traced(ops, label16, ops.matmul, ad, bd.T)
             assert torch.equal(got16, want16), (M, N, K, rep)
     # operands that are column slices of wider matrices (row pitch != K)
     big = torch.randint(-2, 3, (4096, 512 + 256), generator=g).to(torch.bfloat16).to(DEV)
@@ -1038,12 +1069,17 @@ def test_gemm_bf16_256_tile_persistent_form_exact_and_repeatable(ops, monkeypatc
     CU walks tiles b, b + 256, ...; a tile's last K-step pair stages the first two K steps of the NEXT tile, the
     finished tile leaves through the 32-KiB swizzled image behind the staging slots).  Exact integer products: a
     half tile of the wrong tile, a slot restaged before its last read or an image row written to the wrong place
-    shows.  Shapes: one K-step pair per tile (every pair both follows and precedes an epilogue), two, four, many;
-    272 tiles (16 workgroups take a second tile, the others stop), 512 (two each), 1024 (four each), a ragged 17 x 19;
-    bias and alpha; the one-tile kernel (PTD_GEMM_8PH_PERSIST=0) must give the same bits."""
+    shows.  Shapes that reach it (launch trace): three K-step pairs per tile (K = 384, the shortest K the router lets
+    through), four, eight, many; 272 tiles (16 workgroups take a second tile, the others stop), 1024 (four each), a ragged
+    17 x 19; bias and alpha; the one-tile kernel (PTD_GEMM_8PH_PERSIST=0) must give the same bits.
+    The K = 128 and K = 256 shapes were written for tiles of one and two K-step pairs, but do NOT reach this kernel:
+    K <= 256 with 256 | N and M >= 2048 is a short-K product (256-column panel; K = 256 plain: interleaved epilogue), so
+    those tile forms are unreachable through the router (code to retire or to route to: a follow-up).  The shapes stay,
+    under the label they reach; (4352, 4096, 384) and (16384, 4096, 384) are added for the persistent form."""
     g = torch.Generator().manual_seed(19)
     for (M, N, K) in [(4352, 4096, 128), (8192, 4096, 256), (16384, 4096, 512), (4352, 4864, 1024), (8192, 4096, 4096),
-                      (16384, 4096, 128)]:
+                      (16384, 4096, 128), (4352, 4096, 384), (16384, 4096, 384)]:
+        plain, scaled = (P8PH, P8PH) if K > 256 else (SHORTK4 if K == 256 else SHORTK3, SHORTK3)
         a = torch.randint(-2, 3, (M, K), generator=g).to(torch.bfloat16).to(DEV)
         b = torch.randint(-2, 3, (N, K), generator=g).to(torch.bfloat16).to(DEV)
         bias = torch.randint(-3, 4, (N,), generator=g).to(torch.bfloat16).to(DEV)
@@ -1051,10 +1087,10 @@ def test_gemm_bf16_256_tile_persistent_form_exact_and_repeatable(ops, monkeypatc
         want = ref.to(torch.bfloat16)
         want_b = (0.5 * ref + bias.float()).to(torch.bfloat16)
         for rep in range(3):
-            assert torch.equal(ops.matmul(a, b.T), want), (M, N, K, rep)
-        assert torch.equal(ops.matmul(a, b.T, bias=bias, alpha=0.5), want_b), (M, N, K)
+            assert torch.equal(_traced(ops, plain, ops.matmul, a, b.T), want), (M, N, K, rep)
+        assert torch.equal(_traced(ops, scaled, ops.matmul, a, b.T, bias=bias, alpha=0.5), want_b), (M, N, K)
         monkeypatch.setenv("PTD_GEMM_8PH_PERSIST", "0")
-        assert torch.equal(ops.matmul(a, b.T), want), (M, N, K, "one tile per workgroup")
+        assert torch.equal(_traced(ops, T8PH if K > 256 else plain, ops.matmul, a, b.T), want), (M, N, K, "one tile per workgroup")
         monkeypatch.delenv("PTD_GEMM_8PH_PERSIST")
     # row pitches larger than K / N (operands and output are column slices of wider matrices)
     xa = torch.randint(-2, 3, (8192, 512 + 128), generator=g).to(torch.bfloat16).to(DEV)
@@ -1076,10 +1112,11 @@ def test_gemm_bf16_128x256_tile_three_buffer_ring_exact_and_repeatable(ops, monk
         ref = a.float() @ b.float().T                      # exact: |sum| <= 4 K < 2^24
         want = ref.to(torch.bfloat16)
         for rep in range(3):
-            assert torch.equal(ops.matmul(a, b.T), want), (M, N, K, rep)
-        assert torch.equal(ops.matmul(a, b.T, bias=bias, alpha=0.5), (0.5 * ref + bias.float()).to(torch.bfloat16)), (M, N, K)
+            assert torch.equal(_traced(ops, T6PH, ops.matmul, a, b.T), want), (M, N, K, rep)
+        assert torch.equal(_traced(ops, T6PH, ops.matmul, a, b.T, bias=bias, alpha=0.5),
+                           (0.5 * ref + bias.float()).to(torch.bfloat16)), (M, N, K)
         monkeypatch.setenv("PTD_GEMM_6PH", "0")
-        assert torch.equal(ops.matmul(a, b.T), want), (M, N, K, "128 x 128 kernel")
+        assert torch.equal(_traced(ops, GLDS2, ops.matmul, a, b.T), want), (M, N, K, "128 x 128 kernel")
         monkeypatch.delenv("PTD_GEMM_6PH")
     xa = torch.randint(-2, 3, (16384, 1024 + 128), generator=g).to(torch.bfloat16).to(DEV)   # row pitch != K
     wa = torch.randint(-2, 3, (512, 1024 + 64), generator=g).to(torch.bfloat16).to(DEV)
@@ -1099,8 +1136,9 @@ def test_lowrank_forward_bf16_split_k_first_product_exact(ops):
         bias = torch.randint(-3, 4, (n_o,), generator=g).to(torch.bfloat16).to(DEV)
         h = (x.float() @ a.float().T).to(torch.bfloat16).float()
         want = (h @ b.float().T + bias.float()).to(torch.bfloat16)
+        second = {256: SHORTK3, 128: SHORTK2, 512: T64}[r]
         for rep in range(3):
-            got = ops.lowrank_forward(x, a, b, bias)
+            got = _traced(ops, [SPLITK, second], ops.lowrank_forward, x, a, b, bias)
             assert torch.equal(got, want), (T, n_i, r, n_o, rep)
 
 
@@ -1115,7 +1153,7 @@ def test_gemm_f32_256_tile_deep_pipeline_exact_and_repeatable(ops):
         bias = torch.randint(-3, 4, (N,), generator=g).float().to(DEV)
         ref = (a.double() @ b.double().T + bias.double()).float()
         for rep in range(4):
-            got = ops.matmul(a, b.T, bias=bias)
+            got = _traced(ops, "gemm_f32 (256x256)", ops.matmul, a, b.T, bias=bias)
             assert torch.equal(got, ref), (M, N, K, rep)
     # operands that are column slices of wider matrices, random data against f64
     big = torch.randn(4096, 1024 + 256, generator=g).to(DEV)
