@@ -39,7 +39,8 @@ extern "C" {
                              * 6: PTD_F16 (IEEE half) wherever PTD_BF16 is accepted, same shapes, workspaces and codes
                              *    (added since, no entry changed: ptd_lowrank_decode_workspace_bytes, ptd_lowrank_decode,
                              *    ptd_lowrank_skinny_workspace_bytes, ptd_lowrank_skinny,
-                             *    ptd_launch_trace_begin, ptd_launch_trace_end) */
+                             *    ptd_launch_trace_begin, ptd_launch_trace_end,
+                             *    ptd_lowrank_decode_group_workspace_bytes, ptd_lowrank_decode_group) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -332,6 +333,25 @@ size_t ptd_lowrank_decode_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int
 int ptd_lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r,
                        const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy,
                        void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* 1 <= count <= PTD_LOWRANK_GROUP_MAX pairs that read the same x at decode shapes (the q / k / v or gate / up projections
+ * of a decomposed transformer block) in two launches on the caller's stream instead of two per pair.  Member m has its
+ * own A[m] [r[m], n_i], B[m] [n_o[m], r[m]], optional bias[m] and output y[m] [T, n_o[m]] with row pitch ldy[m] (the
+ * column blocks of one [T, sum n_o] tensor, or unrelated buffers); x, T, n_i and dtype are common.  Every y[m] holds the
+ * bits ptd_lowrank_decode gives for that member alone.  The argument arrays are read before the call returns and not
+ * after it (the call may be captured in a graph).  Served when every member is served by ptd_lowrank_decode with the
+ * common x, T, n_i and dtype; anything else, count outside 1 .. PTD_LOWRANK_GROUP_MAX included, returns
+ * PTD_ERR_UNSUPPORTED before a kernel is launched.  Null pointers (bias, or an entry of it, may be NULL), a leading
+ * dimension below its row length or a misaligned workspace PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  The
+ * workspace is the sum of the members' ptd_lowrank_decode workspaces (each a multiple of 256 bytes). */
+#define PTD_LOWRANK_GROUP_MAX 4
+size_t ptd_lowrank_decode_group_workspace_bytes(int count, int64_t T, int64_t n_i, const int64_t* r, int dtype);
+int ptd_lowrank_decode_group(const void* x, int64_t ldx, int64_t T, int64_t n_i, int count,
+                             const void* const* A, const int64_t* lda, const int64_t* r,
+                             const void* const* B, const int64_t* ldb, const int64_t* n_o,
+                             const void* const* bias /* entries may be NULL; the array may be NULL */,
+                             void* const* y, const int64_t* ldy,
+                             void* ws, size_t ws_bytes, int dtype, void* stream);
 
 /* The same pair for 32 <= T <= 96 tokens (continuous batching, speculative verification, short prompt chunks) in
  * bf16 / f16: skinny products on the caller's stream in which the first product's K range is split into f32 slabs,

@@ -4,6 +4,10 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
     lowrank_forward(Tensor x2d, Tensor A, Tensor B, Tensor? bias) -> Tensor              ops.lowrank_forward, or
                                                              ops.lowrank_decode where ops.lowrank_decode_serves (T <= 16),
                                                              ops.lowrank_skinny where ops.lowrank_skinny_serves (32 ... 96)
+    lowrank_forward_group(Tensor x2d, Tensor[] As, Tensor[] Bs, Tensor?[] biases) -> Tensor
+                                                             ops.lowrank_decode_group where ops.lowrank_decode_group_serves
+                                                             (1 to 4 pairs on one x2d, T <= 16), else member by member
+                                                             as lowrank_forward chooses
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -16,7 +20,7 @@ tensor (numel 0) of dy's dtype; the autograd formula of ``lowrank_forward`` hand
 
 from __future__ import annotations
 
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -42,6 +46,44 @@ def _(x2d, A, B, bias):
     torch._check(x2d.dtype == A.dtype == B.dtype, lambda: "lowrank_forward: x2d, A and B must share a dtype")
     torch._check(bias is None or tuple(bias.shape) == (B.shape[0],), lambda: "lowrank_forward: bias must be [n_o]")
     return x2d.new_empty((x2d.shape[0], B.shape[0]))
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_group", mutates_args=())
+def lowrank_forward_group(x2d: torch.Tensor, As: List[torch.Tensor], Bs: List[torch.Tensor],
+                          biases: List[Optional[torch.Tensor]]) -> torch.Tensor:
+    """Pairs that share x2d [T, n_i], side by side: y [T, sum n_o] contiguous, member m = (As[m] [r_m, n_i],
+    Bs[m] [n_o_m, r_m], biases[m]) in columns [off_m, off_m + n_o_m).  At decode shapes two launches for the group
+    (ops.lowrank_decode_group_serves: ptd_lowrank_decode_group, every member's bits those of ops.lowrank_decode);
+    otherwise each member on the entry lowrank_forward picks for it.  Inference only: no autograd formula."""
+    if ops.lowrank_decode_group_serves(x2d, As, Bs, biases):
+        return ops.lowrank_decode_group(x2d, As, Bs, biases)
+    y = x2d.new_empty((x2d.shape[0], sum(B.shape[0] for B in Bs)))
+    off = 0
+    for A, B, bias in zip(As, Bs, biases):
+        if ops.lowrank_decode_serves(x2d, A, B, bias):
+            ym = ops.lowrank_decode(x2d, A, B, bias)
+        elif ops.lowrank_skinny_serves(x2d, A, B, bias):
+            ym = ops.lowrank_skinny(x2d, A, B, bias)
+        else:
+            ym = ops.lowrank_forward(x2d, A, B, bias)
+        y[:, off:off + B.shape[0]] = ym
+        off += B.shape[0]
+    return y
+
+
+@lowrank_forward_group.register_fake
+def _(x2d, As, Bs, biases):
+    torch._check(len(As) >= 1 and len(Bs) == len(As) and len(biases) == len(As),
+                 lambda: "lowrank_forward_group: As, Bs and biases must list the same members, at least one")
+    torch._check(x2d.dim() == 2, lambda: "lowrank_forward_group: x2d must be 2-D")
+    for A, B, bias in zip(As, Bs, biases):
+        torch._check(A.dim() == 2 and B.dim() == 2, lambda: "lowrank_forward_group: 2-D operands")
+        torch._check(A.shape[1] == x2d.shape[1] and B.shape[1] == A.shape[0], lambda: "lowrank_forward_group: shape mismatch")
+        torch._check(x2d.dtype == A.dtype == B.dtype, lambda: "lowrank_forward_group: x2d, A and B must share a dtype")
+        torch._check(A.device == x2d.device and B.device == x2d.device and (bias is None or bias.device == x2d.device),
+                     lambda: "lowrank_forward_group: every operand must be on x2d's device")
+        torch._check(bias is None or tuple(bias.shape) == (B.shape[0],), lambda: "lowrank_forward_group: bias must be [n_o]")
+    return x2d.new_empty((x2d.shape[0], sum(B.shape[0] for B in Bs)))
 
 
 @torch.library.custom_op("ptdeco_amd::lowrank_forward_nchw", mutates_args=())

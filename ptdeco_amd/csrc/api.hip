@@ -507,6 +507,45 @@ int ptd_lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const
   return lowrank_decode(x, ldx, T, n_i, A, lda, r, B, ldb, n_o, bias, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
 }
 
+size_t ptd_lowrank_decode_group_workspace_bytes(int count, int64_t T, int64_t n_i, const int64_t* r, int dtype) {
+  if (!r || count < 1 || count > PTD_LOWRANK_GROUP_MAX) return 0;
+  return lowrank_decode_group_workspace_bytes(count, T, n_i, r, dtype);
+}
+
+int ptd_lowrank_decode_group(const void* x, int64_t ldx, int64_t T, int64_t n_i, int count, const void* const* A,
+                             const int64_t* lda, const int64_t* r, const void* const* B, const int64_t* ldb,
+                             const int64_t* n_o, const void* const* bias, void* const* y, const int64_t* ldy, void* ws,
+                             size_t ws_bytes, int dtype, void* stream) {
+  PTD_REQUIRE(x && A && lda && r && B && ldb && n_o && y && ldy && ws, "ptd_lowrank_decode_group: null pointer");
+  if (count < 1 || count > PTD_LOWRANK_GROUP_MAX) {
+    set_error("ptd_lowrank_decode_group: not served (count=%d: 1 <= count <= %d)", count, PTD_LOWRANK_GROUP_MAX);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16 || dtype == PTD_F16,
+              "ptd_lowrank_decode_group: dtype must be f32, bf16 or f16");
+  PTD_REQUIRE(ldx >= n_i, "ptd_lowrank_decode_group: bad leading dimension");
+  for (int m = 0; m < count; ++m) {
+    PTD_REQUIRE(A[m] && B[m] && y[m], "ptd_lowrank_decode_group: null pointer (member %d)", m);
+    PTD_REQUIRE(lda[m] >= n_i && ldb[m] >= r[m] && ldy[m] >= n_o[m],
+                "ptd_lowrank_decode_group: bad leading dimension (member %d)", m);
+  }
+  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_decode_group: the workspace must be 16-byte aligned");
+  // (nothing is launched for a group the kernels do not serve: the caller runs the members one by one)
+  if (!lowrank_decode_group_serves(count, T, n_i, r, n_o, dtype, x, ldx, A, lda, B, ldb)) {
+    set_error("ptd_lowrank_decode_group: not served (count=%d T=%lld n_i=%lld dtype=%d: for every member 1 <= T <= 16, "
+              "r >= 8, n_i and r multiples of %d, 16-byte aligned rows)", count, (long long)T, (long long)n_i, dtype,
+              dtype == PTD_F32 ? 4 : 8);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  const size_t need = lowrank_decode_group_workspace_bytes(count, T, n_i, r, dtype);
+  if (ws_bytes < need) {
+    set_error("ptd_lowrank_decode_group: workspace %zu < required %zu bytes", ws_bytes, need);
+    return PTD_ERR_WORKSPACE;
+  }
+  return lowrank_decode_group(x, ldx, T, n_i, count, A, lda, r, B, ldb, n_o, bias, y, ldy, ws, dtype,
+                              static_cast<hipStream_t>(stream));
+}
+
 size_t ptd_lowrank_skinny_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
   return lowrank_skinny_workspace_bytes(T, n_i, r, dtype);
 }

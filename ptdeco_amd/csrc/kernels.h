@@ -54,6 +54,17 @@ size_t lowrank_decode_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dty
 int lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r, const void* B,
                    int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_group.hip: 1 .. PTD_LOWRANK_GROUP_MAX pairs on one input at decode shapes in two launches (ptd_lowrank_decode_group);
+// every member's bits are lowrank_decode's on that member alone
+bool lowrank_decode_group_serves(int count, int64_t T, int64_t n_i, const int64_t* r, const int64_t* n_o, int dtype,
+                                 const void* x, int64_t ldx, const void* const* A, const int64_t* lda,
+                                 const void* const* B, const int64_t* ldb);
+size_t lowrank_decode_group_workspace_bytes(int count, int64_t T, int64_t n_i, const int64_t* r, int dtype);
+int lowrank_decode_group(const void* x, int64_t ldx, int64_t T, int64_t n_i, int count, const void* const* A,
+                         const int64_t* lda, const int64_t* r, const void* const* B, const int64_t* ldb,
+                         const int64_t* n_o, const void* const* bias, void* const* y, const int64_t* ldy, void* ws,
+                         int dtype, hipStream_t st);
+
 // lowrank_skinny.hip: the pair at 32 <= T <= 96 tokens (bf16 / f16) as skinny products with a K split (ptd_lowrank_skinny)
 bool lowrank_skinny_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, const void* x, int64_t ldx,
                            const void* A, int64_t lda, const void* B, int64_t ldb);

@@ -23,6 +23,7 @@ from . import _torch_ops  # noqa: F401  (registers torch.ops.ptdeco_amd.*)
 
 _lowrank_forward = torch.ops.ptdeco_amd.lowrank_forward.default
 _lowrank_forward_nchw = torch.ops.ptdeco_amd.lowrank_forward_nchw.default
+_lowrank_forward_group = torch.ops.ptdeco_amd.lowrank_forward_group.default
 
 logger = logging.getLogger(__name__)
 
@@ -75,6 +76,28 @@ class LowRankConv1x1(torch.nn.Sequential):
         rows = x.permute(0, 2, 3, 1).reshape(-1, c)  # NHWC rows: a view for channels_last inputs
         y = _lowrank_forward(rows, wa, wb, bias)
         return y.reshape(b, h, w, second.out_channels).permute(0, 3, 1, 2)
+
+
+def lowrank_group(x: torch.Tensor, pairs) -> torch.Tensor:
+    """The outputs of installed ``LowRankLinear`` modules that read the same x, side by side: [..., sum out_features],
+    member m in the columns after those of the members before it (``y.split([p[1].out_features for p in pairs], -1)``
+    are the members' outputs).  For the q / k / v and gate / up projections of a decomposed transformer block: at decode
+    shapes (1 to 16 tokens, up to four members) the group runs in two kernel launches instead of two per member, and
+    every member's output is bit for bit what the member returns alone.  Inference only: when a gradient is wanted, or
+    a member is not a ``LowRankLinear`` on the HIP kernels' tensors, this is ``torch.cat([p(x) for p in pairs], -1)``.
+    It keeps no state: the modules, their ``state_dict`` and the decompose config are untouched."""
+    pairs = list(pairs)
+    fused = len(pairs) > 0 and all(isinstance(p, LowRankLinear) and p[0].in_features == pairs[0][0].in_features
+                                   for p in pairs)
+    fused = fused and all(_use_hip(x, p[0].weight, "LowRankLinear") for p in pairs)
+    if fused and torch.is_grad_enabled():
+        fused = not (x.requires_grad or any(q.requires_grad for p in pairs for q in p.parameters()))
+    if not fused:
+        return torch.cat([p(x) for p in pairs], -1)
+    x2d = x.reshape(-1, pairs[0][0].in_features)
+    y = _lowrank_forward_group(x2d, [p[0].weight for p in pairs], [p[1].weight for p in pairs],
+                               [p[1].bias for p in pairs])
+    return y.reshape(*x.shape[:-1], y.shape[1])
 
 
 def _is_plain_1x1(m: torch.nn.Module) -> bool:

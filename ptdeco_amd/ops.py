@@ -6,7 +6,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 
@@ -425,6 +425,52 @@ def lowrank_decode(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Op
                                     B.data_ptr(), B.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o,
                                     ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
     _hip.check(rc, "ptd_lowrank_decode")
+    return y
+
+
+# Pairs that read one input at decode shapes (q / k / v, gate / up) run on ptd_lowrank_decode_group: two launches for the
+# group instead of two per pair; every member's columns hold the bits lowrank_decode gives for that member alone.
+_GROUP_MAX = 4
+
+
+def lowrank_decode_group_serves(x2d: torch.Tensor, As: Sequence[torch.Tensor], Bs: Sequence[torch.Tensor],
+                                biases: Sequence[Optional[torch.Tensor]]) -> bool:
+    """Whether ``lowrank_decode_group`` takes these operands as they lie (the rule of ptd_lowrank_decode_group, without
+    loading the library): 1 to 4 members, each served by ``lowrank_decode`` on the common x2d."""
+    if not 1 <= len(As) <= _GROUP_MAX or len(Bs) != len(As) or len(biases) != len(As):
+        return False
+    return all(lowrank_decode_serves(x2d, A, B, bias) for A, B, bias in zip(As, Bs, biases))
+
+
+def lowrank_decode_group(x2d: torch.Tensor, As: Sequence[torch.Tensor], Bs: Sequence[torch.Tensor],
+                         biases: Sequence[Optional[torch.Tensor]]) -> torch.Tensor:
+    """[(x2d @ A_m^T) @ B_m^T + bias_m for m] side by side: y [T, sum n_o] contiguous, member m in columns
+    [off_m, off_m + n_o_m), for 1 <= T <= 16 rows of x2d and 1 to 4 members A_m [r_m, n_i], B_m [n_o_m, r_m]:
+    ptd_lowrank_decode_group.  A group the entry does not serve (``lowrank_decode_group_serves``) raises."""
+    count = len(As)
+    assert 1 <= count and len(Bs) == count and len(biases) == count
+    _dev(x2d, *As, *Bs, *biases)
+    x2d, As, Bs = _rows2d(x2d), [_rows2d(A) for A in As], [_rows2d(B) for B in Bs]
+    T, n_i = x2d.shape
+    for A, B in zip(As, Bs):
+        assert A.shape[1] == n_i and B.shape[1] == A.shape[0] and x2d.dtype == A.dtype == B.dtype
+    biases = [None if b is None else b.to(x2d.dtype).contiguous() for b in biases]
+    widths = [B.shape[0] for B in Bs]
+    total = sum(widths)
+    y = torch.empty((T, total), dtype=x2d.dtype, device=x2d.device)
+    offs = [sum(widths[:m]) * y.element_size() for m in range(count)]
+    ptrs, i64s = ctypes.c_void_p * count, ctypes.c_int64 * count
+    r = i64s(*[A.shape[0] for A in As])
+    lib = _hip.load()
+    ws_bytes = lib.ptd_lowrank_decode_group_workspace_bytes(count, T, n_i, r, _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+    with torch.cuda.device(x2d.device):
+        rc = lib.ptd_lowrank_decode_group(
+            x2d.data_ptr(), x2d.stride(0), T, n_i, count, ptrs(*[A.data_ptr() for A in As]),
+            i64s(*[A.stride(0) for A in As]), r, ptrs(*[B.data_ptr() for B in Bs]), i64s(*[B.stride(0) for B in Bs]),
+            i64s(*widths), ptrs(*[_ptr(b) for b in biases]), ptrs(*[y.data_ptr() + off for off in offs]),
+            i64s(*[total] * count), ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
+    _hip.check(rc, "ptd_lowrank_decode_group")
     return y
 
 
