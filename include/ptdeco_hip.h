@@ -40,7 +40,8 @@ extern "C" {
                              *    (added since, no entry changed: ptd_lowrank_decode_workspace_bytes, ptd_lowrank_decode,
                              *    ptd_lowrank_skinny_workspace_bytes, ptd_lowrank_skinny,
                              *    ptd_launch_trace_begin, ptd_launch_trace_end,
-                             *    ptd_lowrank_decode_group_workspace_bytes, ptd_lowrank_decode_group) */
+                             *    ptd_lowrank_decode_group_workspace_bytes, ptd_lowrank_decode_group,
+                             *    ptd_lowrank_decode_gated_workspace_bytes, ptd_lowrank_decode_gated) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -351,6 +352,27 @@ int ptd_lowrank_decode_group(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                              const void* const* B, const int64_t* ldb, const int64_t* n_o,
                              const void* const* bias /* entries may be NULL; the array may be NULL */,
                              void* const* y, const int64_t* ldy,
+                             void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* The gated pair of a decomposed MLP at decode shapes, y = act(gate(x)) * up(x) with gate = (Ag [r_g, n_i], Bg [n_ff, r_g],
+ * bias_g) and up = (Au [r_u, n_i], Bu [n_ff, r_u], bias_u) on the same x [T, n_i], in two launches on the caller's stream:
+ * both first products, then a kernel that forms both second products row tile by row tile and applies the activation
+ * and the product in the lane that holds both sums (no [T, 2 n_ff] intermediate, no elementwise launch).  g and u are
+ * the bits ptd_lowrank_decode stores for gate and up; the activation is evaluated in f32 on g and rounded once to the
+ * dtype, its product with u is formed in f32 and rounded once -- the rounding points of the unfused act(g) * u.
+ * act: PTD_ACT_SILU v / (1 + exp(-v)), PTD_ACT_GELU_TANH 0.5 v (1 + tanh(sqrt(2 / pi) (v + 0.044715 v^3))),
+ * PTD_ACT_RELU.  Served when both members are served by ptd_lowrank_decode with the common x, T, n_i, n_ff and dtype
+ * and act is one of the three; anything else returns PTD_ERR_UNSUPPORTED before a kernel is launched.  Null pointers
+ * (either bias may be NULL), a leading dimension below its row length or a misaligned workspace PTD_ERR_INVALID; a
+ * short workspace PTD_ERR_WORKSPACE.  The workspace is the sum of the two members' ptd_lowrank_decode workspaces. */
+#define PTD_ACT_SILU 0
+#define PTD_ACT_GELU_TANH 1
+#define PTD_ACT_RELU 2
+size_t ptd_lowrank_decode_gated_workspace_bytes(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype);
+int ptd_lowrank_decode_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                             const void* Ag, int64_t lda_g, int64_t r_g, const void* Bg, int64_t ldb_g, const void* bias_g,
+                             const void* Au, int64_t lda_u, int64_t r_u, const void* Bu, int64_t ldb_u, const void* bias_u,
+                             int64_t n_ff, int act, void* y, int64_t ldy,
                              void* ws, size_t ws_bytes, int dtype, void* stream);
 
 /* The same pair for 32 <= T <= 96 tokens (continuous batching, speculative verification, short prompt chunks) in

@@ -79,6 +79,11 @@ SIGNATURES = {
     "ptd_lowrank_decode_group": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                          c_int, c_void_p]),
+    "ptd_lowrank_decode_gated_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
+    "ptd_lowrank_decode_gated": (c_int, [c_void_p, c_int64, c_int64, c_int64,
+                                         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                         c_int64, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]),
     "ptd_lowrank_skinny_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
     "ptd_lowrank_skinny": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
                                    c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int,

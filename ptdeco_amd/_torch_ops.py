@@ -8,6 +8,11 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
                                                              ops.lowrank_decode_group where ops.lowrank_decode_group_serves
                                                              (1 to 4 pairs on one x2d, T <= 16), else member by member
                                                              as lowrank_forward chooses
+    lowrank_forward_gated(Tensor x2d, Tensor Ag, Tensor Bg, Tensor? bias_g, Tensor Au, Tensor Bu, Tensor? bias_u, str act)
+        -> Tensor                                            act(g) * u of a gate and an up pair on one x2d:
+                                                             ops.lowrank_decode_gated where ops.lowrank_decode_gated_serves
+                                                             (T <= 16), else g and u as lowrank_forward_group forms them
+                                                             and torch's activation and product
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -84,6 +89,54 @@ def _(x2d, As, Bs, biases):
                      lambda: "lowrank_forward_group: every operand must be on x2d's device")
         torch._check(bias is None or tuple(bias.shape) == (B.shape[0],), lambda: "lowrank_forward_group: bias must be [n_o]")
     return x2d.new_empty((x2d.shape[0], sum(B.shape[0] for B in Bs)))
+
+
+# torch's own form of each activation ptd_lowrank_decode_gated knows (the names of ops.GATED_ACTS)
+GATE_ACTS = {"silu": torch.nn.functional.silu,
+             "gelu_tanh": lambda g: torch.nn.functional.gelu(g, approximate="tanh"),
+             "relu": torch.relu}
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_gated", mutates_args=())
+def lowrank_forward_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
+                          Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> torch.Tensor:
+    """act(g) * u for the gate pair (Ag [r_g, n_i], Bg [n_ff, r_g], bias_g) and the up pair (Au [r_u, n_i], Bu [n_ff, r_u],
+    bias_u) on x2d [T, n_i], act "silu", "gelu_tanh" or "relu": y [T, n_ff] contiguous.  At decode shapes two launches
+    (ops.lowrank_decode_gated_serves: ptd_lowrank_decode_gated); otherwise g and u as lowrank_forward_group forms them
+    and torch's own activation and product.  Inference only: no autograd formula."""
+    if act not in GATE_ACTS:
+        raise ValueError(f"act must be one of {sorted(GATE_ACTS)}, got {act!r}")
+    if ops.lowrank_decode_gated_serves(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
+        return ops.lowrank_decode_gated(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
+    As, Bs, biases = [Ag, Au], [Bg, Bu], [bias_g, bias_u]
+    if ops.lowrank_decode_group_serves(x2d, As, Bs, biases):
+        g, u = ops.lowrank_decode_group(x2d, As, Bs, biases).split([Bg.shape[0], Bu.shape[0]], 1)
+    else:
+        g, u = (_member(x2d, A, B, bias) for A, B, bias in zip(As, Bs, biases))
+    return (GATE_ACTS[act](g) * u).contiguous()
+
+
+def _member(x2d, A, B, bias):
+    if ops.lowrank_decode_serves(x2d, A, B, bias):
+        return ops.lowrank_decode(x2d, A, B, bias)
+    if ops.lowrank_skinny_serves(x2d, A, B, bias):
+        return ops.lowrank_skinny(x2d, A, B, bias)
+    return ops.lowrank_forward(x2d, A, B, bias)
+
+
+@lowrank_forward_gated.register_fake
+def _(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
+    torch._check(act in GATE_ACTS, lambda: f"lowrank_forward_gated: act must be one of {sorted(GATE_ACTS)}")
+    torch._check(x2d.dim() == 2, lambda: "lowrank_forward_gated: x2d must be 2-D")
+    for A, B, bias in ((Ag, Bg, bias_g), (Au, Bu, bias_u)):
+        torch._check(A.dim() == 2 and B.dim() == 2, lambda: "lowrank_forward_gated: 2-D operands")
+        torch._check(A.shape[1] == x2d.shape[1] and B.shape[1] == A.shape[0], lambda: "lowrank_forward_gated: shape mismatch")
+        torch._check(x2d.dtype == A.dtype == B.dtype, lambda: "lowrank_forward_gated: x2d, A and B must share a dtype")
+        torch._check(A.device == x2d.device and B.device == x2d.device and (bias is None or bias.device == x2d.device),
+                     lambda: "lowrank_forward_gated: every operand must be on x2d's device")
+        torch._check(bias is None or tuple(bias.shape) == (B.shape[0],), lambda: "lowrank_forward_gated: bias must be [n_ff]")
+    torch._check(Bg.shape[0] == Bu.shape[0], lambda: "lowrank_forward_gated: gate and up must have the same out_features")
+    return x2d.new_empty((x2d.shape[0], Bg.shape[0]))
 
 
 @torch.library.custom_op("ptdeco_amd::lowrank_forward_nchw", mutates_args=())

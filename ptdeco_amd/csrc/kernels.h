@@ -65,6 +65,17 @@ int lowrank_decode_group(const void* x, int64_t ldx, int64_t T, int64_t n_i, int
                          const int64_t* n_o, const void* const* bias, void* const* y, const int64_t* ldy, void* ws,
                          int dtype, hipStream_t st);
 
+// lowrank_gated.hip: act(gate x) * up x for two pairs on one input at decode shapes in two launches
+// (ptd_lowrank_decode_gated); g and u are lowrank_decode's bits for the members, rounded where act(g) * u rounds
+bool lowrank_decode_gated_serves(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int64_t n_o, int act, int dtype,
+                                 const void* x, int64_t ldx, const void* Ag, int64_t lda_g, const void* Bg, int64_t ldb_g,
+                                 const void* Au, int64_t lda_u, const void* Bu, int64_t ldb_u);
+size_t lowrank_decode_gated_workspace_bytes(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype);
+int lowrank_decode_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Ag, int64_t lda_g, int64_t r_g,
+                         const void* Bg, int64_t ldb_g, const void* bias_g, const void* Au, int64_t lda_u, int64_t r_u,
+                         const void* Bu, int64_t ldb_u, const void* bias_u, int64_t n_o, int act, void* y, int64_t ldy,
+                         void* ws, int dtype, hipStream_t st);
+
 // lowrank_skinny.hip: the pair at 32 <= T <= 96 tokens (bf16 / f16) as skinny products with a K split (ptd_lowrank_skinny)
 bool lowrank_skinny_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, const void* x, int64_t ldx,
                            const void* A, int64_t lda, const void* B, int64_t ldb);

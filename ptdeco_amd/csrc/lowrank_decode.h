@@ -219,6 +219,98 @@ __device__ __forceinline__ void decode_hb_body(const float* __restrict__ slabs, 
   }
 }
 
+// The pieces of decode_hb_body as functions of one member's (slabs, r, B) and of an LDS image, for a kernel that forms
+// the sums of TWO members per tile (lowrank_gated.hip).  Each is the lambda of the same name above, statement by
+// statement: the wave's k range from r, the 16-byte pieces of a weight row, the image of h[:, chunk] from the slabs in
+// slab order, the DEC_U matrix-core steps in step order.  A sum built from them has the bits decode_hb_body gives it.
+template <typename P>
+struct HbSide {
+  const float* slabs;
+  const typename P::elem* B;
+  const typename P::elem* bias;
+  int64_t ldb;
+  int nslabs, r;
+};
+
+template <typename P>
+__device__ __forceinline__ void hb_wave_range(const int r, const int chunk, const int wave, int& kbeg, int& kend) {
+  constexpr int KC = DEC_CHUNK_BYTES / (int)sizeof(typename P::elem);
+  const int c0 = chunk * KC, kcv = min(KC, r - c0);
+  const int kw = ((kcv + 3) / 4 + P::KSTEP - 1) / P::KSTEP * P::KSTEP;
+  kbeg = c0 + wave * kw;
+  kend = min(kbeg + kw, c0 + kcv);
+}
+
+// (no load under a branch: a piece outside the wave's range is fetched from the row's start, rows >= n_o read row 0)
+template <typename P, bool NT>
+__device__ __forceinline__ void hb_load_tile(typename P::frag (&w)[DEC_U], const HbSide<P>& m, const int n_o,
+                                             const int tile, const int chunk) {
+  typedef typename P::frag frag;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, kl = P::VEC * (lane >> 4);
+  int kbeg, kend;
+  hb_wave_range<P>(m.r, chunk, wave, kbeg, kend);
+  const int row = tile * 16 + (lane & 15);
+  const typename P::elem* wp = m.B + (int64_t)(row < n_o ? row : 0) * m.ldb;
+#pragma unroll
+  for (int u = 0; u < DEC_U; ++u) {
+    const int kk = kbeg + u * P::KSTEP + kl;
+    w[u] = load_weights<frag, NT>(reinterpret_cast<const frag*>(wp + (kk < kend ? kk : 0)));
+  }
+}
+
+// the image of h[:, chunk] in `himg` (16 rows of DEC_PITCH bytes): the slabs added in slab order, rounded once
+template <typename P>
+__device__ __forceinline__ void hb_stage(char* himg, const HbSide<P>& m, const int T, const int chunk) {
+  typedef typename P::elem elem;
+  constexpr int KC = DEC_CHUNK_BYTES / (int)sizeof(elem);
+  const int r = m.r, nslabs = m.nslabs;
+  const int c0 = chunk * KC, kcv = min(KC, r - c0);
+  const int per = kcv >> 2, items = T * per;      // four k per item
+  for (int i0 = 0; i0 < items; i0 += 4 * DEC_THREADS) {
+    f32x4 v[4][DEC_MAX_SLABS];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = min(i0 + q * DEC_THREADS + (int)threadIdx.x, items - 1);
+      const int t = i / per, k4 = (i - t * per) * 4;
+#pragma unroll
+      for (int s = 0; s < DEC_MAX_SLABS; ++s)
+        v[q][s] = *reinterpret_cast<const f32x4*>(m.slabs + ((int64_t)min(s, nslabs - 1) * T + t) * r + c0 + k4);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = i0 + q * DEC_THREADS + (int)threadIdx.x;
+      const int t = i / per, k4 = (i - t * per) * 4;
+      f32x4 sum = v[q][0];
+#pragma unroll
+      for (int s = 1; s < DEC_MAX_SLABS; ++s)
+        if (s < nslabs) sum += v[q][s];
+      if (i < items) P::put4(reinterpret_cast<elem*>(himg + t * DEC_PITCH) + k4, sum);
+    }
+  }
+}
+
+// acc += this wave's quarter of (tile, chunk): w from hb_load_tile, the token operand from the image
+template <typename P>
+__device__ __forceinline__ f32x4 hb_mma(f32x4 acc, const typename P::frag (&w)[DEC_U], const char* himg, const int r,
+                                        const int chunk, const int T) {
+  typedef typename P::frag frag;
+  typedef typename P::elem elem;
+  constexpr int KC = DEC_CHUNK_BYTES / (int)sizeof(elem);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, tok = lane & 15, kl = P::VEC * (lane >> 4);
+  const bool tok_ok = tok < T;
+  int kbeg, kend;
+  hb_wave_range<P>(r, chunk, wave, kbeg, kend);
+  const char* hp = himg + tok * DEC_PITCH;
+#pragma unroll
+  for (int u = 0; u < DEC_U; ++u) {
+    const int kk = kbeg + u * P::KSTEP + kl;
+    const bool ok = kk < kend;
+    const frag xv = *reinterpret_cast<const frag*>(hp + (ok ? kk - chunk * KC : 0) * (int)sizeof(elem));
+    acc = P::mma(w[u], ok && tok_ok ? xv : frag{}, acc);
+  }
+  return acc;
+}
+
 // K slabs of the first product and the K range of one: from (n_i, r) alone
 template <typename P>
 void xa_split(int64_t n_i, int64_t r, int& nslabs, int& kchunk) {

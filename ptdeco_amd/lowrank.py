@@ -19,11 +19,12 @@ import logging
 
 import torch
 
-from . import _torch_ops  # noqa: F401  (registers torch.ops.ptdeco_amd.*)
+from . import _torch_ops  # (registers torch.ops.ptdeco_amd.*)
 
 _lowrank_forward = torch.ops.ptdeco_amd.lowrank_forward.default
 _lowrank_forward_nchw = torch.ops.ptdeco_amd.lowrank_forward_nchw.default
 _lowrank_forward_group = torch.ops.ptdeco_amd.lowrank_forward_group.default
+_lowrank_forward_gated = torch.ops.ptdeco_amd.lowrank_forward_gated.default
 
 logger = logging.getLogger(__name__)
 
@@ -98,6 +99,34 @@ def lowrank_group(x: torch.Tensor, pairs) -> torch.Tensor:
     y = _lowrank_forward_group(x2d, [p[0].weight for p in pairs], [p[1].weight for p in pairs],
                                [p[1].bias for p in pairs])
     return y.reshape(*x.shape[:-1], y.shape[1])
+
+
+def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu") -> torch.Tensor:
+    """``act(gate(x)) * up(x)`` for the gate and up projections of a decomposed gated MLP (SwiGLU: "silu", GeGLU:
+    "gelu_tanh", ReGLU: "relu"): [..., out_features].  For installed ``LowRankLinear`` modules with equal in_features and
+    out_features at decode shapes (1 to 16 tokens) the whole expression runs in two kernel launches -- no [T, 2 n_ff]
+    intermediate, no elementwise launch --, gate's and up's values bit for bit what the modules return alone, rounded
+    where the expression rounds.  Inference only: when a gradient is wanted, or a member is not a ``LowRankLinear`` on
+    the HIP kernels' tensors, this is the expression itself.  It keeps no state."""
+    if act not in _torch_ops.GATE_ACTS:
+        raise ValueError(f"act must be one of {sorted(_torch_ops.GATE_ACTS)}, got {act!r}")
+    fused = all(isinstance(p, LowRankLinear) for p in (gate, up))
+    fused = fused and gate[0].in_features == up[0].in_features and gate[1].out_features == up[1].out_features
+    fused = fused and all(_use_hip(x, p[0].weight, "LowRankLinear") for p in (gate, up))
+    if fused and torch.is_grad_enabled():
+        fused = not (x.requires_grad or any(q.requires_grad for p in (gate, up) for q in p.parameters()))
+    if not fused:
+        return _torch_ops.GATE_ACTS[act](gate(x)) * up(x)
+    x2d = x.reshape(-1, gate[0].in_features)
+    y = _lowrank_forward_gated(x2d, gate[0].weight, gate[1].weight, gate[1].bias, up[0].weight, up[1].weight,
+                               up[1].bias, act)
+    return y.reshape(*x.shape[:-1], y.shape[1])
+
+
+def lowrank_mlp(x: torch.Tensor, gate, up, down, act: str = "silu") -> torch.Tensor:
+    """``down(act(gate(x)) * up(x))``, the MLP of a decomposed Llama / Mistral / Qwen block: ``lowrank_gated`` and then
+    ``down`` as it is called alone -- at decode shapes four kernel launches in all."""
+    return down(lowrank_gated(x, gate, up, act))
 
 
 def _is_plain_1x1(m: torch.nn.Module) -> bool:

@@ -474,6 +474,51 @@ def lowrank_decode_group(x2d: torch.Tensor, As: Sequence[torch.Tensor], Bs: Sequ
     return y
 
 
+# The gated pair of an MLP at decode shapes, act(gate(x)) * up(x), runs on ptd_lowrank_decode_gated: two launches, the
+# activation and the product in the lanes that hold both sums.  g and u are the bits lowrank_decode gives the members.
+GATED_ACTS = {"silu": 0, "gelu_tanh": 1, "relu": 2}      # PTD_ACT_*
+
+
+def lowrank_decode_gated_serves(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
+                                Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> bool:
+    """Whether ``lowrank_decode_gated`` takes these operands as they lie (the rule of ptd_lowrank_decode_gated, without
+    loading the library): a known activation, gate and up each served by ``lowrank_decode`` on the common x2d, and the
+    same number of output rows."""
+    if act not in GATED_ACTS:
+        return False
+    if not (lowrank_decode_serves(x2d, Ag, Bg, bias_g) and lowrank_decode_serves(x2d, Au, Bu, bias_u)):
+        return False
+    return Bg.shape[0] == Bu.shape[0]
+
+
+def lowrank_decode_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
+                         Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> torch.Tensor:
+    """act((x2d @ Ag^T) @ Bg^T + bias_g) * ((x2d @ Au^T) @ Bu^T + bias_u) for 1 <= T <= 16 rows of x2d, Ag [r_g, n_i],
+    Bg [n_ff, r_g], Au [r_u, n_i], Bu [n_ff, r_u], act one of ``GATED_ACTS``: ptd_lowrank_decode_gated, y [T, n_ff]
+    contiguous.  Operands the entry does not serve (``lowrank_decode_gated_serves``) raise."""
+    if act not in GATED_ACTS:
+        raise ValueError(f"act must be one of {sorted(GATED_ACTS)}, got {act!r}")
+    _dev(x2d, Ag, Bg, bias_g, Au, Bu, bias_u)
+    x2d, Ag, Bg, Au, Bu = (_rows2d(t) for t in (x2d, Ag, Bg, Au, Bu))
+    T, n_i = x2d.shape
+    r_g, r_u, n_ff = Ag.shape[0], Au.shape[0], Bg.shape[0]
+    assert Ag.shape[1] == n_i and Au.shape[1] == n_i and Bg.shape[1] == r_g and Bu.shape == (n_ff, r_u)
+    assert x2d.dtype == Ag.dtype == Bg.dtype == Au.dtype == Bu.dtype
+    y = torch.empty((T, n_ff), dtype=x2d.dtype, device=x2d.device)
+    lib = _hip.load()
+    ws_bytes = lib.ptd_lowrank_decode_gated_workspace_bytes(T, n_i, r_g, r_u, _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+    bias_g = None if bias_g is None else bias_g.to(x2d.dtype).contiguous()
+    bias_u = None if bias_u is None else bias_u.to(x2d.dtype).contiguous()
+    with torch.cuda.device(x2d.device):
+        rc = lib.ptd_lowrank_decode_gated(
+            x2d.data_ptr(), x2d.stride(0), T, n_i, Ag.data_ptr(), Ag.stride(0), r_g, Bg.data_ptr(), Bg.stride(0),
+            _ptr(bias_g), Au.data_ptr(), Au.stride(0), r_u, Bu.data_ptr(), Bu.stride(0), _ptr(bias_u), n_ff,
+            GATED_ACTS[act], y.data_ptr(), n_ff, ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
+    _hip.check(rc, "ptd_lowrank_decode_gated")
+    return y
+
+
 # The pair at small batches (32 <= T <= _SKINNY_MAX_T tokens, bf16 / f16) runs on ptd_lowrank_skinny: skinny products
 # with a K split that depends on the layer alone.  PTD_LOWRANK_SKINNY=0 sends these shapes through lowrank_forward again.
 # (T = 17 ... 31 stays on the tile path: lowering _SKINNY_MIN_T is all a later change needs here.  The cap is measured,
