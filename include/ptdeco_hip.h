@@ -41,7 +41,8 @@ extern "C" {
                              *    ptd_lowrank_skinny_workspace_bytes, ptd_lowrank_skinny,
                              *    ptd_launch_trace_begin, ptd_launch_trace_end,
                              *    ptd_lowrank_decode_group_workspace_bytes, ptd_lowrank_decode_group,
-                             *    ptd_lowrank_decode_gated_workspace_bytes, ptd_lowrank_decode_gated) */
+                             *    ptd_lowrank_decode_gated_workspace_bytes, ptd_lowrank_decode_gated,
+                             *    ptd_lowrank_skinny_gated_workspace_bytes, ptd_lowrank_skinny_gated) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -388,6 +389,24 @@ size_t ptd_lowrank_skinny_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int
 int ptd_lowrank_skinny(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r,
                        const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy,
                        void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* The gated pair of a decomposed MLP at the same 32 <= T <= 96 tokens in bf16 / f16, y = act(gate(x)) * up(x) (arguments
+ * and activations as ptd_lowrank_decode_gated), in three launches on the caller's stream: both first products, both
+ * slab sums, then a kernel that forms both second products for the same 32 rows and 64 tokens and applies the activation
+ * and the product in the lanes that hold both sums -- no [T, 2 n_ff] intermediate and no elementwise launch.  g and u
+ * are the bits ptd_lowrank_skinny stores for gate and up (each member keeps its own K split, wave ranges and orders of
+ * addition, so row t of y depends on row t of x alone); the activation is evaluated in f32 on g and rounded once, its
+ * product with u is formed in f32 and rounded once -- the rounding points of the unfused act(g) * u.  Served when both
+ * members are served by ptd_lowrank_skinny with the common x, T, n_i, n_ff and dtype and act is one of PTD_ACT_*;
+ * anything else, f32 included, returns PTD_ERR_UNSUPPORTED before a kernel is launched.  Null pointers (either bias may
+ * be NULL), a leading dimension below its row length or a misaligned workspace PTD_ERR_INVALID; a short workspace
+ * PTD_ERR_WORKSPACE.  The workspace is the sum of the two members' ptd_lowrank_skinny workspaces. */
+size_t ptd_lowrank_skinny_gated_workspace_bytes(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype);
+int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                             const void* Ag, int64_t lda_g, int64_t r_g, const void* Bg, int64_t ldb_g, const void* bias_g,
+                             const void* Au, int64_t lda_u, int64_t r_u, const void* Bu, int64_t ldb_u, const void* bias_u,
+                             int64_t n_ff, int act, void* y, int64_t ldy,
+                             void* ws, size_t ws_bytes, int dtype, void* stream);
 
 /* The same pair for a 1x1-convolution input in NCHW layout, without the NHWC copy the reference makes
  * (`permute(0,2,3,1).reshape(-1,C)`, dwain.py:116; falor.py:126): per image b, x_b = x + b*n_i*hw is an

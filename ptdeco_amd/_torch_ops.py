@@ -11,8 +11,10 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
     lowrank_forward_gated(Tensor x2d, Tensor Ag, Tensor Bg, Tensor? bias_g, Tensor Au, Tensor Bu, Tensor? bias_u, str act)
         -> Tensor                                            act(g) * u of a gate and an up pair on one x2d:
                                                              ops.lowrank_decode_gated where ops.lowrank_decode_gated_serves
-                                                             (T <= 16), else g and u as lowrank_forward_group forms them
-                                                             and torch's activation and product
+                                                             (T <= 16), ops.lowrank_skinny_gated where
+                                                             ops.lowrank_skinny_gated_serves (32 ... 96), else g and u
+                                                             as lowrank_forward_group forms them and torch's
+                                                             activation and product
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -102,12 +104,15 @@ def lowrank_forward_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor,
                           Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> torch.Tensor:
     """act(g) * u for the gate pair (Ag [r_g, n_i], Bg [n_ff, r_g], bias_g) and the up pair (Au [r_u, n_i], Bu [n_ff, r_u],
     bias_u) on x2d [T, n_i], act "silu", "gelu_tanh" or "relu": y [T, n_ff] contiguous.  At decode shapes two launches
-    (ops.lowrank_decode_gated_serves: ptd_lowrank_decode_gated); otherwise g and u as lowrank_forward_group forms them
+    (ops.lowrank_decode_gated_serves: ptd_lowrank_decode_gated), at small batches three (32 <= T <= 96, bf16 / f16:
+    ops.lowrank_skinny_gated_serves, ptd_lowrank_skinny_gated); otherwise g and u as lowrank_forward_group forms them
     and torch's own activation and product.  Inference only: no autograd formula."""
     if act not in GATE_ACTS:
         raise ValueError(f"act must be one of {sorted(GATE_ACTS)}, got {act!r}")
     if ops.lowrank_decode_gated_serves(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
         return ops.lowrank_decode_gated(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
+    if ops.lowrank_skinny_gated_serves(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
+        return ops.lowrank_skinny_gated(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
     As, Bs, biases = [Ag, Au], [Bg, Bu], [bias_g, bias_u]
     if ops.lowrank_decode_group_serves(x2d, As, Bs, biases):
         g, u = ops.lowrank_decode_group(x2d, As, Bs, biases).split([Bg.shape[0], Bu.shape[0]], 1)

@@ -603,6 +603,37 @@ int ptd_lowrank_skinny(const void* x, int64_t ldx, int64_t T, int64_t n_i, const
   return lowrank_skinny(x, ldx, T, n_i, A, lda, r, B, ldb, n_o, bias, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
 }
 
+size_t ptd_lowrank_skinny_gated_workspace_bytes(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype) {
+  return lowrank_skinny_gated_workspace_bytes(T, n_i, r_g, r_u, dtype);
+}
+
+int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Ag, int64_t lda_g,
+                             int64_t r_g, const void* Bg, int64_t ldb_g, const void* bias_g, const void* Au,
+                             int64_t lda_u, int64_t r_u, const void* Bu, int64_t ldb_u, const void* bias_u, int64_t n_ff,
+                             int act, void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, void* stream) {
+  PTD_REQUIRE(x && Ag && Bg && Au && Bu && y && ws, "ptd_lowrank_skinny_gated: null pointer");
+  PTD_REQUIRE(ldx >= n_i && lda_g >= n_i && lda_u >= n_i && ldb_g >= r_g && ldb_u >= r_u && ldy >= n_ff,
+              "ptd_lowrank_skinny_gated: bad leading dimension");
+  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16 || dtype == PTD_F16,
+              "ptd_lowrank_skinny_gated: dtype must be f32, bf16 or f16");
+  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_skinny_gated: the workspace must be 16-byte aligned");
+  // (nothing is launched for what the kernels do not serve: the caller forms g and u and applies the activation itself)
+  if (!lowrank_skinny_gated_serves(T, n_i, r_g, r_u, n_ff, act, dtype, x, ldx, Ag, lda_g, Bg, ldb_g, Au, lda_u, Bu, ldb_u)) {
+    set_error("ptd_lowrank_skinny_gated: not served (T=%lld n_i=%lld r_g=%lld r_u=%lld n_ff=%lld act=%d dtype=%d: "
+              "bf16 or f16, 32 <= T <= 96, both r >= 8, n_i and both r multiples of 8, 16-byte aligned rows, act 0 (silu), "
+              "1 (gelu_tanh) or 2 (relu))", (long long)T, (long long)n_i, (long long)r_g, (long long)r_u,
+              (long long)n_ff, act, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  const size_t need = lowrank_skinny_gated_workspace_bytes(T, n_i, r_g, r_u, dtype);
+  if (ws_bytes < need) {
+    set_error("ptd_lowrank_skinny_gated: workspace %zu < required %zu bytes", ws_bytes, need);
+    return PTD_ERR_WORKSPACE;
+  }
+  return lowrank_skinny_gated(x, ldx, T, n_i, Ag, lda_g, r_g, Bg, ldb_g, bias_g, Au, lda_u, r_u, Bu, ldb_u, bias_u, n_ff,
+                              act, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
+}
+
 size_t ptd_lowrank_forward_nchw_workspace_bytes(int64_t batch, int64_t hw, int64_t r, int dtype) {
   return align_up((size_t)batch * (size_t)r * (size_t)hw * elt_bytes(dtype), 256);
 }

@@ -83,6 +83,17 @@ size_t lowrank_skinny_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dty
 int lowrank_skinny(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r, const void* B,
                    int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_skinny_gated.hip: act(gate x) * up x at 32 <= T <= 96 tokens (bf16 / f16) in three launches
+// (ptd_lowrank_skinny_gated); g and u are lowrank_skinny's bits for the members, rounded where act(g) * u rounds
+bool lowrank_skinny_gated_serves(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int64_t n_o, int act, int dtype,
+                                 const void* x, int64_t ldx, const void* Ag, int64_t lda_g, const void* Bg, int64_t ldb_g,
+                                 const void* Au, int64_t lda_u, const void* Bu, int64_t ldb_u);
+size_t lowrank_skinny_gated_workspace_bytes(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype);
+int lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Ag, int64_t lda_g, int64_t r_g,
+                         const void* Bg, int64_t ldb_g, const void* bias_g, const void* Au, int64_t lda_u, int64_t r_u,
+                         const void* Bu, int64_t ldb_u, const void* bias_u, int64_t n_o, int act, void* y, int64_t ldy,
+                         void* ws, int dtype, hipStream_t st);
+
 // eigh_jacobi.hip
 size_t eigh_workspace_bytes(int64_t n);
 int eigh_jacobi(const double* A, int64_t lda, int64_t n, int64_t k, double* evals, double* evecs, int64_t ldv,

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "elem16.h"
 #include "kernels.h"
+#include "lowrank_act.h"
 #include "lowrank_decode.h"
 
 namespace ptd {
@@ -41,13 +42,6 @@ __global__ __launch_bounds__(DEC_THREADS) void gated_xa_kernel(const typename P:
   const unsigned local = blockIdx.x - (is_up ? first_up : 0);
   const unsigned by = local / (unsigned)m.row_tiles, bx = local - by * (unsigned)m.row_tiles;
   decode_xa_body<P, NT>(x, ldx, T, n_i, static_cast<const elem*>(m.A), m.lda, m.r, m.slabs, m.kchunk, bx, by);
-}
-
-template <int ACT>
-__device__ __forceinline__ float gate_act(const float v) {
-  if (ACT == PTD_ACT_SILU) return v / (1.f + expf(-v));
-  if (ACT == PTD_ACT_GELU_TANH) return 0.5f * v * (1.f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v)));
-  return v < 0.f ? 0.f : v;      // (a NaN stays a NaN, as in torch.relu)
 }
 
 // LDS of gated_hb_kernel, all of it dynamic (nothing static in front: the base stays 16-byte aligned): the two images of

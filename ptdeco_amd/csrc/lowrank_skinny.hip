@@ -31,30 +31,14 @@
 // Rounding points are the tile path's: f32 sums, h rounded once to the operand type (IEEE conversion for f16), the bias
 // added in f32, y rounded once.  No load sits under a branch: a piece outside the K range, the matrix or the token
 // count is fetched from an address that exists and replaced by zeros in registers.
-#include <algorithm>
-
 #include "common.h"
 #include "elem16.h"
 #include "kernels.h"
+#include "lowrank_skinny.h"
 
 namespace ptd {
 
 namespace {
-
-constexpr int SK_MIN_T = 32;
-constexpr int SK_MAX_T = 96;            // measured (profiles/pair_skinny.json): beyond it the tile path wins a bf16 cell
-constexpr int SK_THREADS = 256;        // four waves
-constexpr int SK_ROWS = 32;            // weight rows of a workgroup: two MFMA row fragments per wave
-constexpr int SK_TOK = 64;             // tokens of a workgroup: four MFMA column tiles
-constexpr int SK_KW = 64;              // k of one step of a wave: a 128-byte line, two MFMA k steps
-constexpr int SK_QUANTUM = 4 * SK_KW;  // K ranges are whole steps of four waves
-constexpr int SK_PITCH = SK_QUANTUM * 2 + 16;   // bytes of a token's row in the image: 33 x 16 B, 16 tokens on 16 slots
-constexpr int SK_MAX_SLABS = 8;
-constexpr int SK_XA_TARGET = 256;      // workgroups per token tile the first product aims for
-constexpr int SK_LDS_BYTES = SK_TOK * SK_PITCH;             // 33,792: the image, then the wave sums (32,768)
-constexpr int SK_PIECES = SK_TOK * 4 * (SK_KW / 8) / SK_THREADS;   // 16-byte token pieces per thread and step: 8
-
-typedef unsigned short elem;
 
 // out[t, i] over the K range of blockIdx.y for rows 32 blockIdx.x + 0..31 and tokens 64 blockIdx.z + 0..63.
 // SLAB: f32 sums to out_f32[(blockIdx.y T + t) R + i]; otherwise round(sum + bias[i]) to y[t ldy + i].
@@ -199,17 +183,6 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_combine_kernel(const float*
     *reinterpret_cast<uint2*>(h + i * 4) = p;
   }
 }
-
-// K slabs of the first product and the K range of one: from (n_i, r) alone
-void xa_split(int64_t n_i, int64_t r, int& nslabs, int& kchunk) {
-  const int64_t row_tiles = ceil_div(r, SK_ROWS);
-  const int64_t s = std::min<int64_t>(SK_MAX_SLABS, std::max<int64_t>(1, ceil_div(SK_XA_TARGET, row_tiles)));
-  const int64_t kc = (int64_t)align_up((size_t)ceil_div(n_i, s), (size_t)SK_QUANTUM);
-  kchunk = (int)kc;
-  nslabs = (int)ceil_div(n_i, kc);
-}
-
-size_t slab_bytes(int64_t T, int64_t r) { return align_up((size_t)SK_MAX_SLABS * (size_t)T * (size_t)r * sizeof(float), 256); }
 
 template <typename EL>
 int launch_skinny(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r, const void* B,

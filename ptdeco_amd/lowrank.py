@@ -104,9 +104,9 @@ def lowrank_group(x: torch.Tensor, pairs) -> torch.Tensor:
 def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu") -> torch.Tensor:
     """``act(gate(x)) * up(x)`` for the gate and up projections of a decomposed gated MLP (SwiGLU: "silu", GeGLU:
     "gelu_tanh", ReGLU: "relu"): [..., out_features].  For installed ``LowRankLinear`` modules with equal in_features and
-    out_features at decode shapes (1 to 16 tokens) the whole expression runs in two kernel launches -- no [T, 2 n_ff]
-    intermediate, no elementwise launch --, gate's and up's values bit for bit what the modules return alone, rounded
-    where the expression rounds.  Inference only: when a gradient is wanted, or a member is not a ``LowRankLinear`` on
+    out_features at decode shapes (1 to 16 tokens) the whole expression runs in two kernel launches, at small batches
+    (32 to 96 tokens, bf16) in three -- no [T, 2 n_ff] intermediate, no elementwise launch --, gate's and up's values
+    bit for bit what the modules return alone, rounded where the expression rounds.  Inference only: when a gradient is wanted, or a member is not a ``LowRankLinear`` on
     the HIP kernels' tensors, this is the expression itself.  It keeps no state."""
     if act not in _torch_ops.GATE_ACTS:
         raise ValueError(f"act must be one of {sorted(_torch_ops.GATE_ACTS)}, got {act!r}")
@@ -125,7 +125,7 @@ def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu") -> torch.Tensor:
 
 def lowrank_mlp(x: torch.Tensor, gate, up, down, act: str = "silu") -> torch.Tensor:
     """``down(act(gate(x)) * up(x))``, the MLP of a decomposed Llama / Mistral / Qwen block: ``lowrank_gated`` and then
-    ``down`` as it is called alone -- at decode shapes four kernel launches in all."""
+    ``down`` as it is called alone -- at decode shapes four kernel launches in all, at 32 to 96 tokens six."""
     return down(lowrank_gated(x, gate, up, act))
 
 

@@ -579,6 +579,52 @@ def lowrank_skinny(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Op
     return y
 
 
+# The gated pair of an MLP at small batches, act(gate(x)) * up(x), runs on ptd_lowrank_skinny_gated: three launches (both
+# first products, both slab sums, both second products with the activation and the product in the lanes that hold both
+# sums).  g and u are the bits lowrank_skinny gives the members.  No switch or constant of its own: the rule is
+# lowrank_skinny_serves of both members.  (profiles/pair_skinny_gated.json: every measured class of cells is won, so
+# the rule excludes no shape the C entry serves.)
+def lowrank_skinny_gated_serves(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
+                                Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> bool:
+    """Whether ``lowrank_skinny_gated`` takes these operands as they lie (the rule of ptd_lowrank_skinny_gated, without
+    loading the library): a known activation, gate and up each served by ``lowrank_skinny`` on the common x2d, and the
+    same number of output rows."""
+    if act not in GATED_ACTS:
+        return False
+    if not (lowrank_skinny_serves(x2d, Ag, Bg, bias_g) and lowrank_skinny_serves(x2d, Au, Bu, bias_u)):
+        return False
+    return Bg.shape[0] == Bu.shape[0]
+
+
+def lowrank_skinny_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
+                         Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> torch.Tensor:
+    """act((x2d @ Ag^T) @ Bg^T + bias_g) * ((x2d @ Au^T) @ Bu^T + bias_u) for 32 <= T <= _SKINNY_MAX_T rows of x2d,
+    Ag [r_g, n_i], Bg [n_ff, r_g], Au [r_u, n_i], Bu [n_ff, r_u], bf16 / f16, act one of ``GATED_ACTS``:
+    ptd_lowrank_skinny_gated, y [T, n_ff] contiguous.  Operands the entry does not serve
+    (``lowrank_skinny_gated_serves``) raise; row t of the result depends on row t of x2d alone."""
+    if act not in GATED_ACTS:
+        raise ValueError(f"act must be one of {sorted(GATED_ACTS)}, got {act!r}")
+    _dev(x2d, Ag, Bg, bias_g, Au, Bu, bias_u)
+    x2d, Ag, Bg, Au, Bu = (_rows2d(t) for t in (x2d, Ag, Bg, Au, Bu))
+    T, n_i = x2d.shape
+    r_g, r_u, n_ff = Ag.shape[0], Au.shape[0], Bg.shape[0]
+    assert Ag.shape[1] == n_i and Au.shape[1] == n_i and Bg.shape[1] == r_g and Bu.shape == (n_ff, r_u)
+    assert x2d.dtype == Ag.dtype == Bg.dtype == Au.dtype == Bu.dtype
+    y = torch.empty((T, n_ff), dtype=x2d.dtype, device=x2d.device)
+    lib = _hip.load()
+    ws_bytes = lib.ptd_lowrank_skinny_gated_workspace_bytes(T, n_i, r_g, r_u, _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+    bias_g = None if bias_g is None else bias_g.to(x2d.dtype).contiguous()
+    bias_u = None if bias_u is None else bias_u.to(x2d.dtype).contiguous()
+    with torch.cuda.device(x2d.device):
+        rc = lib.ptd_lowrank_skinny_gated(
+            x2d.data_ptr(), x2d.stride(0), T, n_i, Ag.data_ptr(), Ag.stride(0), r_g, Bg.data_ptr(), Bg.stride(0),
+            _ptr(bias_g), Au.data_ptr(), Au.stride(0), r_u, Bu.data_ptr(), Bu.stride(0), _ptr(bias_u), n_ff,
+            GATED_ACTS[act], y.data_ptr(), n_ff, ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
+    _hip.check(rc, "ptd_lowrank_skinny_gated")
+    return y
+
+
 def lowrank_forward_nchw(x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
     """The rank-r 1x1-convolution pair on a contiguous NCHW input, no layout copy: per image
     y_b = B (A x_b) + bias[:, None] with x_b viewed [n_i, H W]; y is contiguous NCHW."""
