@@ -42,7 +42,8 @@ extern "C" {
                              *    ptd_launch_trace_begin, ptd_launch_trace_end,
                              *    ptd_lowrank_decode_group_workspace_bytes, ptd_lowrank_decode_group,
                              *    ptd_lowrank_decode_gated_workspace_bytes, ptd_lowrank_decode_gated,
-                             *    ptd_lowrank_skinny_gated_workspace_bytes, ptd_lowrank_skinny_gated) */
+                             *    ptd_lowrank_skinny_gated_workspace_bytes, ptd_lowrank_skinny_gated,
+                             *    ptd_lowrank_decode_w8_workspace_bytes, ptd_lowrank_decode_w8) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -335,6 +336,26 @@ size_t ptd_lowrank_decode_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int
 int ptd_lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r,
                        const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy,
                        void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* The pair at 1 <= T <= 16 tokens with 8-bit factors (weight-only quantisation: 8-bit weights, 16-bit activations):
+ * x [T, n_i], bias [n_o] and y [T, n_o] in dtype D = bf16 or f16, Aq [r, n_i] and Bq [n_o, r] in OCP e4m3fn (one byte
+ * per weight, lda / ldb in bytes = elements), scale_a [r] and scale_b [n_o] in f32, one scale per factor row:
+ *   h[t, i] = round_D(scale_a[i] * sum_k x[t, k] Aq[i, k]),   y[t, o] = round_D(scale_b[o] * sum_i h[t, i] Bq[o, i] + bias[o])
+ * with the sums in f32, each rounded ONCE.  Two weight-streaming kernels on the caller's stream, as ptd_lowrank_decode:
+ * every weight byte is read once and converted to D in registers (exactly: every e4m3 value is a bf16 and an f16
+ * value), no dequantised copy is kept, and row t of y depends on row t of x alone, bit for bit, whatever T is.
+ * w_format: PTD_W8_FP8_E4M3.  Served: dtype bf16 / f16, 1 <= T <= 16, r >= 16, n_i and r multiples of 16, lda and ldb
+ * multiples of 16, ldx a multiple of 8, x, Aq and Bq 16-byte aligned, the scales 4-byte aligned, any n_o >= 1, bias
+ * optional.  Anything else (f32, another w_format) returns PTD_ERR_UNSUPPORTED before a kernel is launched; null
+ * pointers, a leading dimension below its row length or a misaligned workspace PTD_ERR_INVALID; a short workspace
+ * PTD_ERR_WORKSPACE.  The workspace holds the f32 partial sums of the first product's K split, added in a fixed order.
+ * No reference counterpart. */
+#define PTD_W8_FP8_E4M3 0
+size_t ptd_lowrank_decode_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int ptd_lowrank_decode_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                          const void* Aq, int64_t lda, const float* scale_a, int64_t r,
+                          const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o, const void* bias,
+                          void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 
 /* 1 <= count <= PTD_LOWRANK_GROUP_MAX pairs that read the same x at decode shapes (the q / k / v or gate / up projections
  * of a decomposed transformer block) in two launches on the caller's stream instead of two per pair.  Member m has its

@@ -15,6 +15,10 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
                                                              ops.lowrank_skinny_gated_serves (32 ... 96), else g and u
                                                              as lowrank_forward_group forms them and torch's
                                                              activation and product
+    lowrank_forward_w8(Tensor x2d, Tensor Aq, Tensor sa, Tensor Bq, Tensor sb, Tensor? bias) -> Tensor
+                                                             the pair with fp8 (e4m3fn) factors and f32 row scales:
+                                                             ops.lowrank_decode_w8 where ops.lowrank_decode_w8_serves
+                                                             (T <= 16), else the torch expression on 16-bit copies
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -142,6 +146,45 @@ def _(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
         torch._check(bias is None or tuple(bias.shape) == (B.shape[0],), lambda: "lowrank_forward_gated: bias must be [n_ff]")
     torch._check(Bg.shape[0] == Bu.shape[0], lambda: "lowrank_forward_gated: gate and up must have the same out_features")
     return x2d.new_empty((x2d.shape[0], Bg.shape[0]))
+
+
+def lowrank_w8_expression(x: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                          bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The semantics of the fp8 pair in torch, D = x.dtype: h = round_D(sa * (x Aq^T)), y = round_D(sb * (h Bq^T) + bias),
+    on transient copies of the factors in D (exact: every e4m3 value is a bf16 and an f16 value).  ``F.linear`` rounds
+    its f32 sums to D before the scale is applied, so this expression rounds once more per product than the kernels."""
+    linear = torch.nn.functional.linear
+    h = (linear(x, Aq.to(x.dtype)).float() * sa).to(x.dtype)
+    y = linear(h, Bq.to(x.dtype)).float() * sb
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(x.dtype)
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_w8", mutates_args=())
+def lowrank_forward_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                       bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The pair with 8-bit factors: x2d [T, n_i] bf16 / f16, Aq [r, n_i] and Bq [n_o, r] float8_e4m3fn, sa [r] and sb
+    [n_o] f32 scales per factor row, bias [n_o] of x2d's dtype or None; y [T, n_o] contiguous,
+    y = round(sb * (h Bq^T) + bias) with h = round(sa * (x2d Aq^T)).  At decode shapes (1 <= T <= 16, aligned operands:
+    ops.lowrank_decode_w8_serves) on the weight-streaming kernels of ptd_lowrank_decode_w8, which keep the sums in f32
+    and round h and y once each.  Elsewhere ``lowrank_w8_expression``: torch's products on transient 16-bit copies of
+    the factors, which round once more than the kernels do, inside ``F.linear``.  Inference only: no autograd formula."""
+    if ops.lowrank_decode_w8_serves(x2d, Aq, sa, Bq, sb, bias):
+        return ops.lowrank_decode_w8(x2d, Aq, sa, Bq, sb, bias)
+    return lowrank_w8_expression(x2d, Aq, sa, Bq, sb, bias).contiguous()
+
+
+@lowrank_forward_w8.register_fake
+def _(x2d, Aq, sa, Bq, sb, bias):
+    torch._check(x2d.dim() == 2 and Aq.dim() == 2 and Bq.dim() == 2, lambda: "lowrank_forward_w8: 2-D operands")
+    torch._check(Aq.shape[1] == x2d.shape[1] and Bq.shape[1] == Aq.shape[0], lambda: "lowrank_forward_w8: shape mismatch")
+    torch._check(tuple(sa.shape) == (Aq.shape[0],) and tuple(sb.shape) == (Bq.shape[0],),
+                 lambda: "lowrank_forward_w8: one scale per factor row")
+    torch._check(Aq.dtype == torch.float8_e4m3fn and Bq.dtype == torch.float8_e4m3fn,
+                 lambda: "lowrank_forward_w8: the factors must be float8_e4m3fn")
+    torch._check(bias is None or tuple(bias.shape) == (Bq.shape[0],), lambda: "lowrank_forward_w8: bias must be [n_o]")
+    return x2d.new_empty((x2d.shape[0], Bq.shape[0]))
 
 
 @torch.library.custom_op("ptdeco_amd::lowrank_forward_nchw", mutates_args=())

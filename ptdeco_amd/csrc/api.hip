@@ -507,6 +507,33 @@ int ptd_lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const
   return lowrank_decode(x, ldx, T, n_i, A, lda, r, B, ldb, n_o, bias, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
 }
 
+size_t ptd_lowrank_decode_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
+  return lowrank_decode_w8_workspace_bytes(T, n_i, r, dtype);
+}
+
+int ptd_lowrank_decode_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                          const float* scale_a, int64_t r, const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o,
+                          const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format,
+                          void* stream) {
+  PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "ptd_lowrank_decode_w8: null pointer");
+  PTD_REQUIRE(ldx >= n_i && lda >= n_i && ldb >= r && ldy >= n_o, "ptd_lowrank_decode_w8: bad leading dimension");
+  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_decode_w8: the workspace must be 16-byte aligned");
+  // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
+  if (!lowrank_decode_w8_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, scale_a, Bq, ldb, scale_b, bias)) {
+    set_error("ptd_lowrank_decode_w8: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d w_format=%d: bf16 / f16, "
+              "PTD_W8_FP8_E4M3, 1 <= T <= 16, r >= 16, n_i and r multiples of 16, 16-byte aligned rows)", (long long)T,
+              (long long)n_i, (long long)r, (long long)n_o, dtype, w_format);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  if (ws_bytes < lowrank_decode_w8_workspace_bytes(T, n_i, r, dtype)) {
+    set_error("ptd_lowrank_decode_w8: workspace %zu < required %zu bytes", ws_bytes,
+              lowrank_decode_w8_workspace_bytes(T, n_i, r, dtype));
+    return PTD_ERR_WORKSPACE;
+  }
+  return lowrank_decode_w8(x, ldx, T, n_i, Aq, lda, scale_a, r, Bq, ldb, scale_b, n_o, bias, y, ldy, ws, dtype,
+                           static_cast<hipStream_t>(stream));
+}
+
 size_t ptd_lowrank_decode_group_workspace_bytes(int count, int64_t T, int64_t n_i, const int64_t* r, int dtype) {
   if (!r || count < 1 || count > PTD_LOWRANK_GROUP_MAX) return 0;
   return lowrank_decode_group_workspace_bytes(count, T, n_i, r, dtype);

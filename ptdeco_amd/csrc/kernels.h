@@ -54,6 +54,16 @@ size_t lowrank_decode_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dty
 int lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r, const void* B,
                    int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_decode_w8.hip: the same pair with fp8 (e4m3fn) factors and one f32 scale per factor row, bf16 / f16 activations
+// (ptd_lowrank_decode_w8): weights converted in registers, scales applied in f32 where the sums are complete
+bool lowrank_decode_w8_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
+                              int64_t ldx, const void* Aq, int64_t lda, const float* sa, const void* Bq, int64_t ldb,
+                              const float* sb, const void* bias);
+size_t lowrank_decode_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int lowrank_decode_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const float* sa,
+                      int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
+                      int64_t ldy, void* ws, int dtype, hipStream_t st);
+
 // lowrank_group.hip: 1 .. PTD_LOWRANK_GROUP_MAX pairs on one input at decode shapes in two launches (ptd_lowrank_decode_group);
 // every member's bits are lowrank_decode's on that member alone
 bool lowrank_decode_group_serves(int count, int64_t T, int64_t n_i, const int64_t* r, const int64_t* n_o, int dtype,

@@ -25,6 +25,7 @@ _lowrank_forward = torch.ops.ptdeco_amd.lowrank_forward.default
 _lowrank_forward_nchw = torch.ops.ptdeco_amd.lowrank_forward_nchw.default
 _lowrank_forward_group = torch.ops.ptdeco_amd.lowrank_forward_group.default
 _lowrank_forward_gated = torch.ops.ptdeco_amd.lowrank_forward_gated.default
+_lowrank_forward_w8 = torch.ops.ptdeco_amd.lowrank_forward_w8.default
 
 logger = logging.getLogger(__name__)
 
@@ -77,6 +78,139 @@ class LowRankConv1x1(torch.nn.Sequential):
         rows = x.permute(0, 2, 3, 1).reshape(-1, c)  # NHWC rows: a view for channels_last inputs
         y = _lowrank_forward(rows, wa, wb, bias)
         return y.reshape(b, h, w, second.out_channels).permute(0, 3, 1, 2)
+
+
+_W8_DTYPES = (torch.bfloat16, torch.float16)
+_W8_FORMATS = {"fp8_e4m3": (torch.float8_e4m3fn, 448.0)}
+_W8_FIXED = ("weight_a_q", "scale_a", "weight_b_q", "scale_b")
+
+
+class LowRankLinearW8(torch.nn.Module):
+    """A rank-r pair with 8-bit factors (weight-only quantisation): ``weight_a_q`` [rank, in_features] and ``weight_b_q``
+    [out_features, rank] in float8_e4m3fn, one f32 scale per factor row (``scale_a`` [rank], ``scale_b`` [out_features])
+    and ``bias`` [out_features] in the activation dtype (bf16 or f16) or None -- all buffers: the module is
+    inference-only and has no trainable parameters.  With D the activation dtype,
+
+        h = round_D(scale_a * (x weight_a_q^T))        y = round_D(scale_b * (h weight_b_q^T) + bias)
+
+    On a ROCm device, for x of the module's dtype and no gradient wanted, ``forward`` calls
+    ``torch.ops.ptdeco_amd.lowrank_forward_w8``: at 1 to 16 tokens the HIP kernels of ptd_lowrank_decode_w8 (half the
+    factor bytes of the 16-bit pair, converted in registers), at more tokens the torch expression on transient 16-bit
+    copies of the factors.  Anything else (a CPU copy, another input dtype, ``x.requires_grad``) evaluates that
+    expression directly and says so once, at WARNING.  ``.to(device)`` moves the module; a dtype cast (``.half()``,
+    ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the quantised factors and their
+    scales as they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place``, or empty for ``load_state_dict``."""
+
+    def __init__(self, in_features: int, rank: int, out_features: int, bias: bool = True,
+                 dtype: torch.dtype = torch.bfloat16, device=None) -> None:
+        super().__init__()
+        if dtype not in _W8_DTYPES:
+            raise ValueError(f"LowRankLinearW8: the activation dtype must be bfloat16 or float16, got {dtype}")
+        self.in_features, self.rank, self.out_features = int(in_features), int(rank), int(out_features)
+        self._dtype = dtype
+        self.register_buffer("weight_a_q", torch.zeros((rank, in_features), dtype=torch.float8_e4m3fn, device=device))
+        self.register_buffer("scale_a", torch.ones(rank, dtype=torch.float32, device=device))
+        self.register_buffer("weight_b_q", torch.zeros((out_features, rank), dtype=torch.float8_e4m3fn, device=device))
+        self.register_buffer("scale_b", torch.ones(out_features, dtype=torch.float32, device=device))
+        self.register_buffer("bias", torch.zeros(out_features, dtype=dtype, device=device) if bias else None)
+
+    @property
+    def dtype(self) -> torch.dtype:
+        """The activation dtype D: what x must be for the HIP kernels, and what the bias is held in."""
+        return self._dtype
+
+    def _apply(self, fn, *args, **kwargs):
+        fixed = {name: self._buffers[name] for name in _W8_FIXED}
+        super()._apply(fn, *args, **kwargs)
+        for name, old in fixed.items():      # (a dtype cast must not touch the quantised factors or round their scales)
+            new = self._buffers[name]
+            if new.dtype != old.dtype:
+                self._buffers[name] = old.to(new.device)
+        cast = fn(torch.empty(0, dtype=self._dtype)).dtype
+        if cast in _W8_DTYPES:
+            self._dtype = cast
+        if self.bias is not None and self.bias.dtype != self._dtype:
+            self._buffers["bias"] = self.bias.to(self._dtype)
+        return self
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, rank={self.rank}, out_features={self.out_features}, "
+                f"bias={self.bias is not None}, dtype={self._dtype}")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        operands = (self.weight_a_q, self.scale_a, self.weight_b_q, self.scale_b, self.bias)
+        wants_grad = torch.is_grad_enabled() and x.requires_grad
+        if not (x.is_cuda and x.dtype == self._dtype and not wants_grad):
+            why = ("a gradient with respect to x" if x.is_cuda and x.dtype == self._dtype else
+                   "a CPU tensor" if not x.is_cuda else f"input dtype {x.dtype} with activation dtype {self._dtype}")
+            warn_once(f"LowRankLinearW8:{why}", f"ptdeco_amd.LowRankLinearW8: {why} is not served by the HIP fp8 kernels "
+                                                "(bf16 / f16 inference on a ROCm device); evaluating the torch expression "
+                                                "on 16-bit copies of the factors instead")
+            return _torch_ops.lowrank_w8_expression(x, *operands)
+        x2d = x.reshape(-1, self.in_features)
+        y = _lowrank_forward_w8(x2d, *operands)
+        return y.reshape(*x.shape[:-1], self.out_features)
+
+
+def _quantize_rows(w: torch.Tensor, qdtype: torch.dtype, qmax: float):
+    """Per row of w: s = amax|w| / qmax in f32 (1 for a row of zeros), q = clamp(w / s, -qmax, qmax) in qdtype."""
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    if not bool(torch.isfinite(amax).all()):
+        raise ValueError("quantize_pair: the factors hold non-finite values")
+    s = torch.where(amax > 0, amax / qmax, torch.ones_like(amax))
+    # (the cast maps what lies beyond the largest finite value to NaN: a quotient a hair above qmax must be clamped)
+    q = (wf / s[:, None]).clamp(-qmax, qmax).to(qdtype)
+    return q.contiguous(), s.contiguous()
+
+
+def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3") -> LowRankLinearW8:
+    """An installed ``LowRankLinear`` with bf16 or f16 weights as a ``LowRankLinearW8``: each factor row stored as
+    float8_e4m3fn values times one f32 scale (s = amax|row| / 448, round to nearest), the bias as it is.  Every
+    element satisfies |w - s q| <= max(2^-4 |w|, 2^-10 s).  The pair itself is not modified."""
+    if fmt not in _W8_FORMATS:
+        raise ValueError(f"quantize_pair: fmt must be one of {sorted(_W8_FORMATS)}, got {fmt!r}")
+    if not isinstance(pair, LowRankLinear):
+        raise TypeError(f"quantize_pair: expected an installed LowRankLinear, got {type(pair).__name__}")
+    first, second = pair[0], pair[1]
+    dtype = first.weight.dtype
+    if dtype not in _W8_DTYPES or second.weight.dtype != dtype:
+        raise ValueError(f"quantize_pair: the pair's weights must be bfloat16 or float16 (got {dtype} / "
+                         f"{second.weight.dtype}); cast the model first -- the fp8 kernels take 16-bit activations")
+    qdtype, qmax = _W8_FORMATS[fmt]
+    out = LowRankLinearW8(first.in_features, first.out_features, second.out_features, bias=second.bias is not None,
+                          dtype=dtype, device=first.weight.device)
+    out.weight_a_q, out.scale_a = _quantize_rows(first.weight, qdtype, qmax)
+    out.weight_b_q, out.scale_b = _quantize_rows(second.weight, qdtype, qmax)
+    if second.bias is not None:
+        out.bias = second.bias.detach().to(dtype).clone()
+    return out.train(pair.training)
+
+
+def quantize_pairs_in_place(model: torch.nn.Module, fmt: str = "fp8_e4m3", names=None) -> list:
+    """Replace the installed ``LowRankLinear`` modules of ``model`` whose weights are bf16 or f16 -- all of them, or
+    those listed in ``names`` -- by their ``quantize_pair``; returns the replaced names in module order.  To be applied
+    after ``apply_decompose_config_in_place`` and ``load_state_dict`` (the config and the 16-bit state dict describe
+    the unquantised pairs).  ``LowRankConv1x1``, ``nn.Linear`` and everything else stay as they are; a name in ``names``
+    that is not such a pair raises."""
+    if fmt not in _W8_FORMATS:
+        raise ValueError(f"quantize_pairs_in_place: fmt must be one of {sorted(_W8_FORMATS)}, got {fmt!r}")
+    modules = dict(model.named_modules())
+    if names is not None:
+        names = list(names)
+        for name in names:
+            if not name or not isinstance(modules.get(name), LowRankLinear):
+                raise ValueError(f"quantize_pairs_in_place: {name!r} is not an installed LowRankLinear of the model")
+    done = []
+    for name, mod in list(modules.items()):
+        if not name or not isinstance(mod, LowRankLinear) or (names is not None and name not in names):
+            continue
+        if names is None and mod[0].weight.dtype not in _W8_DTYPES:
+            continue
+        parent, _, leaf = name.rpartition(".")
+        setattr(modules[parent], leaf, quantize_pair(mod, fmt))
+        done.append(name)
+    return done
 
 
 def lowrank_group(x: torch.Tensor, pairs) -> torch.Tensor:
