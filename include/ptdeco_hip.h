@@ -43,7 +43,8 @@ extern "C" {
                              *    ptd_lowrank_decode_group_workspace_bytes, ptd_lowrank_decode_group,
                              *    ptd_lowrank_decode_gated_workspace_bytes, ptd_lowrank_decode_gated,
                              *    ptd_lowrank_skinny_gated_workspace_bytes, ptd_lowrank_skinny_gated,
-                             *    ptd_lowrank_decode_w8_workspace_bytes, ptd_lowrank_decode_w8) */
+                             *    ptd_lowrank_decode_w8_workspace_bytes, ptd_lowrank_decode_w8,
+                             *    ptd_lowrank_skinny_w8_workspace_bytes, ptd_lowrank_skinny_w8) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -410,6 +411,24 @@ size_t ptd_lowrank_skinny_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int
 int ptd_lowrank_skinny(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r,
                        const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy,
                        void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* The pair with 8-bit factors (arguments, formats and semantics of ptd_lowrank_decode_w8: h and y from f32 sums, each
+ * scaled in f32 and rounded ONCE) for 32 <= T <= PTD_LOWRANK_SKINNY_W8_MAX_T tokens, with the structure of
+ * ptd_lowrank_skinny: three launches on the caller's stream (first product into f32 slabs of a K split that depends on
+ * (n_i, r) alone, slab sum with scale_a into a 16-bit h, second product with scale_b and the bias).  Every weight byte
+ * is converted to D in registers on its way to the matrix cores; no dequantised copy is kept; row t of y depends on
+ * row t of x alone, bit for bit, whatever T is.  Served: dtype bf16 / f16, w_format PTD_W8_FP8_E4M3, 32 <= T <=
+ * PTD_LOWRANK_SKINNY_W8_MAX_T, r >= 16, n_i and r multiples of 16, lda and ldb multiples of 16, ldx a multiple of 8,
+ * x, Aq and Bq 16-byte aligned, the scales 4-byte aligned, any n_o >= 1, bias optional.  Anything else returns
+ * PTD_ERR_UNSUPPORTED before a kernel is launched; null pointers, a leading dimension below its row length or a
+ * misaligned workspace PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  The workspace holds the slabs and h (the
+ * formula of ptd_lowrank_skinny_workspace_bytes).  No reference counterpart. */
+#define PTD_LOWRANK_SKINNY_W8_MAX_T 96
+size_t ptd_lowrank_skinny_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int ptd_lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                          const void* Aq, int64_t lda, const float* scale_a, int64_t r,
+                          const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o, const void* bias,
+                          void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 
 /* The gated pair of a decomposed MLP at the same 32 <= T <= 96 tokens in bf16 / f16, y = act(gate(x)) * up(x) (arguments
  * and activations as ptd_lowrank_decode_gated), in three launches on the caller's stream: both first products, both

@@ -18,7 +18,9 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
     lowrank_forward_w8(Tensor x2d, Tensor Aq, Tensor sa, Tensor Bq, Tensor sb, Tensor? bias) -> Tensor
                                                              the pair with fp8 (e4m3fn) factors and f32 row scales:
                                                              ops.lowrank_decode_w8 where ops.lowrank_decode_w8_serves
-                                                             (T <= 16), else the torch expression on 16-bit copies
+                                                             (T <= 16), ops.lowrank_skinny_w8 where
+                                                             ops.lowrank_skinny_w8_serves (32 ... 96), else the torch
+                                                             expression on 16-bit copies
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -167,11 +169,14 @@ def lowrank_forward_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq
     """The pair with 8-bit factors: x2d [T, n_i] bf16 / f16, Aq [r, n_i] and Bq [n_o, r] float8_e4m3fn, sa [r] and sb
     [n_o] f32 scales per factor row, bias [n_o] of x2d's dtype or None; y [T, n_o] contiguous,
     y = round(sb * (h Bq^T) + bias) with h = round(sa * (x2d Aq^T)).  At decode shapes (1 <= T <= 16, aligned operands:
-    ops.lowrank_decode_w8_serves) on the weight-streaming kernels of ptd_lowrank_decode_w8, which keep the sums in f32
-    and round h and y once each.  Elsewhere ``lowrank_w8_expression``: torch's products on transient 16-bit copies of
-    the factors, which round once more than the kernels do, inside ``F.linear``.  Inference only: no autograd formula."""
+    ops.lowrank_decode_w8_serves) on the weight-streaming kernels of ptd_lowrank_decode_w8, at small batches (32 <= T <=
+    96: ops.lowrank_skinny_w8_serves) on the skinny products of ptd_lowrank_skinny_w8; both keep the sums in f32 and
+    round h and y once each.  Elsewhere ``lowrank_w8_expression``: torch's products on transient 16-bit copies of the
+    factors, which round once more than the kernels do, inside ``F.linear``.  Inference only: no autograd formula."""
     if ops.lowrank_decode_w8_serves(x2d, Aq, sa, Bq, sb, bias):
         return ops.lowrank_decode_w8(x2d, Aq, sa, Bq, sb, bias)
+    if ops.lowrank_skinny_w8_serves(x2d, Aq, sa, Bq, sb, bias):
+        return ops.lowrank_skinny_w8(x2d, Aq, sa, Bq, sb, bias)
     return lowrank_w8_expression(x2d, Aq, sa, Bq, sb, bias).contiguous()
 
 

@@ -630,6 +630,33 @@ int ptd_lowrank_skinny(const void* x, int64_t ldx, int64_t T, int64_t n_i, const
   return lowrank_skinny(x, ldx, T, n_i, A, lda, r, B, ldb, n_o, bias, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
 }
 
+size_t ptd_lowrank_skinny_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
+  return lowrank_skinny_w8_workspace_bytes(T, n_i, r, dtype);
+}
+
+int ptd_lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                          const float* scale_a, int64_t r, const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o,
+                          const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format,
+                          void* stream) {
+  PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "ptd_lowrank_skinny_w8: null pointer");
+  PTD_REQUIRE(ldx >= n_i && lda >= n_i && ldb >= r && ldy >= n_o, "ptd_lowrank_skinny_w8: bad leading dimension");
+  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_skinny_w8: the workspace must be 16-byte aligned");
+  // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
+  if (!lowrank_skinny_w8_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, scale_a, Bq, ldb, scale_b, bias)) {
+    set_error("ptd_lowrank_skinny_w8: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d w_format=%d: bf16 / f16, "
+              "PTD_W8_FP8_E4M3, 32 <= T <= %d, r >= 16, n_i and r multiples of 16, 16-byte aligned rows)", (long long)T,
+              (long long)n_i, (long long)r, (long long)n_o, dtype, w_format, PTD_LOWRANK_SKINNY_W8_MAX_T);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  if (ws_bytes < lowrank_skinny_w8_workspace_bytes(T, n_i, r, dtype)) {
+    set_error("ptd_lowrank_skinny_w8: workspace %zu < required %zu bytes", ws_bytes,
+              lowrank_skinny_w8_workspace_bytes(T, n_i, r, dtype));
+    return PTD_ERR_WORKSPACE;
+  }
+  return lowrank_skinny_w8(x, ldx, T, n_i, Aq, lda, scale_a, r, Bq, ldb, scale_b, n_o, bias, y, ldy, ws, dtype,
+                           static_cast<hipStream_t>(stream));
+}
+
 size_t ptd_lowrank_skinny_gated_workspace_bytes(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype) {
   return lowrank_skinny_gated_workspace_bytes(T, n_i, r_g, r_u, dtype);
 }

@@ -104,6 +104,16 @@ int lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i, con
                          const void* Bu, int64_t ldb_u, const void* bias_u, int64_t n_o, int act, void* y, int64_t ldy,
                          void* ws, int dtype, hipStream_t st);
 
+// lowrank_skinny_w8.hip: the fp8 pair of lowrank_decode_w8.hip at 32 <= T <= 96 tokens with the structure of
+// lowrank_skinny.hip: three launches, weights converted in registers (ptd_lowrank_skinny_w8)
+bool lowrank_skinny_w8_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
+                              int64_t ldx, const void* Aq, int64_t lda, const float* sa, const void* Bq, int64_t ldb,
+                              const float* sb, const void* bias);
+size_t lowrank_skinny_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const float* sa,
+                      int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
+                      int64_t ldy, void* ws, int dtype, hipStream_t st);
+
 // eigh_jacobi.hip
 size_t eigh_workspace_bytes(int64_t n);
 int eigh_jacobi(const double* A, int64_t lda, int64_t n, int64_t k, double* evals, double* evecs, int64_t ldv,

@@ -95,8 +95,9 @@ class LowRankLinearW8(torch.nn.Module):
 
     On a ROCm device, for x of the module's dtype and no gradient wanted, ``forward`` calls
     ``torch.ops.ptdeco_amd.lowrank_forward_w8``: at 1 to 16 tokens the HIP kernels of ptd_lowrank_decode_w8 (half the
-    factor bytes of the 16-bit pair, converted in registers), at more tokens the torch expression on transient 16-bit
-    copies of the factors.  Anything else (a CPU copy, another input dtype, ``x.requires_grad``) evaluates that
+    factor bytes of the 16-bit pair, converted in registers), at 32 to 96 tokens those of ptd_lowrank_skinny_w8 (the
+    same semantics in three launches), at any other token count the torch expression on transient 16-bit copies of the
+    factors, which rounds once more per product.  Anything else (a CPU copy, another input dtype, ``x.requires_grad``) evaluates that
     expression directly and says so once, at WARNING.  ``.to(device)`` moves the module; a dtype cast (``.half()``,
     ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the quantised factors and their
     scales as they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place``, or empty for ``load_state_dict``."""

@@ -648,6 +648,80 @@ def lowrank_skinny(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Op
     return y
 
 
+# The fp8 pair of lowrank_decode_w8 at small batches (32 <= T <= _SKINNY_W8_MAX_T tokens) runs on ptd_lowrank_skinny_w8:
+# lowrank_skinny's three launches on fp8 weight bytes, the once-rounded semantics of the decode-w8 kernels.
+# PTD_LOWRANK_SKINNY_W8=0 sends these shapes through the torch expression of torch.ops.ptdeco_amd.lowrank_forward_w8
+# again.  The cap is a constant of its own (PTD_LOWRANK_SKINNY_W8_MAX_T of the header) and is measured,
+# profiles/pair_skinny_w8.json: the largest T of the probe's list up to which every fp8 run beats every run of the
+# expression, by more than the expression's run-to-run spread, in every bf16 cell.
+_SKINNY_W8 = os.environ.get("PTD_LOWRANK_SKINNY_W8", "1") != "0"
+_SKINNY_W8_MAX_T = 96
+
+
+def lowrank_skinny_w8_serves(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                             bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``lowrank_skinny_w8`` takes these operands as they lie (the rule of ptd_lowrank_skinny_w8, without
+    loading the library): real tensors on a ROCm device, x2d bf16 / f16, Aq and Bq float8_e4m3fn, sa and sb contiguous
+    f32, _SKINNY_MIN_T <= T <= _SKINNY_W8_MAX_T, r >= 16, n_i and r multiples of 16, weight row pitches multiples of 16
+    bytes, x2d's a multiple of 8 elements, unit inner strides, 16-byte aligned data."""
+    if not _SKINNY_W8:
+        return False
+    ts = (x2d, Aq, sa, Bq, sb) if bias is None else (x2d, Aq, sa, Bq, sb, bias)
+    for t in ts:
+        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
+            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
+    if x2d.dim() != 2 or Aq.dim() != 2 or Bq.dim() != 2 or sa.dim() != 1 or sb.dim() != 1:
+        return False
+    if x2d.dtype not in (torch.bfloat16, torch.float16) or Aq.dtype != torch.float8_e4m3fn or Bq.dtype != Aq.dtype:
+        return False
+    if sa.dtype != torch.float32 or sb.dtype != torch.float32:
+        return False
+    (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
+    if Aq.shape[1] != n_i or Bq.shape[1] != r or sa.shape[0] != r or sb.shape[0] != n_o:
+        return False
+    if not _SKINNY_MIN_T <= T <= _SKINNY_W8_MAX_T or n_o < 1 or r < 16 or n_i % 16 or r % 16:
+        return False
+    if n_i >= 1 << 30 or r >= 1 << 27 or n_o >= 1 << 30:
+        return False
+    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o or bias.dtype != x2d.dtype
+                             or (n_o > 1 and bias.stride(0) != 1)):
+        return False
+    for t, vec in ((x2d, 8), (Aq, 16), (Bq, 16)):
+        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % 16:
+            return False
+    for s in (sa, sb):
+        if (s.shape[0] > 1 and s.stride(0) != 1) or s.data_ptr() % 4:
+            return False
+    return True
+
+
+def lowrank_skinny_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                      bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """round(sb * (h @ Bq^T) + bias) with h = round(sa * (x2d @ Aq^T)) for 32 <= T <= _SKINNY_W8_MAX_T rows of x2d
+    (bf16 / f16), Aq [r, n_i] and Bq [n_o, r] float8_e4m3fn, sa [r] and sb [n_o] f32: ptd_lowrank_skinny_w8 (sums in
+    f32, each rounded once to x2d's dtype).  Operands the entry does not serve (``lowrank_skinny_w8_serves``) raise; row
+    t of the result depends on row t of x2d alone."""
+    _dev(x2d, Aq, sa, Bq, sb, bias)
+    x2d, Aq, Bq = _rows2d(x2d), _rows2d(Aq), _rows2d(Bq)
+    T, n_i = x2d.shape
+    r, n_o = Aq.shape[0], Bq.shape[0]
+    assert Aq.shape[1] == n_i and Bq.shape[1] == r and sa.shape == (r,) and sb.shape == (n_o,)
+    assert Aq.dtype == Bq.dtype == torch.float8_e4m3fn and sa.dtype == sb.dtype == torch.float32
+    sa, sb = sa.contiguous(), sb.contiguous()
+    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
+    lib = _hip.load()
+    ws_bytes = lib.ptd_lowrank_skinny_w8_workspace_bytes(T, n_i, r, _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+    if bias is not None:
+        bias = bias.to(x2d.dtype).contiguous()
+    with torch.cuda.device(x2d.device):
+        rc = lib.ptd_lowrank_skinny_w8(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0), sa.data_ptr(),
+                                       r, Bq.data_ptr(), Bq.stride(0), sb.data_ptr(), n_o, _ptr(bias), y.data_ptr(), n_o,
+                                       ws.data_ptr(), ws_bytes, _code(x2d), W8_FP8_E4M3, _stream(x2d))
+    _hip.check(rc, "ptd_lowrank_skinny_w8")
+    return y
+
+
 # The gated pair of an MLP at small batches, act(gate(x)) * up(x), runs on ptd_lowrank_skinny_gated: three launches (both
 # first products, both slab sums, both second products with the activation and the product in the lanes that hold both
 # sums).  g and u are the bits lowrank_skinny gives the members.  No switch or constant of its own: the rule is
