@@ -44,7 +44,8 @@ extern "C" {
                              *    ptd_lowrank_decode_gated_workspace_bytes, ptd_lowrank_decode_gated,
                              *    ptd_lowrank_skinny_gated_workspace_bytes, ptd_lowrank_skinny_gated,
                              *    ptd_lowrank_decode_w8_workspace_bytes, ptd_lowrank_decode_w8,
-                             *    ptd_lowrank_skinny_w8_workspace_bytes, ptd_lowrank_skinny_w8) */
+                             *    ptd_lowrank_skinny_w8_workspace_bytes, ptd_lowrank_skinny_w8,
+                             *    ptd_lowrank_decode_w4_workspace_bytes, ptd_lowrank_decode_w4) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -356,6 +357,33 @@ size_t ptd_lowrank_decode_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, 
 int ptd_lowrank_decode_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                           const void* Aq, int64_t lda, const float* scale_a, int64_t r,
                           const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o, const void* bias,
+                          void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+
+/* The pair at 1 <= T <= 16 tokens with OCP MXFP4 factors (weight-only quantisation: 4.25 bits per weight, 16-bit
+ * activations): x [T, n_i], bias [n_o] and y [T, n_o] in dtype D = bf16 or f16; Aq [r, n_i / 2] and Bq [n_o, r / 2] bytes of
+ * packed e2m1 codes, scale_a [r, n_i / 32] and scale_b [n_o, r / 32] bytes of e8m0 block scales, one per 32 consecutive
+ * weights of a row; lda, ldb, ldsa and ldsb in bytes.
+ *   code(W, i, k) = (Wq[i, k >> 1] >> (4 * (k & 1))) & 15          (low nibble = even k)
+ *   val(c)        = (c & 8 ? -1 : 1) * {0, .5, 1, 1.5, 2, 3, 4, 6}[c & 7]
+ *   W^[i, k]      = val(code(W, i, k)) * 2^(clamp(scale[i, k >> 5], 114, 140) - 127)
+ *   h[t, i] = round_D(sum_k x[t, k] A^[i, k]),   y[t, o] = round_D(sum_i h[t, i] B^[o, i] + bias[o])
+ * with the sums in f32, each rounded ONCE.  The clamp is part of the semantics: a block exponent in [-13, 13] makes every
+ * W^ a normal number of bf16 and of f16, so the conversion in registers rounds nothing and the result does not depend on
+ * denormal modes.  There are no per-row scales: this is ptd_lowrank_decode on the dequantised factors, with its rounding
+ * points.  Two weight-streaming kernels on the caller's stream: a lane's 16-byte load is one block, converted to D in
+ * registers with the block scale applied by the same instruction; no dequantised copy is kept, and row t of y depends on
+ * row t of x alone, bit for bit, whatever T is.  w_format: PTD_W4_MXFP4.  Served: dtype bf16 / f16, 1 <= T <= 16,
+ * r >= 32, n_i and r multiples of 32, lda and ldb multiples of 16 (lda >= n_i / 2, ldb >= r / 2), ldsa >= n_i / 32 and
+ * ldsb >= r / 32 (the scale rows need no alignment), ldx a multiple of 8, x, Aq and Bq 16-byte aligned, any n_o >= 1,
+ * bias optional.  Anything else (f32, another w_format) returns PTD_ERR_UNSUPPORTED before a kernel is launched; null
+ * pointers, a leading dimension below its row length or a misaligned workspace PTD_ERR_INVALID; a short workspace
+ * PTD_ERR_WORKSPACE.  The workspace holds the f32 partial sums of the first product's K split, added in a fixed order.
+ * No reference counterpart. */
+#define PTD_W4_MXFP4 0
+size_t ptd_lowrank_decode_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int ptd_lowrank_decode_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                          const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
+                          const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
                           void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 
 /* 1 <= count <= PTD_LOWRANK_GROUP_MAX pairs that read the same x at decode shapes (the q / k / v or gate / up projections

@@ -21,6 +21,11 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
                                                              (T <= 16), ops.lowrank_skinny_w8 where
                                                              ops.lowrank_skinny_w8_serves (32 ... 96), else the torch
                                                              expression on 16-bit copies
+    lowrank_forward_w4(Tensor x2d, Tensor Aq, Tensor ea, Tensor Bq, Tensor eb, Tensor? bias) -> Tensor
+                                                             the pair with OCP MXFP4 factors (packed e2m1 codes, e8m0
+                                                             block scales): ops.lowrank_decode_w4 where
+                                                             ops.lowrank_decode_w4_serves (T <= 16), else the torch
+                                                             expression on 16-bit copies
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -190,6 +195,65 @@ def _(x2d, Aq, sa, Bq, sb, bias):
                  lambda: "lowrank_forward_w8: the factors must be float8_e4m3fn")
     torch._check(bias is None or tuple(bias.shape) == (Bq.shape[0],), lambda: "lowrank_forward_w8: bias must be [n_o]")
     return x2d.new_empty((x2d.shape[0], Bq.shape[0]))
+
+
+# e2m1: sign, two exponent bits, one mantissa bit -- the value of code c is (c & 8 ? -1 : 1) * _E2M1[c & 7]
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+W4_BLOCK = 32                  # weights per e8m0 scale byte
+W4_E_MIN, W4_E_MAX = 114, 140  # the clamp of the semantics on a scale byte: block exponents -13 .. 13
+
+
+def lowrank_w4_dequant(q: torch.Tensor, e: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """The MXFP4 factor W^ [rows, cols] in ``dtype`` from its packed codes q [rows, cols / 2] (uint8, the low nibble
+    the even k) and its block scales e [rows, cols / 32] (uint8, e8m0):
+    W^[i, k] = e2m1(code) * 2^(clamp(e[i, k >> 5], 114, 140) - 127).  Exact in bf16 and in f16: the clamp keeps every
+    product between 2^-14 and 49152, a normal number of both."""
+    rows, cols = q.shape[0], 2 * q.shape[1]
+    lut = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float32, device=q.device)
+    codes = torch.stack((q & 15, q >> 4), dim=-1).reshape(rows, cols).long()
+    scale = torch.exp2(e.clamp(W4_E_MIN, W4_E_MAX).float() - 127.0)
+    w = lut[codes].reshape(rows, cols // W4_BLOCK, W4_BLOCK) * scale[:, :, None]
+    return w.reshape(rows, cols).to(dtype)
+
+
+def lowrank_w4_expression(x: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                          bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The semantics of the MXFP4 pair in torch, D = x.dtype: the 16-bit pair on transient copies of the dequantised
+    factors in D (``lowrank_w4_dequant``, exact), h and y rounded where ``F.linear`` rounds them."""
+    linear = torch.nn.functional.linear
+    h = linear(x, lowrank_w4_dequant(Aq, ea, x.dtype))
+    return linear(h, lowrank_w4_dequant(Bq, eb, x.dtype), bias)
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_w4", mutates_args=())
+def lowrank_forward_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                       bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The pair with OCP MXFP4 factors: x2d [T, n_i] bf16 / f16, Aq [r, n_i / 2] and Bq [n_o, r / 2] packed e2m1 codes,
+    ea [r, n_i / 32] and eb [n_o, r / 32] e8m0 block scales (all uint8), bias [n_o] of x2d's dtype or None; y [T, n_o]
+    contiguous, y = round(h B^^T + bias) with h = round(x2d A^^T).  At decode shapes (1 <= T <= 16, aligned operands:
+    ops.lowrank_decode_w4_serves) on the weight-streaming kernels of ptd_lowrank_decode_w4; elsewhere
+    ``lowrank_w4_expression``: torch's products on transient 16-bit copies of the factors.  Inference only: no autograd
+    formula."""
+    if ops.lowrank_decode_w4_serves(x2d, Aq, ea, Bq, eb, bias):
+        return ops.lowrank_decode_w4(x2d, Aq, ea, Bq, eb, bias)
+    return lowrank_w4_expression(x2d, Aq, ea, Bq, eb, bias).contiguous()
+
+
+@lowrank_forward_w4.register_fake
+def _(x2d, Aq, ea, Bq, eb, bias):
+    torch._check(x2d.dim() == 2 and Aq.dim() == 2 and ea.dim() == 2 and Bq.dim() == 2 and eb.dim() == 2,
+                 lambda: "lowrank_forward_w4: 2-D operands")
+    torch._check(all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)),
+                 lambda: "lowrank_forward_w4: the codes and the block scales must be uint8")
+    torch._check(x2d.dtype in (torch.bfloat16, torch.float16), lambda: "lowrank_forward_w4: x2d must be bfloat16 or float16")
+    n_i, r, n_o = x2d.shape[1], Aq.shape[0], Bq.shape[0]
+    torch._check(n_i % W4_BLOCK == 0 and r % W4_BLOCK == 0, lambda: "lowrank_forward_w4: n_i and r must be multiples of 32")
+    torch._check(tuple(Aq.shape) == (r, n_i // 2) and tuple(Bq.shape) == (n_o, r // 2),
+                 lambda: "lowrank_forward_w4: shape mismatch (Aq [r, n_i / 2], Bq [n_o, r / 2])")
+    torch._check(tuple(ea.shape) == (r, n_i // W4_BLOCK) and tuple(eb.shape) == (n_o, r // W4_BLOCK),
+                 lambda: "lowrank_forward_w4: one scale byte per 32 weights of a row")
+    torch._check(bias is None or tuple(bias.shape) == (n_o,), lambda: "lowrank_forward_w4: bias must be [n_o]")
+    return x2d.new_empty((x2d.shape[0], n_o))
 
 
 @torch.library.custom_op("ptdeco_amd::lowrank_forward_nchw", mutates_args=())

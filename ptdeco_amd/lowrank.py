@@ -26,6 +26,7 @@ _lowrank_forward_nchw = torch.ops.ptdeco_amd.lowrank_forward_nchw.default
 _lowrank_forward_group = torch.ops.ptdeco_amd.lowrank_forward_group.default
 _lowrank_forward_gated = torch.ops.ptdeco_amd.lowrank_forward_gated.default
 _lowrank_forward_w8 = torch.ops.ptdeco_amd.lowrank_forward_w8.default
+_lowrank_forward_w4 = torch.ops.ptdeco_amd.lowrank_forward_w4.default
 
 logger = logging.getLogger(__name__)
 
@@ -153,6 +154,90 @@ class LowRankLinearW8(torch.nn.Module):
         return y.reshape(*x.shape[:-1], self.out_features)
 
 
+_W4_FORMAT = "mxfp4"
+_W4_BLOCK = _torch_ops.W4_BLOCK
+_QUANT_FORMATS = tuple(_W8_FORMATS) + (_W4_FORMAT,)
+
+
+class LowRankLinearW4(torch.nn.Module):
+    """A rank-r pair with OCP MXFP4 factors (weight-only quantisation, 4.25 bits per weight): ``weight_a_q``
+    [rank, in_features / 2] and ``weight_b_q`` [out_features, rank / 2] hold packed e2m1 codes (two per byte, the low
+    nibble the even k), ``scale_a`` [rank, in_features / 32] and ``scale_b`` [out_features, rank / 32] one e8m0 scale
+    byte per 32 consecutive weights of a row, and ``bias`` [out_features] is in the activation dtype (bf16 or f16) or
+    None -- all buffers: the module is inference-only and has no trainable parameters.  The codes and the scales are
+    plain ``torch.uint8`` (it moves, saves and loads everywhere); ``.view(torch.float4_e2m1fn_x2)`` and
+    ``.view(torch.float8_e8m0fnu)`` are their standard views.  With D the activation dtype and
+    W^[i, k] = e2m1(code) * 2^(clamp(scale[i, k >> 5], 114, 140) - 127) (``_torch_ops.lowrank_w4_dequant``; the clamp
+    is part of the semantics and makes every W^ exact in D),
+
+        h = round_D(x A^^T)        y = round_D(h B^^T + bias)
+
+    ``in_features`` and ``rank`` are multiples of 32; ``rank`` is the STORED rank: ``quantize_pair`` pads a pair whose
+    rank is not a multiple of 32 with zero rows of A and zero columns of B (scale byte 127), which changes no result.
+
+    On a ROCm device, for x of the module's dtype and no gradient wanted, ``forward`` calls
+    ``torch.ops.ptdeco_amd.lowrank_forward_w4``: at 1 to 16 tokens the HIP kernels of ptd_lowrank_decode_w4 (a quarter
+    of the factor bytes of the 16-bit pair, converted in registers), at any other token count the torch expression on
+    transient 16-bit copies of the factors.  Anything else (a CPU copy, another input dtype, ``x.requires_grad``)
+    evaluates that expression directly and says so once, at WARNING.  The format is coarse -- round to nearest gives a
+    noise-to-signal ratio of about 2.5e-2 on Gaussian factors, against 1.4e-3 for fp8 -- so it is meant to be chosen
+    layer by layer (``quantize_pairs_in_place(model, "mxfp4", names=...)``).  ``.to(device)`` moves the module; a dtype
+    cast (``.half()``, ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the packed buffers
+    as they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place``, or empty for ``load_state_dict``."""
+
+    def __init__(self, in_features: int, rank: int, out_features: int, bias: bool = True,
+                 dtype: torch.dtype = torch.bfloat16, device=None) -> None:
+        super().__init__()
+        if dtype not in _W8_DTYPES:
+            raise ValueError(f"LowRankLinearW4: the activation dtype must be bfloat16 or float16, got {dtype}")
+        if in_features % _W4_BLOCK or rank % _W4_BLOCK or rank < _W4_BLOCK or in_features < _W4_BLOCK:
+            raise ValueError(f"LowRankLinearW4: in_features and rank must be positive multiples of {_W4_BLOCK}, got "
+                             f"{in_features} and {rank}")
+        self.in_features, self.rank, self.out_features = int(in_features), int(rank), int(out_features)
+        self._dtype = dtype
+
+        def zeros(rows, cols, fill=0):
+            return torch.full((rows, cols), fill, dtype=torch.uint8, device=device)
+
+        self.register_buffer("weight_a_q", zeros(rank, in_features // 2))
+        self.register_buffer("scale_a", zeros(rank, in_features // _W4_BLOCK, 127))
+        self.register_buffer("weight_b_q", zeros(out_features, rank // 2))
+        self.register_buffer("scale_b", zeros(out_features, rank // _W4_BLOCK, 127))
+        self.register_buffer("bias", torch.zeros(out_features, dtype=dtype, device=device) if bias else None)
+
+    @property
+    def dtype(self) -> torch.dtype:
+        """The activation dtype D: what x must be for the HIP kernels, and what the bias is held in."""
+        return self._dtype
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)      # (a dtype cast leaves integer buffers alone: the packed bytes stay)
+        cast = fn(torch.empty(0, dtype=self._dtype)).dtype
+        if cast in _W8_DTYPES:
+            self._dtype = cast
+        if self.bias is not None and self.bias.dtype != self._dtype:
+            self._buffers["bias"] = self.bias.to(self._dtype)
+        return self
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, rank={self.rank}, out_features={self.out_features}, "
+                f"bias={self.bias is not None}, dtype={self._dtype}")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        operands = (self.weight_a_q, self.scale_a, self.weight_b_q, self.scale_b, self.bias)
+        wants_grad = torch.is_grad_enabled() and x.requires_grad
+        if not (x.is_cuda and x.dtype == self._dtype and not wants_grad):
+            why = ("a gradient with respect to x" if x.is_cuda and x.dtype == self._dtype else
+                   "a CPU tensor" if not x.is_cuda else f"input dtype {x.dtype} with activation dtype {self._dtype}")
+            warn_once(f"LowRankLinearW4:{why}", f"ptdeco_amd.LowRankLinearW4: {why} is not served by the HIP MXFP4 kernels "
+                                                "(bf16 / f16 inference on a ROCm device); evaluating the torch expression "
+                                                "on 16-bit copies of the factors instead")
+            return _torch_ops.lowrank_w4_expression(x, *operands)
+        x2d = x.reshape(-1, self.in_features)
+        y = _lowrank_forward_w4(x2d, *operands)
+        return y.reshape(*x.shape[:-1], self.out_features)
+
+
 def _quantize_rows(w: torch.Tensor, qdtype: torch.dtype, qmax: float):
     """Per row of w: s = amax|w| / qmax in f32 (1 for a row of zeros), q = clamp(w / s, -qmax, qmax) in qdtype."""
     wf = w.detach().float()
@@ -165,19 +250,79 @@ def _quantize_rows(w: torch.Tensor, qdtype: torch.dtype, qmax: float):
     return q.contiguous(), s.contiguous()
 
 
-def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3") -> LowRankLinearW8:
+# 2 |v| for the e2m1 magnitudes v = 0, .5, 1, 1.5, 2, 3, 4, 6 -> the three low bits of the code
+_E2M1_CODE_OF_TWICE = (0, 1, 2, 3, 4, 0, 5, 0, 6, 0, 0, 0, 7)
+
+
+def _quantize_mxfp4(w: torch.Tensor):
+    """w [rows, cols] (cols a multiple of 32) as OCP MXFP4: per block of 32 consecutive weights of a row the exponent
+    e = clamp(floor(log2 amax) - 2, -13, 13) (0 for a block of zeros), stored as the byte e + 127, and per weight the
+    e2m1 code nearest to w / 2^e, ties to the even code, saturating at +-6; two codes per byte, the low nibble the even
+    k.  Where e is not clamped, |w - w^| <= amax_block / 4: 2^(e + 2) <= amax < 2^(e + 3), the grid's widest step is
+    2 * 2^e (an error of at most 2^e <= amax / 4), and a weight beyond 6 * 2^e errs by less than amax - 6 * 2^e <
+    amax / 4.  Returns (codes [rows, cols / 2], scales [rows, cols / 32]), uint8."""
+    rows, cols = w.shape
+    if cols % _W4_BLOCK:
+        raise ValueError(f"quantize_pair: mxfp4 needs rows of a multiple of {_W4_BLOCK} weights, got {cols}")
+    blocks = w.detach().float().reshape(rows, cols // _W4_BLOCK, _W4_BLOCK)
+    amax = blocks.abs().amax(dim=-1)
+    if not bool(torch.isfinite(amax).all()):
+        raise ValueError("quantize_pair: the factors hold non-finite values")
+    if bool((amax >= 2.0 ** 16).any()):
+        raise ValueError("quantize_pair: a block of 32 weights reaches 2^16, beyond what mxfp4 with block exponents "
+                         "up to 13 represents")
+    _, exponent = torch.frexp(amax)          # amax = m 2^exponent with 0.5 <= m < 1: floor(log2 amax) = exponent - 1
+    e = torch.where(amax > 0, (exponent - 3).clamp(-13, 13), torch.zeros_like(exponent))
+    v = torch.ldexp(blocks, -e[:, :, None])  # exact
+    a = v.abs().clamp(max=6.0)
+    # round to nearest, ties to even, on the grid's three step sizes (.5 below 2, 1 below 4, 2 up to 6): torch.round is
+    # ties-to-even, and an even multiple of the step is the code with mantissa bit 0
+    a = torch.where(a < 2.0, torch.round(a * 2.0) / 2.0, torch.where(a < 4.0, torch.round(a), torch.round(a / 2.0) * 2.0))
+    table = torch.tensor(_E2M1_CODE_OF_TWICE, dtype=torch.uint8, device=w.device)
+    codes = table[(a * 2.0).long()]
+    codes = codes | (((v < 0) & (a > 0)).to(torch.uint8) << 3)
+    codes = codes.reshape(rows, cols)
+    packed = codes[:, 0::2] | (codes[:, 1::2] << 4)
+    return packed.contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def _quantize_pair_mxfp4(first, second, dtype) -> LowRankLinearW4:
+    n_i, r, n_o = first.in_features, first.out_features, second.out_features
+    if n_i % _W4_BLOCK:
+        raise ValueError(f"quantize_pair: mxfp4 needs in_features to be a multiple of {_W4_BLOCK}, got {n_i}")
+    stored = -(-r // _W4_BLOCK) * _W4_BLOCK      # zero rows of A and zero columns of B up to a whole block: no result changes
+    wa, wb = first.weight.detach(), second.weight.detach()
+    if stored != r:
+        wa = torch.cat([wa, wa.new_zeros(stored - r, n_i)], 0)
+        wb = torch.cat([wb, wb.new_zeros(n_o, stored - r)], 1)
+    out = LowRankLinearW4(n_i, stored, n_o, bias=second.bias is not None, dtype=dtype, device=first.weight.device)
+    out.weight_a_q, out.scale_a = _quantize_mxfp4(wa)
+    out.weight_b_q, out.scale_b = _quantize_mxfp4(wb)
+    return out
+
+
+def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3"):
     """An installed ``LowRankLinear`` with bf16 or f16 weights as a ``LowRankLinearW8``: each factor row stored as
     float8_e4m3fn values times one f32 scale (s = amax|row| / 448, round to nearest), the bias as it is.  Every
-    element satisfies |w - s q| <= max(2^-4 |w|, 2^-10 s).  The pair itself is not modified."""
-    if fmt not in _W8_FORMATS:
-        raise ValueError(f"quantize_pair: fmt must be one of {sorted(_W8_FORMATS)}, got {fmt!r}")
+    element satisfies |w - s q| <= max(2^-4 |w|, 2^-10 s).  With ``fmt="mxfp4"`` a ``LowRankLinearW4`` instead: OCP MXFP4
+    blocks of 32 weights (``_quantize_mxfp4``: |w - w^| <= amax_block / 4 where the block exponent is not clamped),
+    in_features a multiple of 32, the rank zero-padded to one; about a quarter of the 16-bit pair's bytes at a
+    noise-to-signal ratio near 2.5e-2 on Gaussian factors, so a format to choose layer by layer.  The pair itself is
+    not modified."""
+    if fmt not in _QUANT_FORMATS:
+        raise ValueError(f"quantize_pair: fmt must be one of {sorted(_QUANT_FORMATS)}, got {fmt!r}")
     if not isinstance(pair, LowRankLinear):
         raise TypeError(f"quantize_pair: expected an installed LowRankLinear, got {type(pair).__name__}")
     first, second = pair[0], pair[1]
     dtype = first.weight.dtype
     if dtype not in _W8_DTYPES or second.weight.dtype != dtype:
         raise ValueError(f"quantize_pair: the pair's weights must be bfloat16 or float16 (got {dtype} / "
-                         f"{second.weight.dtype}); cast the model first -- the fp8 kernels take 16-bit activations")
+                         f"{second.weight.dtype}); cast the model first -- the fp8 and mxfp4 kernels take 16-bit activations")
+    if fmt == _W4_FORMAT:
+        out = _quantize_pair_mxfp4(first, second, dtype)
+        if second.bias is not None:
+            out.bias = second.bias.detach().to(dtype).clone()
+        return out.train(pair.training)
     qdtype, qmax = _W8_FORMATS[fmt]
     out = LowRankLinearW8(first.in_features, first.out_features, second.out_features, bias=second.bias is not None,
                           dtype=dtype, device=first.weight.device)
@@ -190,12 +335,13 @@ def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3") -> LowRankLinearW8
 
 def quantize_pairs_in_place(model: torch.nn.Module, fmt: str = "fp8_e4m3", names=None) -> list:
     """Replace the installed ``LowRankLinear`` modules of ``model`` whose weights are bf16 or f16 -- all of them, or
-    those listed in ``names`` -- by their ``quantize_pair``; returns the replaced names in module order.  To be applied
+    those listed in ``names`` -- by their ``quantize_pair`` in ``fmt`` ("fp8_e4m3" or "mxfp4"); returns the replaced
+    names in module order.  To be applied
     after ``apply_decompose_config_in_place`` and ``load_state_dict`` (the config and the 16-bit state dict describe
     the unquantised pairs).  ``LowRankConv1x1``, ``nn.Linear`` and everything else stay as they are; a name in ``names``
     that is not such a pair raises."""
-    if fmt not in _W8_FORMATS:
-        raise ValueError(f"quantize_pairs_in_place: fmt must be one of {sorted(_W8_FORMATS)}, got {fmt!r}")
+    if fmt not in _QUANT_FORMATS:
+        raise ValueError(f"quantize_pairs_in_place: fmt must be one of {sorted(_QUANT_FORMATS)}, got {fmt!r}")
     modules = dict(model.named_modules())
     if names is not None:
         names = list(names)
