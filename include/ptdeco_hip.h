@@ -45,7 +45,8 @@ extern "C" {
                              *    ptd_lowrank_skinny_gated_workspace_bytes, ptd_lowrank_skinny_gated,
                              *    ptd_lowrank_decode_w8_workspace_bytes, ptd_lowrank_decode_w8,
                              *    ptd_lowrank_skinny_w8_workspace_bytes, ptd_lowrank_skinny_w8,
-                             *    ptd_lowrank_decode_w4_workspace_bytes, ptd_lowrank_decode_w4) */
+                             *    ptd_lowrank_decode_w4_workspace_bytes, ptd_lowrank_decode_w4,
+                             *    ptd_lowrank_plan) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -475,6 +476,47 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                              const void* Au, int64_t lda_u, int64_t r_u, const void* Bu, int64_t ldb_u, const void* bias_u,
                              int64_t n_ff, int act, void* y, int64_t ldy,
                              void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* Host query for tests and tools: the numbers a launch of one serving family of the pair would use for (T, n_i, r, n_o,
+ * dtype) with contiguous, aligned operands -- computed by the functions the launchers and kernels themselves call, so a
+ * test can prove which branch combination a shape reaches.  family: PTD_PLAN_DECODE (ptd_lowrank_decode; every member
+ * of ptd_lowrank_decode_group and both members of ptd_lowrank_decode_gated take the plan of that member alone),
+ * PTD_PLAN_DECODE_W8, PTD_PLAN_DECODE_W4, PTD_PLAN_SKINNY (ptd_lowrank_skinny; both members of
+ * ptd_lowrank_skinny_gated take the plan of that member alone), PTD_PLAN_SKINNY_W8.  Writes out[PTD_PLAN_*] for the
+ * PTD_PLAN_LEN indices below and returns PTD_PLAN_LEN; PTD_ERR_UNSUPPORTED where the family does not serve the shape or
+ * the family is unknown, PTD_ERR_INVALID for a null `out` or cap < PTD_PLAN_LEN.  "First product" is x A^T into K slabs,
+ * "second" h B^T.  A wave's "load step" is the k its 64 lanes cover with one 16-byte load each (32 for bf16 / f16, 16 for
+ * f32, 64 for fp8 and the skinny kernels, 128 for MXFP4).  No device code, no launch, no allocation: works without a
+ * GPU.  No reference counterpart. */
+#define PTD_PLAN_DECODE 0
+#define PTD_PLAN_DECODE_W8 1
+#define PTD_PLAN_DECODE_W4 2
+#define PTD_PLAN_SKINNY 3
+#define PTD_PLAN_SKINNY_W8 4
+#define PTD_PLAN_NSLABS 0             /* K slabs of the first product */
+#define PTD_PLAN_KCHUNK 1             /* k of one slab (four wave ranges of kchunk / 4) */
+#define PTD_PLAN_XA_GRID_X 2          /* first product: row tiles, */
+#define PTD_PLAN_XA_GRID_Y 3          /*   slabs, */
+#define PTD_PLAN_XA_GRID_Z 4          /*   token tiles (1 at decode) */
+#define PTD_PLAN_XA_EMPTY_WAVES 5     /* of the LAST slab's four waves, those whose K range is empty */
+#define PTD_PLAN_XA_TAIL_IN_STEP 6    /* 1: the last non-empty wave's range ends inside a load step */
+#define PTD_PLAN_XA_U 7               /* first product's kernel variant: loads in flight per lane (MXFP4: blocks per lane, U) */
+#define PTD_PLAN_XA_TAIL_BLOCKS 8     /* MXFP4: (n_i / 32) % U -- non-zero: a valid block's scale byte is a shifted one; else 0 */
+#define PTD_PLAN_HB_GRID 9            /* second product: workgroups (skinny: row tiles of 32) */
+#define PTD_PLAN_HB_NCHUNKS 10        /* decode: LDS chunks of h per tile (skinny: 1) */
+#define PTD_PLAN_HB_CHUNK_K 11        /* k of a full chunk (a wave takes a quarter) */
+#define PTD_PLAN_HB_LAST_CHUNK_K 12   /* k of the last chunk */
+#define PTD_PLAN_HB_TILES_MAX 13      /* decode: tiles of 16 rows per workgroup, the most */
+#define PTD_PLAN_HB_TILES_MIN 14      /*   and the fewest (workgroup b takes tiles b, b + grid, ...); skinny: 1 and 1 */
+#define PTD_PLAN_HB_LAST_TILE_ROWS 15 /* rows of n_o in the last row tile (16 at decode, 32 skinny, when it is full) */
+#define PTD_PLAN_HB_U 16              /* second product's variant: loads per lane and chunk (MXFP4: blocks per lane, U) */
+#define PTD_PLAN_HB_TAIL_BLOCKS 17    /* MXFP4: (r / 32) % U; else 0 */
+#define PTD_PLAN_COMBINE_GRID 18      /* skinny: workgroups of the slab sum (decode: 0, the second product sums the slabs) */
+#define PTD_PLAN_TOKEN_TILES 19       /* skinny: tiles of 64 tokens (decode: 1) */
+#define PTD_PLAN_SLABS_ASKED 20      /* the slab count the rank asks for: what the split gives a row of 2^20 k (nslabs is
+                                      * smaller where n_i is too short to be cut that often) */
+#define PTD_PLAN_LEN 21
+int ptd_lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap);
 
 /* The same pair for a 1x1-convolution input in NCHW layout, without the NHWC copy the reference makes
  * (`permute(0,2,3,1).reshape(-1,C)`, dwain.py:116; falor.py:126): per image b, x_b = x + b*n_i*hw is an

@@ -105,6 +105,7 @@ SIGNATURES = {
                                          c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
                                          c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
                                          c_int64, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]),
+    "ptd_lowrank_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),
     "ptd_lowrank_forward_nchw_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
     "ptd_lowrank_forward_nchw": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
                                          c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),

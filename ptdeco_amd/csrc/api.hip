@@ -686,6 +686,17 @@ int ptd_lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                            static_cast<hipStream_t>(stream));
 }
 
+int ptd_lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap) {
+  PTD_REQUIRE(out, "ptd_lowrank_plan: null pointer");
+  PTD_REQUIRE(cap >= PTD_PLAN_LEN, "ptd_lowrank_plan: out holds %d values, the plan has %d", cap, PTD_PLAN_LEN);
+  if (lowrank_plan(family, T, n_i, r, n_o, dtype, out) != PTD_OK) {
+    set_error("ptd_lowrank_plan: not served (family=%d T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d)", family, (long long)T,
+              (long long)n_i, (long long)r, (long long)n_o, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  return PTD_PLAN_LEN;
+}
+
 size_t ptd_lowrank_skinny_gated_workspace_bytes(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype) {
   return lowrank_skinny_gated_workspace_bytes(T, n_i, r_g, r_u, dtype);
 }

@@ -58,6 +58,16 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The first product of the serving pair kernels (lowrank_decode*.hip, lowrank_skinny*.hip): the K range of wave `wave`
+// of slab `slab` -- a quarter of kchunk each, cut at the end of the row.  Host and device: lowrank_plan.hip reports what
+// a launch would do by calling the function the kernels call.
+static __host__ __device__ inline void xa_wave_range(const int slab, const int kchunk, const int wave, const int k_total,
+                                                     int& kbeg, int& kend) {
+  const int kw = kchunk >> 2;     // a multiple of the load step
+  kbeg = slab * kchunk + wave * kw;
+  kend = kbeg + kw < k_total ? kbeg + kw : k_total;
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));

@@ -123,6 +123,10 @@ int lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const 
                       int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
                       int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_plan.hip: what a launch of one serving family would do, from the host rules the launchers call (ptd_lowrank_plan);
+// fills out[PTD_PLAN_*], PTD_OK or PTD_ERR_UNSUPPORTED
+int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out);
+
 // eigh_jacobi.hip
 size_t eigh_workspace_bytes(int64_t n);
 int eigh_jacobi(const double* A, int64_t lda, int64_t n, int64_t k, double* evals, double* evecs, int64_t ldv,

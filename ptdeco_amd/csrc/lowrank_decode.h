@@ -56,6 +56,19 @@ struct DecF32 {
   static __device__ __forceinline__ void put4(elem* dst, f32x4 v) { *reinterpret_cast<f32x4*>(dst) = v; }
 };
 
+// The index rules of the second product that its kernels and the host share (lowrank_plan.hip reports what a launch
+// would do by calling them; xa_wave_range of common.h is the first product's).  LDS chunks of h in a second product (kc = k of one chunk)
+__host__ __device__ inline int hb_nchunks(const int r, const int kc) { return (r + kc - 1) / kc; }
+
+// this wave's k range of chunk `chunk` in a second product: a quarter of the chunk's width, rounded up to whole load steps
+__host__ __device__ inline void hb_chunk_wave_range(const int r, const int kc, const int kstep, const int chunk,
+                                                    const int wave, int& kbeg, int& kend) {
+  const int c0 = chunk * kc, kcv = kc < r - c0 ? kc : r - c0;
+  const int kw = ((kcv + 3) / 4 + kstep - 1) / kstep * kstep;
+  kbeg = c0 + wave * kw;
+  kend = kbeg + kw < c0 + kcv ? kbeg + kw : c0 + kcv;
+}
+
 template <typename F, bool NT>
 __device__ __forceinline__ F load_weights(const F* p) {
   if (NT) return __builtin_nontemporal_load(p);
@@ -73,9 +86,8 @@ __device__ __forceinline__ void decode_xa_body(const typename P::elem* __restric
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = bx * 16 + (lane & 15), tok = lane & 15;
   const bool row_ok = row < r, tok_ok = tok < T;
-  const int kw = kchunk >> 2;     // a multiple of KSTEP
-  const int kbeg = by * kchunk + wave * kw;
-  const int kend = min(kbeg + kw, n_i);      // (n_i and kw are multiples of VEC: a 16-byte piece is inside or outside)
+  int kbeg, kend;      // (n_i and a wave's quarter are multiples of VEC: a 16-byte piece is inside or outside)
+  xa_wave_range((int)by, kchunk, wave, n_i, kbeg, kend);
   // Every load is issued, none under a branch: a piece outside the K range or the matrix is fetched from the start of a
   // row that exists, and the TOKEN operand is zeroed instead (its product adds nothing; rows >= r are never stored).
   const int kl = P::VEC * (lane >> 4);
@@ -123,14 +135,11 @@ __device__ __forceinline__ void decode_hb_body(const float* __restrict__ slabs, 
   __shared__ f32x4 red[2][3][64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, tok = lane & 15;
   const bool tok_ok = tok < T;
-  const int ntiles = (n_o + 15) >> 4, nchunks = (r + KC - 1) / KC;
+  const int ntiles = (n_o + 15) >> 4, nchunks = hb_nchunks(r, KC);
 
   // this wave's weights of (tile, chunk): at most DEC_U steps (a quarter of a chunk)
   auto wave_range = [&](int chunk, int& kbeg, int& kend) {
-    const int c0 = chunk * KC, kcv = min(KC, r - c0);
-    const int kw = ((kcv + 3) / 4 + P::KSTEP - 1) / P::KSTEP * P::KSTEP;
-    kbeg = c0 + wave * kw;
-    kend = min(kbeg + kw, c0 + kcv);
+    hb_chunk_wave_range(r, KC, P::KSTEP, chunk, wave, kbeg, kend);
   };
   const int kl = P::VEC * (lane >> 4);
   // (no load under a branch: a piece outside the wave's range is fetched from the row's start and meets a zero token
@@ -235,10 +244,7 @@ struct HbSide {
 template <typename P>
 __device__ __forceinline__ void hb_wave_range(const int r, const int chunk, const int wave, int& kbeg, int& kend) {
   constexpr int KC = DEC_CHUNK_BYTES / (int)sizeof(typename P::elem);
-  const int c0 = chunk * KC, kcv = min(KC, r - c0);
-  const int kw = ((kcv + 3) / 4 + P::KSTEP - 1) / P::KSTEP * P::KSTEP;
-  kbeg = c0 + wave * kw;
-  kend = min(kbeg + kw, c0 + kcv);
+  hb_chunk_wave_range(r, KC, P::KSTEP, chunk, wave, kbeg, kend);
 }
 
 // (no load under a branch: a piece outside the wave's range is fetched from the row's start, rows >= n_o read row 0)

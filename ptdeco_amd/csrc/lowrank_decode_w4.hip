@@ -35,7 +35,6 @@ namespace ptd {
 
 namespace {
 
-constexpr int W4_KC = DEC_CHUNK_BYTES / 2;              // k of one LDS chunk of h (16-bit elements): 32 blocks
 constexpr int W4_CHUNK_BLOCKS = W4_KC / W4_BLOCK;
 
 // the U scale bytes of blocks b .. b + U - 1 of a row of nblk >= U blocks, byte u in bits 8 u + 0..7: one load that
@@ -59,9 +58,8 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_w4_xa_kernel(const unsigne
   const int row = blockIdx.x * 16 + (lane & 15), tok = lane & 15;
   const bool row_ok = row < r, tok_ok = tok < T;
   const int nblk = n_i / W4_BLOCK;
-  const int wave_blocks = (kchunk >> 2) / W4_BLOCK;      // a multiple of four
-  const int wb = (blockIdx.y * (kchunk / W4_BLOCK)) + wave * wave_blocks;
-  const int wend = min(wb + wave_blocks, nblk);
+  int wb, wend;      // the wave's range in blocks: a quarter of kchunk / W4_BLOCK, a multiple of four
+  xa_wave_range((int)blockIdx.y, kchunk / W4_BLOCK, wave, nblk, wb, wend);
   // Every load is issued, none under a branch: a block outside the wave's range is fetched from the start of a row that
   // exists, and the TOKEN operand is zeroed instead (its product adds nothing).
   const unsigned char* wp = A + (int64_t)(row_ok ? row : 0) * lda;
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_w4_hb_kernel(const float* 
   __shared__ f32x4 red[2][3][64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, tok = lane & 15;
   const bool tok_ok = tok < T;
-  const int ntiles = (n_o + 15) >> 4, nchunks = (r + W4_KC - 1) / W4_KC, nblk = r / W4_BLOCK;
+  const int ntiles = (n_o + 15) >> 4, nchunks = hb_nchunks(r, W4_KC), nblk = r / W4_BLOCK;
   // this lane's first block of a chunk: the lane groups of a wave 4 blocks (256 bytes of the image) apart
   const int bc = 16 * (wave >> 1) + 4 * (lane >> 4) + 2 * (wave & 1);
 
@@ -209,16 +207,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_w4_hb_kernel(const float* 
   }
 }
 
-// K slabs of the first product and the K range of one: from (n_i, r) alone (w8_xa_split with this file's load step)
-void w4_xa_split(int64_t n_i, int64_t r, int& nslabs, int& kchunk) {
-  const int64_t row_tiles = ceil_div(r, 16);
-  const int64_t s = std::min<int64_t>(DEC_MAX_SLABS, std::max<int64_t>(1, ceil_div(DEC_XA_TARGET, row_tiles)));
-  const int64_t quantum = 4 * W4_KSTEP;      // four waves, whole blocks per lane group
-  const int64_t kc = (int64_t)align_up((size_t)ceil_div(n_i, s), (size_t)quantum);
-  kchunk = (int)kc;
-  nslabs = (int)ceil_div(n_i, kc);
-}
-
 template <typename EL, bool NT>
 int launch_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea, int64_t ldsa,
               int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o, const void* bias, void* y,
@@ -228,16 +216,14 @@ int launch_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq
   float* slabs = static_cast<float*>(ws);
   const dim3 g1((unsigned)ceil_div(r, 16), (unsigned)nslabs), blk(DEC_THREADS);
   const dim3 g2((unsigned)hb_grid(n_o));
-  // blocks per lane group of a wave's range: one or two are one super-step of that many per lane, three or more go four
-  // at a time (`run` blocks per group mean n_i > 512 (run - 1): a row always holds the U scale bytes of a step)
-  const int run = kchunk / (4 * W4_KSTEP);
-  auto xa = run == 1 ? decode_w4_xa_kernel<EL, NT, 1> : run == 2 ? decode_w4_xa_kernel<EL, NT, 2>
-                                                                 : decode_w4_xa_kernel<EL, NT, 4>;
+  const int ua = w4_xa_blocks(kchunk);
+  auto xa = ua == 1 ? decode_w4_xa_kernel<EL, NT, 1> : ua == 2 ? decode_w4_xa_kernel<EL, NT, 2>
+                                                               : decode_w4_xa_kernel<EL, NT, 4>;
   hipLaunchKernelGGL(xa, g1, blk, 0, st, static_cast<const unsigned short*>(x), ldx, (int)T, (int)n_i,
                      static_cast<const unsigned char*>(Aq), lda, static_cast<const unsigned char*>(ea), ldsa, (int)r, slabs,
                      kchunk);
   PTD_CHECK_LAUNCH("ptd_lowrank_decode_w4 (x Aq^T slabs)");
-  auto hb = r >= 2 * W4_BLOCK ? decode_w4_hb_kernel<EL, NT, 2> : decode_w4_hb_kernel<EL, NT, 1>;
+  auto hb = w4_hb_blocks(r) == 2 ? decode_w4_hb_kernel<EL, NT, 2> : decode_w4_hb_kernel<EL, NT, 1>;
   hipLaunchKernelGGL(hb, g2, blk, 0, st, slabs, nslabs, (int)T, (int)r, static_cast<const unsigned char*>(Bq), ldb,
                      static_cast<const unsigned char*>(eb), ldsb, (int)n_o, static_cast<const unsigned short*>(bias),
                      static_cast<unsigned short*>(y), ldy);

@@ -29,9 +29,6 @@ namespace ptd {
 
 namespace {
 
-constexpr int W8_KC = DEC_CHUNK_BYTES / 2;              // k of one LDS chunk of h (16-bit elements)
-constexpr int W8_HB_U = W8_KC / 4 / W8_KSTEP;           // load steps of a wave's quarter of a chunk (4 x 16 B per lane)
-
 // slab_s[t, i] for the 16 rows i of blockIdx.x and the K range of blockIdx.y; U load steps in flight per lane
 template <typename EL, bool NT, int U>
 __global__ __launch_bounds__(DEC_THREADS) void decode_w8_xa_kernel(const unsigned short* __restrict__ x, const int64_t ldx,
@@ -43,9 +40,8 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_w8_xa_kernel(const unsigne
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 16 + (lane & 15), tok = lane & 15;
   const bool row_ok = row < r, tok_ok = tok < T;
-  const int kw = kchunk >> 2;     // a multiple of W8_KSTEP
-  const int kbeg = blockIdx.y * kchunk + wave * kw;
-  const int kend = min(kbeg + kw, n_i);      // (n_i and kw are multiples of W8_VEC: a 16-byte piece is inside or outside)
+  int kbeg, kend;      // (n_i and a wave's quarter are multiples of W8_VEC: a 16-byte piece is inside or outside)
+  xa_wave_range((int)blockIdx.y, kchunk, wave, n_i, kbeg, kend);
   // Every load is issued, none under a branch: a piece outside the K range is fetched from the start of a row that
   // exists, and the TOKEN operand is zeroed instead (its product adds nothing).
   const int kl = W8_VEC * (lane >> 4);
@@ -98,14 +94,11 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_w8_hb_kernel(const float* 
   __shared__ f32x4 red[2][3][64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, tok = lane & 15;
   const bool tok_ok = tok < T;
-  const int ntiles = (n_o + 15) >> 4, nchunks = (r + W8_KC - 1) / W8_KC;
+  const int ntiles = (n_o + 15) >> 4, nchunks = hb_nchunks(r, W8_KC);
 
   // this wave's weights of (tile, chunk): at most W8_HB_U steps (a quarter of a chunk)
   auto wave_range = [&](int chunk, int& kbeg, int& kend) {
-    const int c0 = chunk * W8_KC, kcv = min(W8_KC, r - c0);
-    const int kw = ((kcv + 3) / 4 + W8_KSTEP - 1) / W8_KSTEP * W8_KSTEP;
-    kbeg = c0 + wave * kw;
-    kend = min(kbeg + kw, c0 + kcv);
+    hb_chunk_wave_range(r, W8_KC, W8_KSTEP, chunk, wave, kbeg, kend);
   };
   const int kl = W8_VEC * (lane >> 4);
   // (no load under a branch: a piece outside the wave's range is fetched from the row's start and meets a zero token
@@ -203,16 +196,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_w8_hb_kernel(const float* 
   }
 }
 
-// K slabs of the first product and the K range of one: from (n_i, r) alone (xa_split with this file's load step)
-void w8_xa_split(int64_t n_i, int64_t r, int& nslabs, int& kchunk) {
-  const int64_t row_tiles = ceil_div(r, 16);
-  const int64_t s = std::min<int64_t>(DEC_MAX_SLABS, std::max<int64_t>(1, ceil_div(DEC_XA_TARGET, row_tiles)));
-  const int64_t quantum = 4 * W8_KSTEP;      // four waves, whole load steps
-  const int64_t kc = (int64_t)align_up((size_t)ceil_div(n_i, s), (size_t)quantum);
-  kchunk = (int)kc;
-  nslabs = (int)ceil_div(n_i, kc);
-}
-
 template <typename EL, bool NT>
 int launch_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const float* sa, int64_t r,
               const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws,
@@ -222,8 +205,7 @@ int launch_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq
   float* slabs = static_cast<float*>(ws);
   const dim3 g1((unsigned)ceil_div(r, 16), (unsigned)nslabs), blk(DEC_THREADS);
   const dim3 g2((unsigned)hb_grid(n_o));
-  // a wave range of at most four load steps keeps four in flight, a longer one DEC_U (the sums and their order are the same)
-  auto xa = kchunk / 4 <= 4 * W8_KSTEP ? decode_w8_xa_kernel<EL, NT, 4> : decode_w8_xa_kernel<EL, NT, DEC_U>;
+  auto xa = w8_xa_steps(kchunk) == 4 ? decode_w8_xa_kernel<EL, NT, 4> : decode_w8_xa_kernel<EL, NT, DEC_U>;
   hipLaunchKernelGGL(xa, g1, blk, 0, st, static_cast<const unsigned short*>(x), ldx, (int)T, (int)n_i,
                      static_cast<const fp8*>(Aq), lda, (int)r, slabs, kchunk);
   PTD_CHECK_LAUNCH("ptd_lowrank_decode_w8 (x Aq^T slabs)");

@@ -28,7 +28,7 @@ constexpr int SK_PIECES = SK_TOK * 4 * (SK_KW / 8) / SK_THREADS;   // 16-byte to
 typedef unsigned short elem;
 
 // K slabs of the first product and the K range of one: from (n_i, r) alone
-inline void xa_split(int64_t n_i, int64_t r, int& nslabs, int& kchunk) {
+inline void sk_xa_split(int64_t n_i, int64_t r, int& nslabs, int& kchunk) {
   const int64_t row_tiles = ceil_div(r, SK_ROWS);
   const int64_t s = std::min<int64_t>(SK_MAX_SLABS, std::max<int64_t>(1, ceil_div(SK_XA_TARGET, row_tiles)));
   const int64_t kc = (int64_t)align_up((size_t)ceil_div(n_i, s), (size_t)SK_QUANTUM);

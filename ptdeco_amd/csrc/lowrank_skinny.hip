@@ -58,7 +58,8 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_product_kernel(const elem* 
   const int tok0 = blockIdx.z * SK_TOK;
 
   // weights: this wave's k range, rows f * 16 + (lane & 15)
-  const int wk0 = kbase + wave * kw, wkend = min(wk0 + kw, kend);
+  int wk0, wkend;
+  xa_wave_range((int)blockIdx.y, kchunk, wave, K, wk0, wkend);
   const int kl = 8 * (lane >> 4);
   const elem* wp[2];
 #pragma unroll
@@ -188,7 +189,7 @@ template <typename EL>
 int launch_skinny(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r, const void* B,
                   int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, hipStream_t st) {
   int nslabs, kchunk;
-  xa_split(n_i, r, nslabs, kchunk);
+  sk_xa_split(n_i, r, nslabs, kchunk);
   float* slabs = static_cast<float*>(ws);
   elem* h = reinterpret_cast<elem*>(static_cast<char*>(ws) + slab_bytes(T, r));
   const unsigned tiles = (unsigned)ceil_div(T, SK_TOK);

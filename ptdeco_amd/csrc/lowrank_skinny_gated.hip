@@ -6,7 +6,7 @@
 //   skinny_gated_hb    g = round(h_g B_g^T + bias_g),  u = round(h_u B_u^T + bias_u),  y = round(round(act(g)) * u)
 //
 // The first two launches are the members' own first products and slab sums laid end to end: gate's workgroups, then
-// up's, each with the coordinates, the xa_split(n_i, r_m) and the region of the workspace that ptd_lowrank_skinny gives
+// up's, each with the coordinates, the sk_xa_split(n_i, r_m) and the region of the workspace that ptd_lowrank_skinny gives
 // the member alone; the member is chosen by one wave-uniform compare of blockIdx.x, the token tile stays in blockIdx.z.
 // In the third a workgroup owns rows 32 b .. 32 b + 31 of B_gate AND of B_up for one token tile: it runs gate's loop over
 // r_g, adds the four waves' sums through LDS in wave order, then up's loop over r_u and its sums, so wave w ends with both
@@ -49,8 +49,7 @@ __device__ __forceinline__ void sk_setup(SkOperands& o, const elem* __restrict__
   o.nsteps = kw / SK_KW;
   const int kbase = by * kchunk;
   const int kend = min(kbase + kchunk, K);            // (K, kchunk multiples of 8: a 16-byte piece is inside or outside)
-  o.wk0 = kbase + wave * kw;
-  o.wkend = min(o.wk0 + kw, kend);
+  xa_wave_range((int)by, kchunk, wave, K, o.wk0, o.wkend);
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
     const int row = bx * SK_ROWS + f * 16 + (lane & 15);
@@ -169,7 +168,7 @@ struct XaSide {
   float* slabs;        // the member's own region of the workspace
   int64_t lda;
   int r;
-  int kchunk;          // xa_split(n_i, r)
+  int kchunk;          // sk_xa_split(n_i, r)
   int row_tiles;       // ceil(r / 32): the member's workgroups per token tile are row_tiles x nslabs, row tile fastest
 };
 
@@ -303,8 +302,8 @@ int launch_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void*
   elem* const h_g = reinterpret_cast<elem*>(ws_g + slab_bytes(T, r_g));
   elem* const h_u = reinterpret_cast<elem*>(ws_u + slab_bytes(T, r_u));
   int ns_g, kc_g, ns_u, kc_u;
-  xa_split(n_i, r_g, ns_g, kc_g);
-  xa_split(n_i, r_u, ns_u, kc_u);
+  sk_xa_split(n_i, r_g, ns_g, kc_g);
+  sk_xa_split(n_i, r_u, ns_u, kc_u);
   const unsigned tiles = (unsigned)ceil_div(T, SK_TOK);
   const dim3 blk(SK_THREADS);
 

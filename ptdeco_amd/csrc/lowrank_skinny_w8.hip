@@ -20,7 +20,7 @@
 // odd lane groups swap the dwords of their weight load the same way (four v_cndmask per load) instead of moving token
 // data between registers.  The order of every sum stays a function of the lane alone.
 //
-// Split, order and rounding.  xa_split / slab_bytes of lowrank_skinny.h as they are: the slab count and every K range
+// Split, order and rounding.  sk_xa_split / slab_bytes of lowrank_skinny.h as they are: the slab count and every K range
 // depend on (n_i, r) alone, never on T, and a column of the MFMA's B operand only reaches the same column of its result,
 // so row t of y is a function of row t of x, bit for bit.  The scales are applied in f32 where the sums are complete
 // (sa in the combine kernel, sb in the second product's epilogue); h and y are rounded once each.  Three plain launches
@@ -63,7 +63,8 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_w8_product_kernel(const ele
   const int tok0 = blockIdx.z * SK_TOK;
 
   // weights: this wave's k range, rows f * 16 + (lane & 15), 16 fp8 per lane and step
-  const int wk0 = kbase + wave * kw, wkend = min(wk0 + kw, kend);
+  int wk0, wkend;
+  xa_wave_range((int)blockIdx.y, kchunk, wave, K, wk0, wkend);
   const int kl = W8_VEC * (lane >> 4);
   const bool swap = (lane >> 4) & 1;
   const fp8* wp[2];
@@ -222,7 +223,7 @@ int launch_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const v
                      int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
                      int64_t ldy, void* ws, hipStream_t st) {
   int nslabs, kchunk;
-  xa_split(n_i, r, nslabs, kchunk);
+  sk_xa_split(n_i, r, nslabs, kchunk);
   float* slabs = static_cast<float*>(ws);
   elem* h = reinterpret_cast<elem*>(static_cast<char*>(ws) + slab_bytes(T, r));
   const unsigned tiles = (unsigned)ceil_div(T, SK_TOK);

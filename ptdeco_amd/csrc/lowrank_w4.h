@@ -5,8 +5,11 @@
 // keeps every product a normal number of bf16 and of f16: the conversion rounds nothing.
 #pragma once
 
+#include <algorithm>
+
 #include "common.h"
 #include "elem16.h"
+#include "lowrank_decode.h"
 
 namespace ptd {
 
@@ -17,7 +20,30 @@ constexpr int W4_BLOCK_BYTES = 16;
 constexpr int W4_KSTEP = 128;       // k of one load of a wave (4 lane groups x one block)
 constexpr unsigned W4_E_MIN = 114, W4_E_MAX = 140;      // the clamp of the semantics: block exponents -13 .. 13
 
+constexpr int W4_KC = DEC_CHUNK_BYTES / 2;      // k of one LDS chunk of h (16-bit elements): 32 blocks
+
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// K slabs of the first product and the K range of one: from (n_i, r) alone (w8_xa_split with this format's load step)
+inline void w4_xa_split(int64_t n_i, int64_t r, int& nslabs, int& kchunk) {
+  const int64_t row_tiles = ceil_div(r, 16);
+  const int64_t s = std::min<int64_t>(DEC_MAX_SLABS, std::max<int64_t>(1, ceil_div(DEC_XA_TARGET, row_tiles)));
+  const int64_t quantum = 4 * W4_KSTEP;      // four waves, whole blocks per lane group
+  const int64_t kc = (int64_t)align_up((size_t)ceil_div(n_i, s), (size_t)quantum);
+  kchunk = (int)kc;
+  nslabs = (int)ceil_div(n_i, kc);
+}
+
+// U of the first product, the consecutive blocks a lane takes per step.  `run` blocks per lane group of a wave's range:
+// one or two are one super-step of that many per lane, three or more go four at a time (`run` blocks per group mean
+// n_i > 512 (run - 1): a row always holds the U scale bytes of a step)
+inline int w4_xa_blocks(int kchunk) {
+  const int run = kchunk / (4 * W4_KSTEP);
+  return run == 1 ? 1 : run == 2 ? 2 : 4;
+}
+
+// U of the second product: 2; 1 only where a row of B is a single block, r = 32
+inline int w4_hb_blocks(int64_t r) { return r >= 2 * W4_BLOCK ? 2 : 1; }
 
 // the scale operand of the conversion for scale byte e: 2^(clamp(e) - 127) as an f32 (the clamp is one v_med3_u32)
 __device__ __forceinline__ float w4_scale(unsigned e) {

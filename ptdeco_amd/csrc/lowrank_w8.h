@@ -4,8 +4,11 @@
 // nothing.
 #pragma once
 
+#include <algorithm>
+
 #include "common.h"
 #include "elem16.h"
+#include "lowrank_decode.h"
 
 namespace ptd {
 
@@ -14,8 +17,25 @@ namespace {
 constexpr int W8_VEC = 16;        // fp8 weights of a 16-byte load
 constexpr int W8_KSTEP = 64;      // k of one load step of a wave (4 lane groups x W8_VEC): two MFMAs
 
+constexpr int W8_KC = DEC_CHUNK_BYTES / 2;              // decode: k of one LDS chunk of h (16-bit elements)
+constexpr int W8_HB_U = W8_KC / 4 / W8_KSTEP;           // ... and the load steps of a wave's quarter of it (4 x 16 B per lane)
+
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned char fp8;
+
+// decode: K slabs of the first product and the K range of one, from (n_i, r) alone (xa_split with this format's load step)
+inline void w8_xa_split(int64_t n_i, int64_t r, int& nslabs, int& kchunk) {
+  const int64_t row_tiles = ceil_div(r, 16);
+  const int64_t s = std::min<int64_t>(DEC_MAX_SLABS, std::max<int64_t>(1, ceil_div(DEC_XA_TARGET, row_tiles)));
+  const int64_t quantum = 4 * W8_KSTEP;      // four waves, whole load steps
+  const int64_t kc = (int64_t)align_up((size_t)ceil_div(n_i, s), (size_t)quantum);
+  kchunk = (int)kc;
+  nslabs = (int)ceil_div(n_i, kc);
+}
+
+// decode: load steps in flight per lane of the first product -- a wave range of at most four load steps keeps four, a
+// longer one DEC_U (the sums and their order are the same)
+inline int w8_xa_steps(int kchunk) { return kchunk / 4 <= 4 * W8_KSTEP ? 4 : DEC_U; }
 
 // two fp8 (the low or the high half of a dword) -> two 16-bit elements, exact
 template <typename EL>
