@@ -686,6 +686,35 @@ int ptd_lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                            static_cast<hipStream_t>(stream));
 }
 
+size_t ptd_lowrank_skinny_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
+  return lowrank_skinny_w4_workspace_bytes(T, n_i, r, dtype);
+}
+
+int ptd_lowrank_skinny_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                          const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                          int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
+                          int dtype, int w_format, void* stream) {
+  PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "ptd_lowrank_skinny_w4: null pointer");
+  // (lda, ldb, ldsa and ldsb in bytes: two codes per byte, one scale byte per 32 weights)
+  PTD_REQUIRE(ldx >= n_i && lda >= n_i / 2 && ldb >= r / 2 && ldsa >= n_i / 32 && ldsb >= r / 32 && ldy >= n_o,
+              "ptd_lowrank_skinny_w4: bad leading dimension");
+  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_skinny_w4: the workspace must be 16-byte aligned");
+  // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
+  if (!lowrank_skinny_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias)) {
+    set_error("ptd_lowrank_skinny_w4: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d w_format=%d: bf16 / f16, "
+              "PTD_W4_MXFP4, 32 <= T <= %d, r >= 32, n_i and r multiples of 32, 8-byte aligned code rows)", (long long)T,
+              (long long)n_i, (long long)r, (long long)n_o, dtype, w_format, PTD_LOWRANK_SKINNY_W4_MAX_T);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  if (ws_bytes < lowrank_skinny_w4_workspace_bytes(T, n_i, r, dtype)) {
+    set_error("ptd_lowrank_skinny_w4: workspace %zu < required %zu bytes", ws_bytes,
+              lowrank_skinny_w4_workspace_bytes(T, n_i, r, dtype));
+    return PTD_ERR_WORKSPACE;
+  }
+  return lowrank_skinny_w4(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
+                           static_cast<hipStream_t>(stream));
+}
+
 int ptd_lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap) {
   PTD_REQUIRE(out, "ptd_lowrank_plan: null pointer");
   PTD_REQUIRE(cap >= PTD_PLAN_LEN, "ptd_lowrank_plan: out holds %d values, the plan has %d", cap, PTD_PLAN_LEN);

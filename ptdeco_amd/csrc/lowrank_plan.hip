@@ -1,7 +1,8 @@
 // ptd_lowrank_plan: what a launch of one serving family of the low-rank pair would do for a shape, computed on the host by
 // the very functions its launcher and its kernels call -- xa_split<P> / w8_xa_split / w4_xa_split / sk_xa_split
 // for the K slabs, hb_grid for the second decode product, xa_wave_range, hb_nchunks and hb_chunk_wave_range for the wave
-// ranges, w8_xa_steps / w4_xa_blocks / w4_hb_blocks for the kernel variant, *_serves for what the family takes.  No
+// ranges, w8_xa_steps / w4_xa_blocks / w4_hb_blocks / w4_sk_scale_bytes for the kernel variant, *_serves for what the
+// family takes.  No
 // device code, no launch, no allocation.  The tests use it to prove which branch combination a shape reaches.
 #include "common.h"
 #include "elem16.h"
@@ -118,6 +119,14 @@ void plan_skinny(int* out, int64_t T, int64_t n_i, int64_t r, int64_t n_o) {
   out[PTD_PLAN_TOKEN_TILES] = tiles;
 }
 
+// lowrank_skinny_w4.hip: the skinny split and grids; the variant of each product is the scale bytes of one load
+void plan_skinny_w4(int* out, int64_t T, int64_t n_i, int64_t r, int64_t n_o) {
+  plan_skinny(out, T, n_i, r, n_o);
+  const int ua = w4_sk_scale_bytes(n_i), ub = w4_sk_scale_bytes(r);
+  out[PTD_PLAN_XA_U] = ua, out[PTD_PLAN_XA_TAIL_BLOCKS] = (int)(n_i / W4_BLOCK % ua);
+  out[PTD_PLAN_HB_U] = ub, out[PTD_PLAN_HB_TAIL_BLOCKS] = (int)(r / W4_BLOCK % ub);
+}
+
 }  // namespace
 
 int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out) {
@@ -152,6 +161,11 @@ int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int
       if (!lowrank_skinny_w8_serves(T, n_i, r, n_o, dtype, PTD_W8_FP8_E4M3, p, n_i, p, n_i, s, p, r, s, p))
         return PTD_ERR_UNSUPPORTED;
       plan_skinny(out, T, n_i, r, n_o);
+      return PTD_OK;
+    case PTD_PLAN_SKINNY_W4:
+      if (!lowrank_skinny_w4_serves(T, n_i, r, n_o, dtype, PTD_W4_MXFP4, p, n_i, p, n_i / 2, p, r / 2, p))
+        return PTD_ERR_UNSUPPORTED;
+      plan_skinny_w4(out, T, n_i, r, n_o);
       return PTD_OK;
   }
   return PTD_ERR_UNSUPPORTED;

@@ -45,6 +45,10 @@ inline int w4_xa_blocks(int kchunk) {
 // U of the second product: 2; 1 only where a row of B is a single block, r = 32
 inline int w4_hb_blocks(int64_t r) { return r >= 2 * W4_BLOCK ? 2 : 1; }
 
+// lowrank_skinny_w4.hip: the scale bytes a lane fetches per 64-k step of a product over rows of k_total weights (n_i in
+// the first product, r in the second) -- the step's two blocks in one load; one only where a row is a single block
+inline int w4_sk_scale_bytes(int64_t k_total) { return k_total >= 2 * W4_BLOCK ? 2 : 1; }
+
 // the scale operand of the conversion for scale byte e: 2^(clamp(e) - 127) as an f32 (the clamp is one v_med3_u32)
 __device__ __forceinline__ float w4_scale(unsigned e) {
   return __builtin_bit_cast(float, min(max(e & 255u, W4_E_MIN), W4_E_MAX) << 23);

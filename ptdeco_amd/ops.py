@@ -792,6 +792,80 @@ def lowrank_skinny_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq:
     return y
 
 
+# The MXFP4 pair of lowrank_decode_w4 at small batches (32 <= T <= _SKINNY_W4_MAX_T tokens) runs on ptd_lowrank_skinny_w4:
+# lowrank_skinny's three launches on packed e2m1 codes and e8m0 block scales, the once-rounded semantics of the decode-w4
+# kernels.  PTD_LOWRANK_SKINNY_W4=0 sends these shapes through the torch expression of
+# torch.ops.ptdeco_amd.lowrank_forward_w4 again.  The cap is a constant of its own (PTD_LOWRANK_SKINNY_W4_MAX_T of the
+# header) and is measured, profiles/pair_skinny_w4.json: the largest T of the probe's list up to which every MXFP4 run
+# beats every run of the expression, by more than the expression's run-to-run spread, in every bf16 cell.
+_SKINNY_W4 = os.environ.get("PTD_LOWRANK_SKINNY_W4", "1") != "0"
+_SKINNY_W4_MAX_T = 96
+
+
+def lowrank_skinny_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                             bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``lowrank_skinny_w4`` takes these operands as they lie (the rule of ptd_lowrank_skinny_w4, without
+    loading the library): real tensors on a ROCm device, x2d bf16 / f16, Aq [r, n_i / 2], ea [r, n_i / 32], Bq
+    [n_o, r / 2] and eb [n_o, r / 32] uint8, _SKINNY_MIN_T <= T <= _SKINNY_W4_MAX_T, r >= 32, n_i and r multiples of 32,
+    code row pitches multiples of 8 bytes, x2d's a multiple of 8 elements, unit inner strides, x2d 16-byte and the codes
+    8-byte aligned (the scale rows need no alignment)."""
+    if not _SKINNY_W4:
+        return False
+    ts = (x2d, Aq, ea, Bq, eb) if bias is None else (x2d, Aq, ea, Bq, eb, bias)
+    for t in ts:
+        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
+            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
+    if any(t.dim() != 2 for t in (x2d, Aq, ea, Bq, eb)) or any(t.dtype != torch.uint8 for t in (Aq, ea, Bq, eb)):
+        return False
+    if x2d.dtype not in (torch.bfloat16, torch.float16):
+        return False
+    (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
+    if not _SKINNY_MIN_T <= T <= _SKINNY_W4_MAX_T or n_o < 1 or r < 32 or n_i < 32 or n_i % 32 or r % 32:
+        return False
+    if n_i >= 1 << 30 or r >= 1 << 27 or n_o >= 1 << 30:
+        return False
+    if (tuple(Aq.shape) != (r, n_i // 2) or tuple(ea.shape) != (r, n_i // 32) or tuple(Bq.shape) != (n_o, r // 2)
+            or tuple(eb.shape) != (n_o, r // 32)):
+        return False
+    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o or bias.dtype != x2d.dtype
+                             or (n_o > 1 and bias.stride(0) != 1)):
+        return False
+    for t, vec, align in ((x2d, 8, 16), (Aq, 8, 8), (Bq, 8, 8)):
+        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % align:
+            return False
+    for e in (ea, eb):
+        if (e.shape[1] > 1 and e.stride(1) != 1) or e.stride(0) < e.shape[1]:
+            return False
+    return True
+
+
+def lowrank_skinny_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                      bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """round(h @ B^^T + bias) with h = round(x2d @ A^^T) for 32 <= T <= _SKINNY_W4_MAX_T rows of x2d (bf16 / f16), A^ and
+    B^ the MXFP4 factors of ``lowrank_decode_w4``: ptd_lowrank_skinny_w4 (sums in f32, each rounded once to x2d's
+    dtype).  Operands the entry does not serve (``lowrank_skinny_w4_serves``) raise; row t of the result depends on row
+    t of x2d alone."""
+    _dev(x2d, Aq, ea, Bq, eb, bias)
+    x2d, Aq, ea, Bq, eb = _rows2d(x2d), _rows2d(Aq), _rows2d(ea), _rows2d(Bq), _rows2d(eb)
+    T, n_i = x2d.shape
+    r, n_o = Aq.shape[0], Bq.shape[0]
+    assert all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)) and n_i % 32 == 0 and r % 32 == 0
+    assert Aq.shape == (r, n_i // 2) and ea.shape == (r, n_i // 32) and Bq.shape == (n_o, r // 2) and eb.shape == (n_o, r // 32)
+    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
+    lib = _hip.load()
+    ws_bytes = lib.ptd_lowrank_skinny_w4_workspace_bytes(T, n_i, r, _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+    if bias is not None:
+        bias = bias.to(x2d.dtype).contiguous()
+    with torch.cuda.device(x2d.device):
+        rc = lib.ptd_lowrank_skinny_w4(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0), ea.data_ptr(),
+                                       ea.stride(0), r, Bq.data_ptr(), Bq.stride(0), eb.data_ptr(), eb.stride(0), n_o,
+                                       _ptr(bias), y.data_ptr(), n_o, ws.data_ptr(), ws_bytes, _code(x2d), W4_MXFP4,
+                                       _stream(x2d))
+    _hip.check(rc, "ptd_lowrank_skinny_w4")
+    return y
+
+
 # The gated pair of an MLP at small batches, act(gate(x)) * up(x), runs on ptd_lowrank_skinny_gated: three launches (both
 # first products, both slab sums, both second products with the activation and the product in the lanes that hold both
 # sums).  g and u are the bits lowrank_skinny gives the members.  No switch or constant of its own: the rule is
