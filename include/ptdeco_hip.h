@@ -47,7 +47,8 @@ extern "C" {
                              *    ptd_lowrank_skinny_w8_workspace_bytes, ptd_lowrank_skinny_w8,
                              *    ptd_lowrank_decode_w4_workspace_bytes, ptd_lowrank_decode_w4,
                              *    ptd_lowrank_plan,
-                             *    ptd_lowrank_skinny_w4_workspace_bytes, ptd_lowrank_skinny_w4) */
+                             *    ptd_lowrank_skinny_w4_workspace_bytes, ptd_lowrank_skinny_w4,
+                             *    ptd_lowrank_decode_w6_workspace_bytes, ptd_lowrank_decode_w6) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -480,6 +481,36 @@ int ptd_lowrank_skinny_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                           const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
                           void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 
+/* The pair at 1 <= T <= 16 tokens with OCP MXFP6 factors, E2M3 elements (weight-only quantisation: 6.25 bits per weight,
+ * 16-bit activations): x [T, n_i], bias [n_o] and y [T, n_o] in dtype D = bf16 or f16; Aq [r, 3 n_i / 4] and
+ * Bq [n_o, 3 r / 4] bytes of packed 6-bit codes, scale_a [r, n_i / 32] and scale_b [n_o, r / 32] bytes of e8m0 block
+ * scales, one per 32 consecutive weights of a row; lda, ldb, ldsa and ldsb in bytes.  Block b of row i is bytes
+ * 24 b .. 24 b + 23 of the row, read as one 192-bit little-endian integer; the code of k = 32 b + j sits at its bits
+ * 6 j .. 6 j + 5:
+ *   code(W, i, k) = (block(W, i, k >> 5) >> (6 * (k & 31))) & 63
+ *   val(c)        = (c & 32 ? -1 : 1) * (E == 0 ? M / 8 : (1 + M / 8) * 2^(E - 1)),   E = (c >> 3) & 3,  M = c & 7
+ *                   (magnitudes 0, 0.125, ..., 7.5)
+ *   W^[i, k]      = val(code(W, i, k)) * 2^(clamp(scale[i, k >> 5], 116, 140) - 127)
+ *   h[t, i] = round_D(sum_k x[t, k] A^[i, k]),   y[t, o] = round_D(sum_i h[t, i] B^[o, i] + bias[o])
+ * with the sums in f32, each rounded ONCE.  The clamp is part of the semantics: a block exponent in [-11, 13] makes every
+ * non-zero W^ a normal number of f16 (2^-3 * 2^-11 = 2^-14, 7.5 * 2^13 = 61440) and of bf16, so the conversion in
+ * registers rounds nothing and the result does not depend on denormal modes.  There are no per-row scales: this is
+ * ptd_lowrank_decode on the dequantised factors, with its rounding points.  Two weight-streaming kernels on the caller's
+ * stream: a lane's 24-byte load is one block, converted to D in registers by one instruction that applies the block
+ * scale; no dequantised copy is kept, and row t of y depends on row t of x alone, bit for bit, whatever T is.  w_format:
+ * PTD_W6_MXFP6_E2M3.  Served: dtype bf16 / f16, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, lda and ldb multiples
+ * of 8 (lda >= 3 n_i / 4, ldb >= 3 r / 4), ldsa >= n_i / 32 and ldsb >= r / 32 (the scale rows need no alignment), ldx a
+ * multiple of 8, x 16-byte aligned, Aq and Bq 8-byte aligned, any n_o >= 1, bias optional.  Anything else (f32, another
+ * w_format) returns PTD_ERR_UNSUPPORTED before a kernel is launched; null pointers, a leading dimension below its row
+ * length or a misaligned workspace PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  The workspace holds the f32
+ * partial sums of the first product's K split, added in a fixed order.  No reference counterpart. */
+#define PTD_W6_MXFP6_E2M3 0
+size_t ptd_lowrank_decode_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int ptd_lowrank_decode_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                          const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
+                          const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
+                          void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+
 /* The gated pair of a decomposed MLP at the same 32 <= T <= 96 tokens in bf16 / f16, y = act(gate(x)) * up(x) (arguments
  * and activations as ptd_lowrank_decode_gated), in three launches on the caller's stream: both first products, both
  * slab sums, then a kernel that forms both second products for the same 32 rows and 64 tokens and applies the activation
@@ -505,7 +536,8 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
  * PTD_PLAN_DECODE_W8, PTD_PLAN_DECODE_W4, PTD_PLAN_SKINNY (ptd_lowrank_skinny; both members of
  * ptd_lowrank_skinny_gated take the plan of that member alone), PTD_PLAN_SKINNY_W8, PTD_PLAN_SKINNY_W4 (xa_u and hb_u:
  * the scale bytes of one load, 1 or 2; the tail fields: blocks of a row % that -- non-zero: the last block's scale byte
- * comes out of the clamped, shifted load).  Writes out[PTD_PLAN_*] for the
+ * comes out of the clamped, shifted load), PTD_PLAN_DECODE_W6 (ptd_lowrank_decode_w6: every field with the meaning
+ * PTD_PLAN_DECODE_W4 gives it, "MXFP4" below read as "MXFP4 and MXFP6").  Writes out[PTD_PLAN_*] for the
  * PTD_PLAN_LEN indices below and returns PTD_PLAN_LEN; PTD_ERR_UNSUPPORTED where the family does not serve the shape or
  * the family is unknown, PTD_ERR_INVALID for a null `out` or cap < PTD_PLAN_LEN.  "First product" is x A^T into K slabs,
  * "second" h B^T.  A wave's "load step" is the k its 64 lanes cover with one 16-byte load each (32 for bf16 / f16, 16 for
@@ -517,6 +549,7 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
 #define PTD_PLAN_SKINNY 3
 #define PTD_PLAN_SKINNY_W8 4
 #define PTD_PLAN_SKINNY_W4 5
+#define PTD_PLAN_DECODE_W6 6
 #define PTD_PLAN_NSLABS 0             /* K slabs of the first product */
 #define PTD_PLAN_KCHUNK 1             /* k of one slab (four wave ranges of kchunk / 4) */
 #define PTD_PLAN_XA_GRID_X 2          /* first product: row tiles, */

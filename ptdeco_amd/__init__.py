@@ -8,7 +8,7 @@ from . import _torch_ops  # noqa: F401  (torch.ops.ptdeco_amd.*: the pair as cus
 from . import dwain  # noqa: F401
 from . import falor  # noqa: F401
 from . import utils  # noqa: F401
-from .lowrank import (LowRankConv1x1, LowRankLinear, LowRankLinearW4, LowRankLinearW8, lowrank_gated, lowrank_group,  # noqa: F401
-                      lowrank_mlp, quantize_pair, quantize_pairs_in_place)
+from .lowrank import (LowRankConv1x1, LowRankLinear, LowRankLinearW4, LowRankLinearW6, LowRankLinearW8,  # noqa: F401
+                      lowrank_gated, lowrank_group, lowrank_mlp, quantize_pair, quantize_pairs_in_place)
 
 __version__ = "0.1.0"

@@ -27,6 +27,11 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
                                                              ops.lowrank_decode_w4_serves (T <= 16), ops.lowrank_skinny_w4
                                                              where ops.lowrank_skinny_w4_serves (32 ... 96), else the
                                                              torch expression on 16-bit copies
+    lowrank_forward_w6(Tensor x2d, Tensor Aq, Tensor ea, Tensor Bq, Tensor eb, Tensor? bias) -> Tensor
+                                                             the pair with OCP MXFP6 (e2m3) factors (packed 6-bit codes,
+                                                             e8m0 block scales): ops.lowrank_decode_w6 where
+                                                             ops.lowrank_decode_w6_serves (T <= 16), else the torch
+                                                             expression on 16-bit copies
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -257,6 +262,84 @@ def _(x2d, Aq, ea, Bq, eb, bias):
     torch._check(tuple(ea.shape) == (r, n_i // W4_BLOCK) and tuple(eb.shape) == (n_o, r // W4_BLOCK),
                  lambda: "lowrank_forward_w4: one scale byte per 32 weights of a row")
     torch._check(bias is None or tuple(bias.shape) == (n_o,), lambda: "lowrank_forward_w4: bias must be [n_o]")
+    return x2d.new_empty((x2d.shape[0], n_o))
+
+
+# e2m3: sign, two exponent bits, three mantissa bits -- with S = c >> 5, E = (c >> 3) & 3, M = c & 7 the value of code c
+# is (-1)^S * (M / 8 if E == 0 else (1 + M / 8) * 2^(E - 1)): magnitudes 0, 0.125, ..., 7.5
+_E2M3 = tuple(m / 8.0 for m in range(8)) + tuple((1.0 + m / 8.0) * 2.0 ** (e - 1) for e in (1, 2, 3) for m in range(8))
+W6_BLOCK = 32                  # weights per e8m0 scale byte, in 24 bytes of codes
+W6_E_MIN, W6_E_MAX = 116, 140  # the clamp of the semantics on a scale byte: block exponents -11 .. 13
+
+
+def lowrank_w6_unpack(q: torch.Tensor) -> torch.Tensor:
+    """The 6-bit codes [rows, cols] (uint8) of packed rows q [rows, 3 cols / 4]: a block of 32 codes is 24 bytes read as
+    one little-endian integer, code j at its bits 6 j .. 6 j + 5 -- so four codes lie in three bytes."""
+    b = q.reshape(q.shape[0], -1, 3)
+    b0, b1, b2 = b[..., 0], b[..., 1], b[..., 2]
+    codes = torch.stack((b0 & 63, (b0 >> 6) | ((b1 & 15) << 2), (b1 >> 4) | ((b2 & 3) << 4), b2 >> 2), dim=-1)
+    return codes.reshape(q.shape[0], -1)
+
+
+def lowrank_w6_pack(codes: torch.Tensor) -> torch.Tensor:
+    """Packed rows [rows, 3 cols / 4] of the 6-bit codes [rows, cols] (uint8, cols a multiple of 4): the inverse of
+    ``lowrank_w6_unpack``."""
+    c = codes.reshape(codes.shape[0], -1, 4)
+    c0, c1, c2, c3 = c[..., 0], c[..., 1], c[..., 2], c[..., 3]
+    packed = torch.stack((c0 | (c1 << 6), (c1 >> 2) | (c2 << 4), (c2 >> 4) | (c3 << 2)), dim=-1)      # (uint8 shifts wrap)
+    return packed.reshape(codes.shape[0], -1).contiguous()
+
+
+def lowrank_w6_dequant(q: torch.Tensor, e: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """The MXFP6 (e2m3) factor W^ [rows, cols] in ``dtype`` from its packed codes q [rows, 3 cols / 4] (uint8: block b
+    of a row is its bytes 24 b .. 24 b + 23 as one little-endian integer, the code of k = 32 b + j at bits
+    6 j .. 6 j + 5) and its block scales e [rows, cols / 32] (uint8, e8m0):
+    W^[i, k] = e2m3(code) * 2^(clamp(e[i, k >> 5], 116, 140) - 127).  Exact in bf16 and in f16: a code has a 4-bit
+    significand and the clamp keeps every non-zero product between 2^-14 and 61440, a normal number of both."""
+    rows, cols = q.shape[0], q.shape[1] // 3 * 4
+    lut = torch.tensor(_E2M3 + tuple(-v for v in _E2M3), dtype=torch.float32, device=q.device)
+    scale = torch.exp2(e.clamp(W6_E_MIN, W6_E_MAX).float() - 127.0)
+    w = lut[lowrank_w6_unpack(q).long()].reshape(rows, cols // W6_BLOCK, W6_BLOCK) * scale[:, :, None]
+    return w.reshape(rows, cols).to(dtype)
+
+
+def lowrank_w6_expression(x: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                          bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The semantics of the MXFP6 pair in torch, D = x.dtype: the 16-bit pair on transient copies of the dequantised
+    factors in D (``lowrank_w6_dequant``, exact), h and y rounded where ``F.linear`` rounds them."""
+    linear = torch.nn.functional.linear
+    h = linear(x, lowrank_w6_dequant(Aq, ea, x.dtype))
+    return linear(h, lowrank_w6_dequant(Bq, eb, x.dtype), bias)
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_w6", mutates_args=())
+def lowrank_forward_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                       bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The pair with OCP MXFP6 (e2m3) factors: x2d [T, n_i] bf16 / f16, Aq [r, 3 n_i / 4] and Bq [n_o, 3 r / 4] packed
+    6-bit codes, ea [r, n_i / 32] and eb [n_o, r / 32] e8m0 block scales (all uint8), bias [n_o] of x2d's dtype or None;
+    y [T, n_o] contiguous, y = round(h B^^T + bias) with h = round(x2d A^^T).  At decode shapes (1 <= T <= 16, aligned
+    operands: ops.lowrank_decode_w6_serves) on the weight-streaming kernels of ptd_lowrank_decode_w6; elsewhere
+    ``lowrank_w6_expression``: torch's products on transient 16-bit copies of the factors.  Inference only: no autograd
+    formula."""
+    if ops.lowrank_decode_w6_serves(x2d, Aq, ea, Bq, eb, bias):
+        return ops.lowrank_decode_w6(x2d, Aq, ea, Bq, eb, bias)
+    return lowrank_w6_expression(x2d, Aq, ea, Bq, eb, bias).contiguous()
+
+
+@lowrank_forward_w6.register_fake
+def _(x2d, Aq, ea, Bq, eb, bias):
+    torch._check(x2d.dim() == 2 and Aq.dim() == 2 and ea.dim() == 2 and Bq.dim() == 2 and eb.dim() == 2,
+                 lambda: "lowrank_forward_w6: 2-D operands")
+    torch._check(all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)),
+                 lambda: "lowrank_forward_w6: the codes and the block scales must be uint8")
+    torch._check(x2d.dtype in (torch.bfloat16, torch.float16), lambda: "lowrank_forward_w6: x2d must be bfloat16 or float16")
+    n_i, r, n_o = x2d.shape[1], Aq.shape[0], Bq.shape[0]
+    torch._check(n_i % W6_BLOCK == 0 and r % W6_BLOCK == 0, lambda: "lowrank_forward_w6: n_i and r must be multiples of 32")
+    torch._check(tuple(Aq.shape) == (r, 3 * n_i // 4) and tuple(Bq.shape) == (n_o, 3 * r // 4),
+                 lambda: "lowrank_forward_w6: shape mismatch (Aq [r, 3 n_i / 4], Bq [n_o, 3 r / 4])")
+    torch._check(tuple(ea.shape) == (r, n_i // W6_BLOCK) and tuple(eb.shape) == (n_o, r // W6_BLOCK),
+                 lambda: "lowrank_forward_w6: one scale byte per 32 weights of a row")
+    torch._check(bias is None or tuple(bias.shape) == (n_o,), lambda: "lowrank_forward_w6: bias must be [n_o]")
     return x2d.new_empty((x2d.shape[0], n_o))
 
 

@@ -563,6 +563,35 @@ int ptd_lowrank_decode_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                            static_cast<hipStream_t>(stream));
 }
 
+size_t ptd_lowrank_decode_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
+  return lowrank_decode_w6_workspace_bytes(T, n_i, r, dtype);
+}
+
+int ptd_lowrank_decode_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                          const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                          int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
+                          int dtype, int w_format, void* stream) {
+  PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "ptd_lowrank_decode_w6: null pointer");
+  // (lda, ldb, ldsa and ldsb in bytes: four codes per three bytes, one scale byte per 32 weights)
+  PTD_REQUIRE(ldx >= n_i && lda >= 3 * (n_i / 4) && ldb >= 3 * (r / 4) && ldsa >= n_i / 32 && ldsb >= r / 32 && ldy >= n_o,
+              "ptd_lowrank_decode_w6: bad leading dimension");
+  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_decode_w6: the workspace must be 16-byte aligned");
+  // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
+  if (!lowrank_decode_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias)) {
+    set_error("ptd_lowrank_decode_w6: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d w_format=%d: bf16 / f16, "
+              "PTD_W6_MXFP6_E2M3, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, 8-byte aligned rows)", (long long)T,
+              (long long)n_i, (long long)r, (long long)n_o, dtype, w_format);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  if (ws_bytes < lowrank_decode_w6_workspace_bytes(T, n_i, r, dtype)) {
+    set_error("ptd_lowrank_decode_w6: workspace %zu < required %zu bytes", ws_bytes,
+              lowrank_decode_w6_workspace_bytes(T, n_i, r, dtype));
+    return PTD_ERR_WORKSPACE;
+  }
+  return lowrank_decode_w6(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
+                           static_cast<hipStream_t>(stream));
+}
+
 size_t ptd_lowrank_decode_group_workspace_bytes(int count, int64_t T, int64_t n_i, const int64_t* r, int dtype) {
   if (!r || count < 1 || count > PTD_LOWRANK_GROUP_MAX) return 0;
   return lowrank_decode_group_workspace_bytes(count, T, n_i, r, dtype);

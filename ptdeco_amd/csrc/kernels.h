@@ -73,6 +73,15 @@ int lowrank_decode_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const 
                       int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
                       const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_decode_w6.hip: the same pair with OCP MXFP6 factors (e2m3 codes, 24 bytes per block of 32, one e8m0 scale byte per
+// block), bf16 / f16 activations (ptd_lowrank_decode_w6): a lane's 24-byte load is one block, converted by one instruction
+bool lowrank_decode_w6_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
+                              int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias);
+size_t lowrank_decode_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int lowrank_decode_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea,
+                      int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
+                      const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
+
 // lowrank_group.hip: 1 .. PTD_LOWRANK_GROUP_MAX pairs on one input at decode shapes in two launches (ptd_lowrank_decode_group);
 // every member's bits are lowrank_decode's on that member alone
 bool lowrank_decode_group_serves(int count, int64_t T, int64_t n_i, const int64_t* r, const int64_t* n_o, int dtype,

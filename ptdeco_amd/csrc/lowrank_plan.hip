@@ -1,7 +1,7 @@
 // ptd_lowrank_plan: what a launch of one serving family of the low-rank pair would do for a shape, computed on the host by
-// the very functions its launcher and its kernels call -- xa_split<P> / w8_xa_split / w4_xa_split / sk_xa_split
+// the very functions its launcher and its kernels call -- xa_split<P> / w8_xa_split / w4_xa_split / w6_xa_split / sk_xa_split
 // for the K slabs, hb_grid for the second decode product, xa_wave_range, hb_nchunks and hb_chunk_wave_range for the wave
-// ranges, w8_xa_steps / w4_xa_blocks / w4_hb_blocks / w4_sk_scale_bytes for the kernel variant, *_serves for what the
+// ranges, w8_xa_steps / w4_xa_blocks / w4_hb_blocks / w6_xa_blocks / w6_hb_blocks / w4_sk_scale_bytes for the kernel variant, *_serves for what the
 // family takes.  No
 // device code, no launch, no allocation.  The tests use it to prove which branch combination a shape reaches.
 #include "common.h"
@@ -10,6 +10,7 @@
 #include "lowrank_decode.h"
 #include "lowrank_skinny.h"
 #include "lowrank_w4.h"
+#include "lowrank_w6.h"
 #include "lowrank_w8.h"
 
 namespace ptd {
@@ -95,6 +96,22 @@ void plan_decode_w4(int* out, int64_t n_i, int64_t r, int64_t n_o) {
   out[PTD_PLAN_HB_U] = ub, out[PTD_PLAN_HB_TAIL_BLOCKS] = (int)(r / W4_BLOCK % ub);
 }
 
+// lowrank_decode_w6.hip: the fields of plan_decode_w4, from this format's rules
+void plan_decode_w6(int* out, int64_t n_i, int64_t r, int64_t n_o) {
+  int nslabs, kchunk;
+  int asked, unused;
+  w6_xa_split(PLAN_LONG_ROW, r, asked, unused);
+  out[PTD_PLAN_SLABS_ASKED] = asked;
+  w6_xa_split(n_i, r, nslabs, kchunk);
+  out[PTD_PLAN_NSLABS] = nslabs, out[PTD_PLAN_KCHUNK] = kchunk;
+  out[PTD_PLAN_XA_GRID_X] = (int)ceil_div(r, 16), out[PTD_PLAN_XA_GRID_Y] = nslabs, out[PTD_PLAN_XA_GRID_Z] = 1;
+  xa_waves(out, nslabs, kchunk, (int)n_i, W6_KSTEP);
+  const int ua = w6_xa_blocks(kchunk), ub = w6_hb_blocks(r);
+  out[PTD_PLAN_XA_U] = ua, out[PTD_PLAN_XA_TAIL_BLOCKS] = (int)(n_i / W6_BLOCK % ua);
+  hb_decode(out, r, n_o, W6_KC);
+  out[PTD_PLAN_HB_U] = ub, out[PTD_PLAN_HB_TAIL_BLOCKS] = (int)(r / W6_BLOCK % ub);
+}
+
 // lowrank_skinny.hip and lowrank_skinny_w8.hip: one split, one grid rule
 void plan_skinny(int* out, int64_t T, int64_t n_i, int64_t r, int64_t n_o) {
   int nslabs, kchunk;
@@ -152,6 +169,11 @@ int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int
       if (!lowrank_decode_w4_serves(T, n_i, r, n_o, dtype, PTD_W4_MXFP4, p, n_i, p, n_i / 2, p, r / 2, p))
         return PTD_ERR_UNSUPPORTED;
       plan_decode_w4(out, n_i, r, n_o);
+      return PTD_OK;
+    case PTD_PLAN_DECODE_W6:
+      if (!lowrank_decode_w6_serves(T, n_i, r, n_o, dtype, PTD_W6_MXFP6_E2M3, p, n_i, p, 3 * (n_i / 4), p, 3 * (r / 4), p))
+        return PTD_ERR_UNSUPPORTED;
+      plan_decode_w6(out, n_i, r, n_o);
       return PTD_OK;
     case PTD_PLAN_SKINNY:
       if (!lowrank_skinny_serves(T, n_i, r, n_o, dtype, p, n_i, p, n_i, p, r)) return PTD_ERR_UNSUPPORTED;

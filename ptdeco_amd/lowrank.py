@@ -27,6 +27,7 @@ _lowrank_forward_group = torch.ops.ptdeco_amd.lowrank_forward_group.default
 _lowrank_forward_gated = torch.ops.ptdeco_amd.lowrank_forward_gated.default
 _lowrank_forward_w8 = torch.ops.ptdeco_amd.lowrank_forward_w8.default
 _lowrank_forward_w4 = torch.ops.ptdeco_amd.lowrank_forward_w4.default
+_lowrank_forward_w6 = torch.ops.ptdeco_amd.lowrank_forward_w6.default
 
 logger = logging.getLogger(__name__)
 
@@ -156,7 +157,9 @@ class LowRankLinearW8(torch.nn.Module):
 
 _W4_FORMAT = "mxfp4"
 _W4_BLOCK = _torch_ops.W4_BLOCK
-_QUANT_FORMATS = tuple(_W8_FORMATS) + (_W4_FORMAT,)
+_W6_FORMAT = "mxfp6_e2m3"
+_W6_BLOCK = _torch_ops.W6_BLOCK
+_QUANT_FORMATS = tuple(_W8_FORMATS) + (_W4_FORMAT, _W6_FORMAT)
 
 
 class LowRankLinearW4(torch.nn.Module):
@@ -238,6 +241,85 @@ class LowRankLinearW4(torch.nn.Module):
         return y.reshape(*x.shape[:-1], self.out_features)
 
 
+class LowRankLinearW6(torch.nn.Module):
+    """A rank-r pair with OCP MXFP6 factors, e2m3 elements (weight-only quantisation, 6.25 bits per weight):
+    ``weight_a_q`` [rank, 3 in_features / 4] and ``weight_b_q`` [out_features, 3 rank / 4] hold packed 6-bit codes (a
+    block of 32 codes is 24 bytes read as one little-endian integer, the code of k = 32 b + j at its bits
+    6 j .. 6 j + 5), ``scale_a`` [rank, in_features / 32] and ``scale_b`` [out_features, rank / 32] one e8m0 scale byte
+    per 32 consecutive weights of a row, and ``bias`` [out_features] is in the activation dtype (bf16 or f16) or None --
+    all buffers: the module is inference-only and has no trainable parameters.  The codes and the scales are plain
+    ``torch.uint8`` (it moves, saves and loads everywhere).  With D the activation dtype and
+    W^[i, k] = e2m3(code) * 2^(clamp(scale[i, k >> 5], 116, 140) - 127) (``_torch_ops.lowrank_w6_dequant``; the clamp
+    is part of the semantics and makes every W^ exact in D),
+
+        h = round_D(x A^^T)        y = round_D(h B^^T + bias)
+
+    ``in_features`` and ``rank`` are multiples of 32; ``rank`` is the STORED rank: ``quantize_pair`` pads a pair whose
+    rank is not a multiple of 32 with zero rows of A and zero columns of B (scale byte 127), which changes no result.
+
+    On a ROCm device, for x of the module's dtype and no gradient wanted, ``forward`` calls
+    ``torch.ops.ptdeco_amd.lowrank_forward_w6``: at 1 to 16 tokens the HIP kernels of ptd_lowrank_decode_w6 (0.39 of
+    the factor bytes of the 16-bit pair, 0.78 of the fp8 pair's, converted in registers), at any other token count the
+    torch expression on transient 16-bit copies of the factors.  Anything else (a CPU copy, another input dtype,
+    ``x.requires_grad``) evaluates that expression directly and says so once, at WARNING.  The format keeps fp8's three
+    mantissa bits: round to nearest gives a noise-to-signal ratio of about 1.6e-3 on Gaussian factors, fp8's class
+    (1.3 .. 1.5e-3) and a sixteenth of MXFP4's.  ``.to(device)`` moves the module; a dtype cast (``.half()``,
+    ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the packed buffers as they are.
+    Built by ``quantize_pair`` / ``quantize_pairs_in_place`` with ``"mxfp6_e2m3"``, or empty for ``load_state_dict``."""
+
+    def __init__(self, in_features: int, rank: int, out_features: int, bias: bool = True,
+                 dtype: torch.dtype = torch.bfloat16, device=None) -> None:
+        super().__init__()
+        if dtype not in _W8_DTYPES:
+            raise ValueError(f"LowRankLinearW6: the activation dtype must be bfloat16 or float16, got {dtype}")
+        if in_features % _W6_BLOCK or rank % _W6_BLOCK or rank < _W6_BLOCK or in_features < _W6_BLOCK:
+            raise ValueError(f"LowRankLinearW6: in_features and rank must be positive multiples of {_W6_BLOCK}, got "
+                             f"{in_features} and {rank}")
+        self.in_features, self.rank, self.out_features = int(in_features), int(rank), int(out_features)
+        self._dtype = dtype
+
+        def zeros(rows, cols, fill=0):
+            return torch.full((rows, cols), fill, dtype=torch.uint8, device=device)
+
+        self.register_buffer("weight_a_q", zeros(rank, 3 * in_features // 4))
+        self.register_buffer("scale_a", zeros(rank, in_features // _W6_BLOCK, 127))
+        self.register_buffer("weight_b_q", zeros(out_features, 3 * rank // 4))
+        self.register_buffer("scale_b", zeros(out_features, rank // _W6_BLOCK, 127))
+        self.register_buffer("bias", torch.zeros(out_features, dtype=dtype, device=device) if bias else None)
+
+    @property
+    def dtype(self) -> torch.dtype:
+        """The activation dtype D: what x must be for the HIP kernels, and what the bias is held in."""
+        return self._dtype
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)      # (a dtype cast leaves integer buffers alone: the packed bytes stay)
+        cast = fn(torch.empty(0, dtype=self._dtype)).dtype
+        if cast in _W8_DTYPES:
+            self._dtype = cast
+        if self.bias is not None and self.bias.dtype != self._dtype:
+            self._buffers["bias"] = self.bias.to(self._dtype)
+        return self
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, rank={self.rank}, out_features={self.out_features}, "
+                f"bias={self.bias is not None}, dtype={self._dtype}")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        operands = (self.weight_a_q, self.scale_a, self.weight_b_q, self.scale_b, self.bias)
+        wants_grad = torch.is_grad_enabled() and x.requires_grad
+        if not (x.is_cuda and x.dtype == self._dtype and not wants_grad):
+            why = ("a gradient with respect to x" if x.is_cuda and x.dtype == self._dtype else
+                   "a CPU tensor" if not x.is_cuda else f"input dtype {x.dtype} with activation dtype {self._dtype}")
+            warn_once(f"LowRankLinearW6:{why}", f"ptdeco_amd.LowRankLinearW6: {why} is not served by the HIP MXFP6 kernels "
+                                                "(bf16 / f16 inference on a ROCm device); evaluating the torch expression "
+                                                "on 16-bit copies of the factors instead")
+            return _torch_ops.lowrank_w6_expression(x, *operands)
+        x2d = x.reshape(-1, self.in_features)
+        y = _lowrank_forward_w6(x2d, *operands)
+        return y.reshape(*x.shape[:-1], self.out_features)
+
+
 def _quantize_rows(w: torch.Tensor, qdtype: torch.dtype, qmax: float):
     """Per row of w: s = amax|w| / qmax in f32 (1 for a row of zeros), q = clamp(w / s, -qmax, qmax) in qdtype."""
     wf = w.detach().float()
@@ -286,19 +368,66 @@ def _quantize_mxfp4(w: torch.Tensor):
     return packed.contiguous(), (e + 127).to(torch.uint8).contiguous()
 
 
-def _quantize_pair_mxfp4(first, second, dtype) -> LowRankLinearW4:
+# 8 |v| for the e2m3 magnitudes v = 0, 0.125, ..., 7.5 -> the five low bits of the code
+_E2M3_CODE_OF_8X = [0] * 61
+for _code, _value in enumerate(_torch_ops._E2M3):
+    _E2M3_CODE_OF_8X[int(_value * 8)] = _code
+
+
+def _quantize_mxfp6_e2m3(w: torch.Tensor):
+    """w [rows, cols] (cols a multiple of 32) as OCP MXFP6 with e2m3 elements: per block of 32 consecutive weights of a
+    row the exponent e = clamp(floor(log2 amax) - 2, -11, 13) (the OCP rule with the element's emax of 2; 0 for a block
+    of zeros), stored as the byte e + 127, and per weight the e2m3 code nearest to w / 2^e, ties to the even code,
+    saturating at +-7.5; a block's 32 codes packed into 24 bytes, code j at bits 6 j .. 6 j + 5 of the block read as
+    one little-endian integer.  Where e is not clamped, |w - w^| <= amax_block / 8: 2^(e + 2) <= amax < 2^(e + 3), so
+    amax >= 4 * 2^e; the grid's widest step is 0.5 * 2^e (a rounding error of at most 0.25 * 2^e <= amax / 16), and a
+    weight beyond 7.5 * 2^e errs by less than 8 * 2^e - 7.5 * 2^e = 0.5 * 2^e <= amax / 8.  Returns
+    (codes [rows, 3 cols / 4], scales [rows, cols / 32]), uint8."""
+    rows, cols = w.shape
+    if cols % _W6_BLOCK:
+        raise ValueError(f"quantize_pair: mxfp6_e2m3 needs rows of a multiple of {_W6_BLOCK} weights, got {cols}")
+    blocks = w.detach().float().reshape(rows, cols // _W6_BLOCK, _W6_BLOCK)
+    amax = blocks.abs().amax(dim=-1)
+    if not bool(torch.isfinite(amax).all()):
+        raise ValueError("quantize_pair: the factors hold non-finite values")
+    if bool((amax >= 2.0 ** 16).any()):
+        raise ValueError("quantize_pair: a block of 32 weights reaches 2^16, beyond what mxfp6_e2m3 with block exponents "
+                         "up to 13 represents")
+    _, exponent = torch.frexp(amax)          # amax = m 2^exponent with 0.5 <= m < 1: floor(log2 amax) = exponent - 1
+    e = torch.where(amax > 0, (exponent - 3).clamp(-11, 13), torch.zeros_like(exponent))
+    v = torch.ldexp(blocks, -e[:, :, None])  # exact
+    a = v.abs().clamp(max=7.5)
+    # round to nearest, ties to even, on the grid's three step sizes (.125 below 2, .25 below 4, .5 up to 7.5):
+    # torch.round is ties-to-even, and an even multiple of the step is a code with an even mantissa
+    a = torch.where(a < 2.0, torch.round(a * 8.0) / 8.0, torch.where(a < 4.0, torch.round(a * 4.0) / 4.0,
+                                                                     torch.round(a * 2.0) / 2.0))
+    table = torch.tensor(_E2M3_CODE_OF_8X, dtype=torch.uint8, device=w.device)
+    codes = table[(a * 8.0).long()]
+    codes = codes | (((v < 0) & (a > 0)).to(torch.uint8) << 5)
+    return _torch_ops.lowrank_w6_pack(codes.reshape(rows, cols)), (e + 127).to(torch.uint8).contiguous()
+
+
+def _quantize_pair_mx(first, second, dtype, cls, quantize, name):
     n_i, r, n_o = first.in_features, first.out_features, second.out_features
     if n_i % _W4_BLOCK:
-        raise ValueError(f"quantize_pair: mxfp4 needs in_features to be a multiple of {_W4_BLOCK}, got {n_i}")
+        raise ValueError(f"quantize_pair: {name} needs in_features to be a multiple of {_W4_BLOCK}, got {n_i}")
     stored = -(-r // _W4_BLOCK) * _W4_BLOCK      # zero rows of A and zero columns of B up to a whole block: no result changes
     wa, wb = first.weight.detach(), second.weight.detach()
     if stored != r:
         wa = torch.cat([wa, wa.new_zeros(stored - r, n_i)], 0)
         wb = torch.cat([wb, wb.new_zeros(n_o, stored - r)], 1)
-    out = LowRankLinearW4(n_i, stored, n_o, bias=second.bias is not None, dtype=dtype, device=first.weight.device)
-    out.weight_a_q, out.scale_a = _quantize_mxfp4(wa)
-    out.weight_b_q, out.scale_b = _quantize_mxfp4(wb)
+    out = cls(n_i, stored, n_o, bias=second.bias is not None, dtype=dtype, device=first.weight.device)
+    out.weight_a_q, out.scale_a = quantize(wa)
+    out.weight_b_q, out.scale_b = quantize(wb)
     return out
+
+
+def _quantize_pair_mxfp4(first, second, dtype) -> LowRankLinearW4:
+    return _quantize_pair_mx(first, second, dtype, LowRankLinearW4, _quantize_mxfp4, "mxfp4")
+
+
+def _quantize_pair_mxfp6(first, second, dtype) -> LowRankLinearW6:
+    return _quantize_pair_mx(first, second, dtype, LowRankLinearW6, _quantize_mxfp6_e2m3, "mxfp6_e2m3")
 
 
 def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3"):
@@ -307,8 +436,10 @@ def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3"):
     element satisfies |w - s q| <= max(2^-4 |w|, 2^-10 s).  With ``fmt="mxfp4"`` a ``LowRankLinearW4`` instead: OCP MXFP4
     blocks of 32 weights (``_quantize_mxfp4``: |w - w^| <= amax_block / 4 where the block exponent is not clamped),
     in_features a multiple of 32, the rank zero-padded to one; about a quarter of the 16-bit pair's bytes at a
-    noise-to-signal ratio near 2.5e-2 on Gaussian factors, so a format to choose layer by layer.  The pair itself is
-    not modified."""
+    noise-to-signal ratio near 2.5e-2 on Gaussian factors, so a format to choose layer by layer.  With
+    ``fmt="mxfp6_e2m3"`` a ``LowRankLinearW6``: OCP MXFP6 blocks of 32 e2m3 weights (``_quantize_mxfp6_e2m3``:
+    |w - w^| <= amax_block / 8 where the block exponent is not clamped), the same shape rules, 0.39 of the 16-bit pair's
+    bytes at a noise-to-signal ratio near 1.6e-3, fp8's class.  The pair itself is not modified."""
     if fmt not in _QUANT_FORMATS:
         raise ValueError(f"quantize_pair: fmt must be one of {sorted(_QUANT_FORMATS)}, got {fmt!r}")
     if not isinstance(pair, LowRankLinear):
@@ -317,9 +448,9 @@ def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3"):
     dtype = first.weight.dtype
     if dtype not in _W8_DTYPES or second.weight.dtype != dtype:
         raise ValueError(f"quantize_pair: the pair's weights must be bfloat16 or float16 (got {dtype} / "
-                         f"{second.weight.dtype}); cast the model first -- the fp8 and mxfp4 kernels take 16-bit activations")
-    if fmt == _W4_FORMAT:
-        out = _quantize_pair_mxfp4(first, second, dtype)
+                         f"{second.weight.dtype}); cast the model first -- the fp8, mxfp4 and mxfp6 kernels take 16-bit activations")
+    if fmt in (_W4_FORMAT, _W6_FORMAT):
+        out = (_quantize_pair_mxfp4 if fmt == _W4_FORMAT else _quantize_pair_mxfp6)(first, second, dtype)
         if second.bias is not None:
             out.bias = second.bias.detach().to(dtype).clone()
         return out.train(pair.training)
@@ -335,7 +466,7 @@ def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3"):
 
 def quantize_pairs_in_place(model: torch.nn.Module, fmt: str = "fp8_e4m3", names=None) -> list:
     """Replace the installed ``LowRankLinear`` modules of ``model`` whose weights are bf16 or f16 -- all of them, or
-    those listed in ``names`` -- by their ``quantize_pair`` in ``fmt`` ("fp8_e4m3" or "mxfp4"); returns the replaced
+    those listed in ``names`` -- by their ``quantize_pair`` in ``fmt`` ("fp8_e4m3", "mxfp4" or "mxfp6_e2m3"); returns the replaced
     names in module order.  To be applied
     after ``apply_decompose_config_in_place`` and ``load_state_dict`` (the config and the 16-bit state dict describe
     the unquantised pairs).  ``LowRankConv1x1``, ``nn.Linear`` and everything else stay as they are; a name in ``names``
