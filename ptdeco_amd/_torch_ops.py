@@ -209,6 +209,32 @@ W4_BLOCK = 32                  # weights per e8m0 scale byte
 W4_E_MIN, W4_E_MAX = 114, 140  # the clamp of the semantics on a scale byte: block exponents -13 .. 13
 
 
+def _mx_expression(dequant, x, Aq, ea, Bq, eb, bias):
+    """The 16-bit pair on transient copies of the factors dequantised by ``dequant`` to D = x.dtype, h and y rounded
+    where ``F.linear`` rounds them."""
+    linear = torch.nn.functional.linear
+    h = linear(x, dequant(Aq, ea, x.dtype))
+    return linear(h, dequant(Bq, eb, x.dtype), bias)
+
+
+def _mx_fake(op, code_cols, shapes, x2d, Aq, ea, Bq, eb, bias):
+    """What the fake kernel of MX op ``op`` checks (``code_cols(n)`` code bytes per row of n weights; ``shapes`` says so
+    in the message) and returns."""
+    torch._check(x2d.dim() == 2 and Aq.dim() == 2 and ea.dim() == 2 and Bq.dim() == 2 and eb.dim() == 2,
+                 lambda: f"{op}: 2-D operands")
+    torch._check(all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)),
+                 lambda: f"{op}: the codes and the block scales must be uint8")
+    torch._check(x2d.dtype in (torch.bfloat16, torch.float16), lambda: f"{op}: x2d must be bfloat16 or float16")
+    n_i, r, n_o = x2d.shape[1], Aq.shape[0], Bq.shape[0]
+    torch._check(n_i % W4_BLOCK == 0 and r % W4_BLOCK == 0, lambda: f"{op}: n_i and r must be multiples of 32")
+    torch._check(tuple(Aq.shape) == (r, code_cols(n_i)) and tuple(Bq.shape) == (n_o, code_cols(r)),
+                 lambda: f"{op}: shape mismatch ({shapes})")
+    torch._check(tuple(ea.shape) == (r, n_i // W4_BLOCK) and tuple(eb.shape) == (n_o, r // W4_BLOCK),
+                 lambda: f"{op}: one scale byte per 32 weights of a row")
+    torch._check(bias is None or tuple(bias.shape) == (n_o,), lambda: f"{op}: bias must be [n_o]")
+    return x2d.new_empty((x2d.shape[0], n_o))
+
+
 def lowrank_w4_dequant(q: torch.Tensor, e: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     """The MXFP4 factor W^ [rows, cols] in ``dtype`` from its packed codes q [rows, cols / 2] (uint8, the low nibble
     the even k) and its block scales e [rows, cols / 32] (uint8, e8m0):
@@ -226,9 +252,7 @@ def lowrank_w4_expression(x: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, B
                           bias: Optional[torch.Tensor]) -> torch.Tensor:
     """The semantics of the MXFP4 pair in torch, D = x.dtype: the 16-bit pair on transient copies of the dequantised
     factors in D (``lowrank_w4_dequant``, exact), h and y rounded where ``F.linear`` rounds them."""
-    linear = torch.nn.functional.linear
-    h = linear(x, lowrank_w4_dequant(Aq, ea, x.dtype))
-    return linear(h, lowrank_w4_dequant(Bq, eb, x.dtype), bias)
+    return _mx_expression(lowrank_w4_dequant, x, Aq, ea, Bq, eb, bias)
 
 
 @torch.library.custom_op("ptdeco_amd::lowrank_forward_w4", mutates_args=())
@@ -250,19 +274,7 @@ def lowrank_forward_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq
 
 @lowrank_forward_w4.register_fake
 def _(x2d, Aq, ea, Bq, eb, bias):
-    torch._check(x2d.dim() == 2 and Aq.dim() == 2 and ea.dim() == 2 and Bq.dim() == 2 and eb.dim() == 2,
-                 lambda: "lowrank_forward_w4: 2-D operands")
-    torch._check(all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)),
-                 lambda: "lowrank_forward_w4: the codes and the block scales must be uint8")
-    torch._check(x2d.dtype in (torch.bfloat16, torch.float16), lambda: "lowrank_forward_w4: x2d must be bfloat16 or float16")
-    n_i, r, n_o = x2d.shape[1], Aq.shape[0], Bq.shape[0]
-    torch._check(n_i % W4_BLOCK == 0 and r % W4_BLOCK == 0, lambda: "lowrank_forward_w4: n_i and r must be multiples of 32")
-    torch._check(tuple(Aq.shape) == (r, n_i // 2) and tuple(Bq.shape) == (n_o, r // 2),
-                 lambda: "lowrank_forward_w4: shape mismatch (Aq [r, n_i / 2], Bq [n_o, r / 2])")
-    torch._check(tuple(ea.shape) == (r, n_i // W4_BLOCK) and tuple(eb.shape) == (n_o, r // W4_BLOCK),
-                 lambda: "lowrank_forward_w4: one scale byte per 32 weights of a row")
-    torch._check(bias is None or tuple(bias.shape) == (n_o,), lambda: "lowrank_forward_w4: bias must be [n_o]")
-    return x2d.new_empty((x2d.shape[0], n_o))
+    return _mx_fake("lowrank_forward_w4", lambda n: n // 2, "Aq [r, n_i / 2], Bq [n_o, r / 2]", x2d, Aq, ea, Bq, eb, bias)
 
 
 # e2m3: sign, two exponent bits, three mantissa bits -- with S = c >> 5, E = (c >> 3) & 3, M = c & 7 the value of code c
@@ -307,9 +319,7 @@ def lowrank_w6_expression(x: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, B
                           bias: Optional[torch.Tensor]) -> torch.Tensor:
     """The semantics of the MXFP6 pair in torch, D = x.dtype: the 16-bit pair on transient copies of the dequantised
     factors in D (``lowrank_w6_dequant``, exact), h and y rounded where ``F.linear`` rounds them."""
-    linear = torch.nn.functional.linear
-    h = linear(x, lowrank_w6_dequant(Aq, ea, x.dtype))
-    return linear(h, lowrank_w6_dequant(Bq, eb, x.dtype), bias)
+    return _mx_expression(lowrank_w6_dequant, x, Aq, ea, Bq, eb, bias)
 
 
 @torch.library.custom_op("ptdeco_amd::lowrank_forward_w6", mutates_args=())
@@ -328,19 +338,8 @@ def lowrank_forward_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq
 
 @lowrank_forward_w6.register_fake
 def _(x2d, Aq, ea, Bq, eb, bias):
-    torch._check(x2d.dim() == 2 and Aq.dim() == 2 and ea.dim() == 2 and Bq.dim() == 2 and eb.dim() == 2,
-                 lambda: "lowrank_forward_w6: 2-D operands")
-    torch._check(all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)),
-                 lambda: "lowrank_forward_w6: the codes and the block scales must be uint8")
-    torch._check(x2d.dtype in (torch.bfloat16, torch.float16), lambda: "lowrank_forward_w6: x2d must be bfloat16 or float16")
-    n_i, r, n_o = x2d.shape[1], Aq.shape[0], Bq.shape[0]
-    torch._check(n_i % W6_BLOCK == 0 and r % W6_BLOCK == 0, lambda: "lowrank_forward_w6: n_i and r must be multiples of 32")
-    torch._check(tuple(Aq.shape) == (r, 3 * n_i // 4) and tuple(Bq.shape) == (n_o, 3 * r // 4),
-                 lambda: "lowrank_forward_w6: shape mismatch (Aq [r, 3 n_i / 4], Bq [n_o, 3 r / 4])")
-    torch._check(tuple(ea.shape) == (r, n_i // W6_BLOCK) and tuple(eb.shape) == (n_o, r // W6_BLOCK),
-                 lambda: "lowrank_forward_w6: one scale byte per 32 weights of a row")
-    torch._check(bias is None or tuple(bias.shape) == (n_o,), lambda: "lowrank_forward_w6: bias must be [n_o]")
-    return x2d.new_empty((x2d.shape[0], n_o))
+    return _mx_fake("lowrank_forward_w6", lambda n: 3 * n // 4, "Aq [r, 3 n_i / 4], Bq [n_o, 3 r / 4]", x2d, Aq, ea, Bq, eb,
+                    bias)
 
 
 @torch.library.custom_op("ptdeco_amd::lowrank_forward_nchw", mutates_args=())

@@ -534,6 +534,33 @@ int ptd_lowrank_decode_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                            static_cast<hipStream_t>(stream));
 }
 
+// What precedes a launch of an MX entry `name`, in the order it is reported: null pointers, leading dimensions (lda, ldb,
+// ldsa and ldsb in bytes: code_a / code_b code bytes per row of A / B -- n / 2 for MXFP4, 3 (n / 4) for MXFP6 -- and one
+// scale byte per 32 weights), the workspace's alignment, what the kernels serve (`served`: the entry's *_serves; `rule`:
+// what it asks for, for the message) and the workspace's size (`need`: the entry's *_workspace_bytes).
+#define PTD_STR_(v) #v
+#define PTD_STR(v) PTD_STR_(v)
+static int mx_entry_checks(const char* name, const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                           int64_t ldsb, int64_t n_o, const void* y, int64_t ldy, const void* ws, size_t ws_bytes, int dtype,
+                           int w_format, int64_t code_a, int64_t code_b, bool served, const char* rule, size_t need) {
+  PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "%s: null pointer", name);
+  PTD_REQUIRE(ldx >= n_i && lda >= code_a && ldb >= code_b && ldsa >= n_i / 32 && ldsb >= r / 32 && ldy >= n_o,
+              "%s: bad leading dimension", name);
+  PTD_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", name);
+  // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
+  if (!served) {
+    set_error("%s: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d w_format=%d: bf16 / f16, %s)", name, (long long)T,
+              (long long)n_i, (long long)r, (long long)n_o, dtype, w_format, rule);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  if (ws_bytes < need) {
+    set_error("%s: workspace %zu < required %zu bytes", name, ws_bytes, need);
+    return PTD_ERR_WORKSPACE;
+  }
+  return PTD_OK;
+}
+
 size_t ptd_lowrank_decode_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
   return lowrank_decode_w4_workspace_bytes(T, n_i, r, dtype);
 }
@@ -542,23 +569,12 @@ int ptd_lowrank_decode_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
                           int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
                           int dtype, int w_format, void* stream) {
-  PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "ptd_lowrank_decode_w4: null pointer");
-  // (lda, ldb, ldsa and ldsb in bytes: two codes per byte, one scale byte per 32 weights)
-  PTD_REQUIRE(ldx >= n_i && lda >= n_i / 2 && ldb >= r / 2 && ldsa >= n_i / 32 && ldsb >= r / 32 && ldy >= n_o,
-              "ptd_lowrank_decode_w4: bad leading dimension");
-  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_decode_w4: the workspace must be 16-byte aligned");
-  // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
-  if (!lowrank_decode_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias)) {
-    set_error("ptd_lowrank_decode_w4: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d w_format=%d: bf16 / f16, "
-              "PTD_W4_MXFP4, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, 16-byte aligned rows)", (long long)T,
-              (long long)n_i, (long long)r, (long long)n_o, dtype, w_format);
-    return PTD_ERR_UNSUPPORTED;
-  }
-  if (ws_bytes < lowrank_decode_w4_workspace_bytes(T, n_i, r, dtype)) {
-    set_error("ptd_lowrank_decode_w4: workspace %zu < required %zu bytes", ws_bytes,
-              lowrank_decode_w4_workspace_bytes(T, n_i, r, dtype));
-    return PTD_ERR_WORKSPACE;
-  }
+  const int rc = mx_entry_checks("ptd_lowrank_decode_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
+                                 ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2,
+                                 lowrank_decode_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                 "PTD_W4_MXFP4, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, 16-byte aligned rows",
+                                 lowrank_decode_w4_workspace_bytes(T, n_i, r, dtype));
+  if (rc != PTD_OK) return rc;
   return lowrank_decode_w4(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
                            static_cast<hipStream_t>(stream));
 }
@@ -571,23 +587,12 @@ int ptd_lowrank_decode_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
                           int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
                           int dtype, int w_format, void* stream) {
-  PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "ptd_lowrank_decode_w6: null pointer");
-  // (lda, ldb, ldsa and ldsb in bytes: four codes per three bytes, one scale byte per 32 weights)
-  PTD_REQUIRE(ldx >= n_i && lda >= 3 * (n_i / 4) && ldb >= 3 * (r / 4) && ldsa >= n_i / 32 && ldsb >= r / 32 && ldy >= n_o,
-              "ptd_lowrank_decode_w6: bad leading dimension");
-  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_decode_w6: the workspace must be 16-byte aligned");
-  // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
-  if (!lowrank_decode_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias)) {
-    set_error("ptd_lowrank_decode_w6: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d w_format=%d: bf16 / f16, "
-              "PTD_W6_MXFP6_E2M3, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, 8-byte aligned rows)", (long long)T,
-              (long long)n_i, (long long)r, (long long)n_o, dtype, w_format);
-    return PTD_ERR_UNSUPPORTED;
-  }
-  if (ws_bytes < lowrank_decode_w6_workspace_bytes(T, n_i, r, dtype)) {
-    set_error("ptd_lowrank_decode_w6: workspace %zu < required %zu bytes", ws_bytes,
-              lowrank_decode_w6_workspace_bytes(T, n_i, r, dtype));
-    return PTD_ERR_WORKSPACE;
-  }
+  const int rc = mx_entry_checks("ptd_lowrank_decode_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
+                                 ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4),
+                                 lowrank_decode_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                 "PTD_W6_MXFP6_E2M3, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, 8-byte aligned rows",
+                                 lowrank_decode_w6_workspace_bytes(T, n_i, r, dtype));
+  if (rc != PTD_OK) return rc;
   return lowrank_decode_w6(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
                            static_cast<hipStream_t>(stream));
 }
@@ -723,23 +728,13 @@ int ptd_lowrank_skinny_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
                           int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
                           int dtype, int w_format, void* stream) {
-  PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "ptd_lowrank_skinny_w4: null pointer");
-  // (lda, ldb, ldsa and ldsb in bytes: two codes per byte, one scale byte per 32 weights)
-  PTD_REQUIRE(ldx >= n_i && lda >= n_i / 2 && ldb >= r / 2 && ldsa >= n_i / 32 && ldsb >= r / 32 && ldy >= n_o,
-              "ptd_lowrank_skinny_w4: bad leading dimension");
-  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_skinny_w4: the workspace must be 16-byte aligned");
-  // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
-  if (!lowrank_skinny_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias)) {
-    set_error("ptd_lowrank_skinny_w4: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d w_format=%d: bf16 / f16, "
-              "PTD_W4_MXFP4, 32 <= T <= %d, r >= 32, n_i and r multiples of 32, 8-byte aligned code rows)", (long long)T,
-              (long long)n_i, (long long)r, (long long)n_o, dtype, w_format, PTD_LOWRANK_SKINNY_W4_MAX_T);
-    return PTD_ERR_UNSUPPORTED;
-  }
-  if (ws_bytes < lowrank_skinny_w4_workspace_bytes(T, n_i, r, dtype)) {
-    set_error("ptd_lowrank_skinny_w4: workspace %zu < required %zu bytes", ws_bytes,
-              lowrank_skinny_w4_workspace_bytes(T, n_i, r, dtype));
-    return PTD_ERR_WORKSPACE;
-  }
+  const int rc = mx_entry_checks("ptd_lowrank_skinny_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
+                                 ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2,
+                                 lowrank_skinny_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                 "PTD_W4_MXFP4, 32 <= T <= " PTD_STR(PTD_LOWRANK_SKINNY_W4_MAX_T)
+                                 ", r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
+                                 lowrank_skinny_w4_workspace_bytes(T, n_i, r, dtype));
+  if (rc != PTD_OK) return rc;
   return lowrank_skinny_w4(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
                            static_cast<hipStream_t>(stream));
 }

@@ -64,7 +64,7 @@ int lowrank_decode_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const 
                       int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
                       int64_t ldy, void* ws, int dtype, hipStream_t st);
 
-// lowrank_decode_w4.hip: the same pair with OCP MXFP4 factors (e2m1 codes, one e8m0 scale byte per 32 weights of a row),
+// lowrank_decode_mx.hip: the same pair with OCP MXFP4 factors (e2m1 codes, one e8m0 scale byte per 32 weights of a row),
 // bf16 / f16 activations (ptd_lowrank_decode_w4): a lane's 16-byte load is one block, converted in registers with its scale
 bool lowrank_decode_w4_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
                               int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias);
@@ -73,7 +73,7 @@ int lowrank_decode_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const 
                       int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
                       const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 
-// lowrank_decode_w6.hip: the same pair with OCP MXFP6 factors (e2m3 codes, 24 bytes per block of 32, one e8m0 scale byte per
+// lowrank_decode_mx.hip: the same pair with OCP MXFP6 factors (e2m3 codes, 24 bytes per block of 32, one e8m0 scale byte per
 // block), bf16 / f16 activations (ptd_lowrank_decode_w6): a lane's 24-byte load is one block, converted by one instruction
 bool lowrank_decode_w6_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
                               int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias);
@@ -132,7 +132,7 @@ int lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const 
                       int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
                       int64_t ldy, void* ws, int dtype, hipStream_t st);
 
-// lowrank_skinny_w4.hip: the MXFP4 pair of lowrank_decode_w4.hip at 32 <= T <= PTD_LOWRANK_SKINNY_W4_MAX_T tokens with the
+// lowrank_skinny_w4.hip: the MXFP4 pair of lowrank_decode_mx.hip at 32 <= T <= PTD_LOWRANK_SKINNY_W4_MAX_T tokens with the
 // structure of lowrank_skinny_w8.hip: three launches, a lane's 8-byte load is half a block, converted in registers with
 // its block scale (ptd_lowrank_skinny_w4)
 bool lowrank_skinny_w4_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,

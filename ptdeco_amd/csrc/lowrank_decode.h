@@ -121,6 +121,39 @@ __device__ __forceinline__ void decode_xa_body(const typename P::elem* __restric
     *reinterpret_cast<f32x4*>(slabs + ((int64_t)by * T + tok) * r + row0) = acc;
 }
 
+// The image of h[:, chunk] in `himg` (16 rows of DEC_PITCH bytes) for a second product over r: the slabs added in slab
+// order, rounded once to the operand type.  The only copy: decode_hb_body, lowrank_gated.hip and lowrank_decode_mx.hip
+// call it (the fp8 kernels' staging also applies the row scale and is their own).
+template <typename P>
+__device__ __forceinline__ void hb_stage(char* himg, const float* __restrict__ slabs, const int nslabs, const int r,
+                                         const int T, const int chunk) {
+  typedef typename P::elem elem;
+  constexpr int KC = DEC_CHUNK_BYTES / (int)sizeof(elem);     // k of one LDS chunk
+  const int c0 = chunk * KC, kcv = min(KC, r - c0);
+  const int per = kcv >> 2, items = T * per;      // four k per item
+  for (int i0 = 0; i0 < items; i0 += 4 * DEC_THREADS) {
+    f32x4 v[4][DEC_MAX_SLABS];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = min(i0 + q * DEC_THREADS + (int)threadIdx.x, items - 1);
+      const int t = i / per, k4 = (i - t * per) * 4;
+#pragma unroll
+      for (int s = 0; s < DEC_MAX_SLABS; ++s)      // (all in flight together; a slab that does not exist: the last one again)
+        v[q][s] = *reinterpret_cast<const f32x4*>(slabs + ((int64_t)min(s, nslabs - 1) * T + t) * r + c0 + k4);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = i0 + q * DEC_THREADS + (int)threadIdx.x;
+      const int t = i / per, k4 = (i - t * per) * 4;
+      f32x4 sum = v[q][0];
+#pragma unroll
+      for (int s = 1; s < DEC_MAX_SLABS; ++s)
+        if (s < nslabs) sum += v[q][s];
+      if (i < items) P::put4(reinterpret_cast<elem*>(himg + t * DEC_PITCH) + k4, sum);
+    }
+  }
+}
+
 // y[t, o] for 16 rows o of B at a time: tiles g.tile0(), g.tile0() + g.stride(), ...  (`G` says where the workgroup
 // stands among those that share this B: asked where the value is used, as the kernel of one pair asks blockIdx / gridDim)
 template <typename P, bool NT, typename G>
@@ -155,33 +188,6 @@ __device__ __forceinline__ void decode_hb_body(const float* __restrict__ slabs, 
       w[u] = load_weights<frag, NT>(reinterpret_cast<const frag*>(wp + (kk < kend ? kk : 0)));
     }
   };
-  // the LDS image of h[:, chunk]: the slabs added in slab order, rounded once to the operand type
-  auto stage = [&](int chunk) {
-    const int c0 = chunk * KC, kcv = min(KC, r - c0);
-    const int per = kcv >> 2, items = T * per;      // four k per item
-    for (int i0 = 0; i0 < items; i0 += 4 * DEC_THREADS) {
-      f32x4 v[4][DEC_MAX_SLABS];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = min(i0 + q * DEC_THREADS + (int)threadIdx.x, items - 1);
-        const int t = i / per, k4 = (i - t * per) * 4;
-#pragma unroll
-        for (int s = 0; s < DEC_MAX_SLABS; ++s)      // (all in flight together; a slab that does not exist: the last one again)
-          v[q][s] = *reinterpret_cast<const f32x4*>(slabs + ((int64_t)min(s, nslabs - 1) * T + t) * r + c0 + k4);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = i0 + q * DEC_THREADS + (int)threadIdx.x;
-        const int t = i / per, k4 = (i - t * per) * 4;
-        f32x4 sum = v[q][0];
-#pragma unroll
-        for (int s = 1; s < DEC_MAX_SLABS; ++s)
-          if (s < nslabs) sum += v[q][s];
-        if (i < items) P::put4(reinterpret_cast<elem*>(himg + t * DEC_PITCH) + k4, sum);
-      }
-    }
-  };
-
   int tile = g.tile0();
   if (tile >= ntiles) return;
   frag w[DEC_U];
@@ -193,7 +199,7 @@ __device__ __forceinline__ void decode_hb_body(const float* __restrict__ slabs, 
     for (int chunk = 0; chunk < nchunks; ++chunk) {
       if (nchunks > 1 || tile == (int)g.tile0()) {
         if (tile != (int)g.tile0() || chunk > 0) __syncthreads();     // every wave is done with the previous image
-        stage(chunk);
+        hb_stage<P>(himg, slabs, nslabs, r, T, chunk);
         __syncthreads();
       }
       if (!loaded) load_tile(w, tile, chunk);
@@ -230,8 +236,8 @@ __device__ __forceinline__ void decode_hb_body(const float* __restrict__ slabs, 
 
 // The pieces of decode_hb_body as functions of one member's (slabs, r, B) and of an LDS image, for a kernel that forms
 // the sums of TWO members per tile (lowrank_gated.hip).  Each is the lambda of the same name above, statement by
-// statement: the wave's k range from r, the 16-byte pieces of a weight row, the image of h[:, chunk] from the slabs in
-// slab order, the DEC_U matrix-core steps in step order.  A sum built from them has the bits decode_hb_body gives it.
+// statement: the wave's k range from r, the 16-byte pieces of a weight row, the DEC_U matrix-core steps in step order
+// (the image of h[:, chunk] is hb_stage, which both call).  A sum built from them has the bits decode_hb_body gives it.
 template <typename P>
 struct HbSide {
   const float* slabs;
@@ -261,37 +267,6 @@ __device__ __forceinline__ void hb_load_tile(typename P::frag (&w)[DEC_U], const
   for (int u = 0; u < DEC_U; ++u) {
     const int kk = kbeg + u * P::KSTEP + kl;
     w[u] = load_weights<frag, NT>(reinterpret_cast<const frag*>(wp + (kk < kend ? kk : 0)));
-  }
-}
-
-// the image of h[:, chunk] in `himg` (16 rows of DEC_PITCH bytes): the slabs added in slab order, rounded once
-template <typename P>
-__device__ __forceinline__ void hb_stage(char* himg, const HbSide<P>& m, const int T, const int chunk) {
-  typedef typename P::elem elem;
-  constexpr int KC = DEC_CHUNK_BYTES / (int)sizeof(elem);
-  const int r = m.r, nslabs = m.nslabs;
-  const int c0 = chunk * KC, kcv = min(KC, r - c0);
-  const int per = kcv >> 2, items = T * per;      // four k per item
-  for (int i0 = 0; i0 < items; i0 += 4 * DEC_THREADS) {
-    f32x4 v[4][DEC_MAX_SLABS];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = min(i0 + q * DEC_THREADS + (int)threadIdx.x, items - 1);
-      const int t = i / per, k4 = (i - t * per) * 4;
-#pragma unroll
-      for (int s = 0; s < DEC_MAX_SLABS; ++s)
-        v[q][s] = *reinterpret_cast<const f32x4*>(m.slabs + ((int64_t)min(s, nslabs - 1) * T + t) * r + c0 + k4);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = i0 + q * DEC_THREADS + (int)threadIdx.x;
-      const int t = i / per, k4 = (i - t * per) * 4;
-      f32x4 sum = v[q][0];
-#pragma unroll
-      for (int s = 1; s < DEC_MAX_SLABS; ++s)
-        if (s < nslabs) sum += v[q][s];
-      if (i < items) P::put4(reinterpret_cast<elem*>(himg + t * DEC_PITCH) + k4, sum);
-    }
   }
 }
 

@@ -75,8 +75,8 @@ __global__ __launch_bounds__(DEC_THREADS) void gated_hb_kernel(const int T, cons
   // an image that holds all of its member's h is staged once per workgroup; when both do, together
   bool staged_g = false, staged_u = false, read_g = false, read_u = false;
   if (nch_g == 1 && nch_u == 1) {
-    hb_stage<P>(img_g, gate, T, 0);
-    hb_stage<P>(img_u, up, T, 0);
+    hb_stage<P>(img_g, gate.slabs, gate.nslabs, gate.r, T, 0);
+    hb_stage<P>(img_u, up.slabs, up.nslabs, up.r, T, 0);
     __syncthreads();
     staged_g = staged_u = true;
   }
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(DEC_THREADS) void gated_hb_kernel(const int T, cons
     for (int chunk = 0; chunk < nch_g; ++chunk) {
       if (nch_g > 1 || !staged_g) {
         if (read_g) __syncthreads();     // every wave is done with the previous image
-        hb_stage<P>(img_g, gate, T, chunk);
+        hb_stage<P>(img_g, gate.slabs, gate.nslabs, gate.r, T, chunk);
         __syncthreads();
         staged_g = true;
       }
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(DEC_THREADS) void gated_hb_kernel(const int T, cons
     for (int chunk = 0; chunk < nch_u; ++chunk) {
       if (nch_u > 1 || !staged_u) {
         if (read_u) __syncthreads();
-        hb_stage<P>(img_u, up, T, chunk);
+        hb_stage<P>(img_u, up.slabs, up.nslabs, up.r, T, chunk);
         __syncthreads();
         staged_u = true;
       }

@@ -1,16 +1,14 @@
 // ptd_lowrank_plan: what a launch of one serving family of the low-rank pair would do for a shape, computed on the host by
-// the very functions its launcher and its kernels call -- xa_split<P> / w8_xa_split / w4_xa_split / w6_xa_split / sk_xa_split
-// for the K slabs, hb_grid for the second decode product, xa_wave_range, hb_nchunks and hb_chunk_wave_range for the wave
-// ranges, w8_xa_steps / w4_xa_blocks / w4_hb_blocks / w6_xa_blocks / w6_hb_blocks / w4_sk_scale_bytes for the kernel variant, *_serves for what the
-// family takes.  No
-// device code, no launch, no allocation.  The tests use it to prove which branch combination a shape reaches.
+// the very functions its launcher and its kernels call -- xa_split<P> / w8_xa_split / mx_xa_split / sk_xa_split for the
+// K slabs, hb_grid for the second decode product, xa_wave_range, hb_nchunks and hb_chunk_wave_range for the wave ranges,
+// w8_xa_steps / mx_xa_blocks / mx_hb_blocks / mx_sk_scale_bytes for the kernel variant, *_serves for what the family
+// takes.  No device code, no launch, no allocation.  The tests use it to prove which branch combination a shape reaches.
 #include "common.h"
 #include "elem16.h"
 #include "kernels.h"
 #include "lowrank_decode.h"
 #include "lowrank_skinny.h"
-#include "lowrank_w4.h"
-#include "lowrank_w6.h"
+#include "lowrank_mx.h"
 #include "lowrank_w8.h"
 
 namespace ptd {
@@ -81,35 +79,20 @@ void plan_decode_w8(int* out, int64_t n_i, int64_t r, int64_t n_o) {
   out[PTD_PLAN_HB_U] = W8_HB_U, out[PTD_PLAN_HB_TAIL_BLOCKS] = 0;
 }
 
-void plan_decode_w4(int* out, int64_t n_i, int64_t r, int64_t n_o) {
+// lowrank_decode_mx.hip: MXFP4 and MXFP6 alike -- the split and the blocks of a lane follow from the block size
+void plan_decode_mx(int* out, int64_t n_i, int64_t r, int64_t n_o) {
   int nslabs, kchunk;
   int asked, unused;
-  w4_xa_split(PLAN_LONG_ROW, r, asked, unused);
+  mx_xa_split(PLAN_LONG_ROW, r, asked, unused);
   out[PTD_PLAN_SLABS_ASKED] = asked;
-  w4_xa_split(n_i, r, nslabs, kchunk);
+  mx_xa_split(n_i, r, nslabs, kchunk);
   out[PTD_PLAN_NSLABS] = nslabs, out[PTD_PLAN_KCHUNK] = kchunk;
   out[PTD_PLAN_XA_GRID_X] = (int)ceil_div(r, 16), out[PTD_PLAN_XA_GRID_Y] = nslabs, out[PTD_PLAN_XA_GRID_Z] = 1;
-  xa_waves(out, nslabs, kchunk, (int)n_i, W4_KSTEP);
-  const int ua = w4_xa_blocks(kchunk), ub = w4_hb_blocks(r);
-  out[PTD_PLAN_XA_U] = ua, out[PTD_PLAN_XA_TAIL_BLOCKS] = (int)(n_i / W4_BLOCK % ua);
-  hb_decode(out, r, n_o, W4_KC);
-  out[PTD_PLAN_HB_U] = ub, out[PTD_PLAN_HB_TAIL_BLOCKS] = (int)(r / W4_BLOCK % ub);
-}
-
-// lowrank_decode_w6.hip: the fields of plan_decode_w4, from this format's rules
-void plan_decode_w6(int* out, int64_t n_i, int64_t r, int64_t n_o) {
-  int nslabs, kchunk;
-  int asked, unused;
-  w6_xa_split(PLAN_LONG_ROW, r, asked, unused);
-  out[PTD_PLAN_SLABS_ASKED] = asked;
-  w6_xa_split(n_i, r, nslabs, kchunk);
-  out[PTD_PLAN_NSLABS] = nslabs, out[PTD_PLAN_KCHUNK] = kchunk;
-  out[PTD_PLAN_XA_GRID_X] = (int)ceil_div(r, 16), out[PTD_PLAN_XA_GRID_Y] = nslabs, out[PTD_PLAN_XA_GRID_Z] = 1;
-  xa_waves(out, nslabs, kchunk, (int)n_i, W6_KSTEP);
-  const int ua = w6_xa_blocks(kchunk), ub = w6_hb_blocks(r);
-  out[PTD_PLAN_XA_U] = ua, out[PTD_PLAN_XA_TAIL_BLOCKS] = (int)(n_i / W6_BLOCK % ua);
-  hb_decode(out, r, n_o, W6_KC);
-  out[PTD_PLAN_HB_U] = ub, out[PTD_PLAN_HB_TAIL_BLOCKS] = (int)(r / W6_BLOCK % ub);
+  xa_waves(out, nslabs, kchunk, (int)n_i, MX_KSTEP);
+  const int ua = mx_xa_blocks(kchunk), ub = mx_hb_blocks(r);
+  out[PTD_PLAN_XA_U] = ua, out[PTD_PLAN_XA_TAIL_BLOCKS] = (int)(n_i / MX_BLOCK % ua);
+  hb_decode(out, r, n_o, MX_KC);
+  out[PTD_PLAN_HB_U] = ub, out[PTD_PLAN_HB_TAIL_BLOCKS] = (int)(r / MX_BLOCK % ub);
 }
 
 // lowrank_skinny.hip and lowrank_skinny_w8.hip: one split, one grid rule
@@ -139,9 +122,9 @@ void plan_skinny(int* out, int64_t T, int64_t n_i, int64_t r, int64_t n_o) {
 // lowrank_skinny_w4.hip: the skinny split and grids; the variant of each product is the scale bytes of one load
 void plan_skinny_w4(int* out, int64_t T, int64_t n_i, int64_t r, int64_t n_o) {
   plan_skinny(out, T, n_i, r, n_o);
-  const int ua = w4_sk_scale_bytes(n_i), ub = w4_sk_scale_bytes(r);
-  out[PTD_PLAN_XA_U] = ua, out[PTD_PLAN_XA_TAIL_BLOCKS] = (int)(n_i / W4_BLOCK % ua);
-  out[PTD_PLAN_HB_U] = ub, out[PTD_PLAN_HB_TAIL_BLOCKS] = (int)(r / W4_BLOCK % ub);
+  const int ua = mx_sk_scale_bytes(n_i), ub = mx_sk_scale_bytes(r);
+  out[PTD_PLAN_XA_U] = ua, out[PTD_PLAN_XA_TAIL_BLOCKS] = (int)(n_i / MX_BLOCK % ua);
+  out[PTD_PLAN_HB_U] = ub, out[PTD_PLAN_HB_TAIL_BLOCKS] = (int)(r / MX_BLOCK % ub);
 }
 
 }  // namespace
@@ -168,12 +151,12 @@ int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int
     case PTD_PLAN_DECODE_W4:
       if (!lowrank_decode_w4_serves(T, n_i, r, n_o, dtype, PTD_W4_MXFP4, p, n_i, p, n_i / 2, p, r / 2, p))
         return PTD_ERR_UNSUPPORTED;
-      plan_decode_w4(out, n_i, r, n_o);
+      plan_decode_mx(out, n_i, r, n_o);
       return PTD_OK;
     case PTD_PLAN_DECODE_W6:
       if (!lowrank_decode_w6_serves(T, n_i, r, n_o, dtype, PTD_W6_MXFP6_E2M3, p, n_i, p, 3 * (n_i / 4), p, 3 * (r / 4), p))
         return PTD_ERR_UNSUPPORTED;
-      plan_decode_w6(out, n_i, r, n_o);
+      plan_decode_mx(out, n_i, r, n_o);
       return PTD_OK;
     case PTD_PLAN_SKINNY:
       if (!lowrank_skinny_serves(T, n_i, r, n_o, dtype, p, n_i, p, n_i, p, r)) return PTD_ERR_UNSUPPORTED;

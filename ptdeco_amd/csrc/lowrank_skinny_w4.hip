@@ -1,6 +1,6 @@
 // The low-rank pair at small batches (32 <= T <= SKW4_MAX_T tokens) with OCP MXFP4 factors (packed e2m1 codes, one e8m0
 // scale byte per 32 consecutive weights of a row): the structure of lowrank_skinny_w8.hip on the weight bytes and
-// semantics of lowrank_decode_w4.hip.
+// semantics of lowrank_decode_mx.hip.
 //
 //   W^[i, k]                       = e2m1(code(W, i, k)) * 2^(clamp(e[i, k >> 5], 114, 140) - 127)
 //   skinny_w4_product<.., true>    slab_s[t, i] = sum_{k in K range s} x[t, k] A^[i, k]         (f32 partial sums, workspace)
@@ -27,7 +27,7 @@
 // second.  The two bytes are one unaligned 16-bit load per fragment and step (scale rows have byte alignment only); its
 // address is clamped so that both bytes lie inside the row and the value is shifted accordingly -- reached where the
 // row's block count is odd.  A row of a single block (n_i = 32, r = 32) takes the one-byte instance: the choice is
-// w4_sk_scale_bytes of lowrank_w4.h, a function of the row length alone.  The clamp to [114, 140] is applied in the lane.
+// mx_sk_scale_bytes of lowrank_mx.h, a function of the row length alone.  The clamp to [114, 140] is applied in the lane.
 //
 // Split, order and rounding.  sk_xa_split / slab_bytes of lowrank_skinny.h as they are: the slab count and every K range
 // depend on (n_i, r) alone, never on T, and a column of the MFMA's B operand only reaches the same column of its result,
@@ -48,12 +48,12 @@ namespace {
 
 constexpr int SKW4_MAX_T = PTD_LOWRANK_SKINNY_W4_MAX_T;      // the cap of the MXFP4 route (measured: profiles/pair_skinny_w4.json)
 
-static_assert(SK_KW == 2 * W4_BLOCK, "a wave's step is two MX blocks: 8 code bytes per lane");
+static_assert(SK_KW == 2 * MX_BLOCK, "a wave's step is two MX blocks: 8 code bytes per lane");
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // out[t, i] over the K range of blockIdx.y for rows 32 blockIdx.x + 0..31 and tokens 64 blockIdx.z + 0..63; W [R, K / 2]
-// code bytes with row pitch ldw, E [R, K / 32] scale bytes with row pitch ldse, U scale bytes per load (w4_sk_scale_bytes).
+// code bytes with row pitch ldw, E [R, K / 32] scale bytes with row pitch ldse, U scale bytes per load (mx_sk_scale_bytes).
 // SLAB: f32 sums to out_f32[(blockIdx.y T + t) R + i]; otherwise round(sum + bias[i]) to y[t ldy + i].
 template <typename EL, bool SLAB, int U>
 __global__ __launch_bounds__(SK_THREADS) void skinny_w4_product_kernel(const elem* __restrict__ X, const int64_t ldx,
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_w4_product_kernel(const ele
   const int kbase = blockIdx.y * kchunk;
   const int kend = min(kbase + kchunk, K);            // (K, kchunk multiples of 32: a lane's 16 k are inside or outside)
   const int tok0 = blockIdx.z * SK_TOK;
-  const int nblk = K / W4_BLOCK;                      // (>= U: w4_sk_scale_bytes)
+  const int nblk = K / MX_BLOCK;                      // (>= U: mx_sk_scale_bytes)
 
   // weights: this wave's k range, rows f * 16 + (lane & 15), 16 codes (8 bytes) per lane and step
   int wk0, wkend;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_w4_product_kernel(const ele
     const int ks = wk0 + step * SK_KW;
     // the step's U scale bytes in one load that stays inside the row (blocks ks / 32 + 0 .. U - 1; where the row's
     // block count is odd its last block is the second byte of the load one block back: shifted down)
-    const int b = ks / W4_BLOCK, bl = min(b, nblk - U);
+    const int b = ks / MX_BLOCK, bl = min(b, nblk - U);
     const int sh = 8 * (min(b - bl, U - 1) + eb);
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_w4_product_kernel(const ele
       const bool ok = k < wkend;
       const u32x2 v = *reinterpret_cast<const u32x2*>(wp[f] + ((ok ? k : 0) >> 1));
       wn[f] = ok ? v : u32x2{};          // (code 0 is +0 under every clamped scale)
-      en[f] = w4_load_scales<U>(ep[f] + bl) >> sh;
+      en[f] = mx_load_scales<U>(ep[f] + bl) >> sh;
     }
 #pragma unroll
     for (int q = 0; q < SK_PIECES; ++q) {
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_w4_product_kernel(const ele
     s16x8 w[2][2];
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
-      const float scale = w4_scale(en[f]);
+      const float scale = mx_scale<MxFp4>(en[f]);
 #pragma unroll
       for (int j = 0; j < 2; ++j)
         w[f][j] = w4_operand<EL>(__builtin_amdgcn_alignbit(wn[f][j], wn[f][j], rot), scale);
@@ -243,7 +243,7 @@ int launch_skinny_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const v
   const unsigned tiles = (unsigned)ceil_div(T, SK_TOK);
   const dim3 blk(SK_THREADS);
   const dim3 g1((unsigned)ceil_div(r, SK_ROWS), (unsigned)nslabs, tiles);
-  auto xa = w4_sk_scale_bytes(n_i) == 2 ? skinny_w4_product_kernel<EL, true, 2> : skinny_w4_product_kernel<EL, true, 1>;
+  auto xa = mx_sk_scale_bytes(n_i) == 2 ? skinny_w4_product_kernel<EL, true, 2> : skinny_w4_product_kernel<EL, true, 1>;
   hipLaunchKernelGGL(xa, g1, blk, 0, st, static_cast<const elem*>(x), ldx, (int)T, (int)n_i,
                      static_cast<const unsigned char*>(Aq), lda, static_cast<const unsigned char*>(ea), ldsa, (int)r,
                      kchunk, slabs, (const elem*)nullptr, (elem*)nullptr, (int64_t)0);
@@ -253,7 +253,7 @@ int launch_skinny_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const v
                      nslabs, items, h);
   PTD_CHECK_LAUNCH("ptd_lowrank_skinny_w4 (slab sum)");
   const dim3 g2((unsigned)ceil_div(n_o, SK_ROWS), 1, tiles);
-  auto hb = w4_sk_scale_bytes(r) == 2 ? skinny_w4_product_kernel<EL, false, 2> : skinny_w4_product_kernel<EL, false, 1>;
+  auto hb = mx_sk_scale_bytes(r) == 2 ? skinny_w4_product_kernel<EL, false, 2> : skinny_w4_product_kernel<EL, false, 1>;
   hipLaunchKernelGGL(hb, g2, blk, 0, st, h, r, (int)T, (int)r, static_cast<const unsigned char*>(Bq), ldb,
                      static_cast<const unsigned char*>(eb), ldsb, (int)n_o,
                      (int)align_up((size_t)r, (size_t)SK_QUANTUM), (float*)nullptr, static_cast<const elem*>(bias),
@@ -268,8 +268,8 @@ bool lowrank_skinny_w4_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, in
                               int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias) {
   if (dtype != PTD_BF16 && dtype != PTD_F16) return false;
   if (w_format != PTD_W4_MXFP4) return false;
-  if (T < SK_MIN_T || T > SKW4_MAX_T || n_o < 1 || r < W4_BLOCK || n_i < W4_BLOCK) return false;
-  if (n_i % W4_BLOCK || r % W4_BLOCK || ldx % 8 || lda % 8 || ldb % 8) return false;
+  if (T < SK_MIN_T || T > SKW4_MAX_T || n_o < 1 || r < MX_BLOCK || n_i < MX_BLOCK) return false;
+  if (n_i % MX_BLOCK || r % MX_BLOCK || ldx % 8 || lda % 8 || ldb % 8) return false;
   if (n_i >= (1ll << 30) || r >= (1ll << 27) || n_o >= (1ll << 30)) return false;      // (lowrank_skinny_serves' limits)
   if (reinterpret_cast<uintptr_t>(bias) & 1) return false;
   if ((reinterpret_cast<uintptr_t>(Aq) & 7) || (reinterpret_cast<uintptr_t>(Bq) & 7)) return false;

@@ -87,7 +87,29 @@ _W8_FORMATS = {"fp8_e4m3": (torch.float8_e4m3fn, 448.0)}
 _W8_FIXED = ("weight_a_q", "scale_a", "weight_b_q", "scale_b")
 
 
-class LowRankLinearW8(torch.nn.Module):
+class _QuantizedPair(torch.nn.Module):
+    """What the quantised pairs share: the activation dtype and what a cast does to it and to the bias."""
+
+    @property
+    def dtype(self) -> torch.dtype:
+        """The activation dtype D: what x must be for the HIP kernels, and what the bias is held in."""
+        return self._dtype
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)      # (a dtype cast leaves integer buffers alone: packed bytes stay)
+        cast = fn(torch.empty(0, dtype=self._dtype)).dtype
+        if cast in _W8_DTYPES:
+            self._dtype = cast
+        if self.bias is not None and self.bias.dtype != self._dtype:
+            self._buffers["bias"] = self.bias.to(self._dtype)
+        return self
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, rank={self.rank}, out_features={self.out_features}, "
+                f"bias={self.bias is not None}, dtype={self._dtype}")
+
+
+class LowRankLinearW8(_QuantizedPair):
     """A rank-r pair with 8-bit factors (weight-only quantisation): ``weight_a_q`` [rank, in_features] and ``weight_b_q``
     [out_features, rank] in float8_e4m3fn, one f32 scale per factor row (``scale_a`` [rank], ``scale_b`` [out_features])
     and ``bias`` [out_features] in the activation dtype (bf16 or f16) or None -- all buffers: the module is
@@ -117,11 +139,6 @@ class LowRankLinearW8(torch.nn.Module):
         self.register_buffer("scale_b", torch.ones(out_features, dtype=torch.float32, device=device))
         self.register_buffer("bias", torch.zeros(out_features, dtype=dtype, device=device) if bias else None)
 
-    @property
-    def dtype(self) -> torch.dtype:
-        """The activation dtype D: what x must be for the HIP kernels, and what the bias is held in."""
-        return self._dtype
-
     def _apply(self, fn, *args, **kwargs):
         fixed = {name: self._buffers[name] for name in _W8_FIXED}
         super()._apply(fn, *args, **kwargs)
@@ -129,16 +146,7 @@ class LowRankLinearW8(torch.nn.Module):
             new = self._buffers[name]
             if new.dtype != old.dtype:
                 self._buffers[name] = old.to(new.device)
-        cast = fn(torch.empty(0, dtype=self._dtype)).dtype
-        if cast in _W8_DTYPES:
-            self._dtype = cast
-        if self.bias is not None and self.bias.dtype != self._dtype:
-            self._buffers["bias"] = self.bias.to(self._dtype)
         return self
-
-    def extra_repr(self) -> str:
-        return (f"in_features={self.in_features}, rank={self.rank}, out_features={self.out_features}, "
-                f"bias={self.bias is not None}, dtype={self._dtype}")
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         operands = (self.weight_a_q, self.scale_a, self.weight_b_q, self.scale_b, self.bias)
@@ -156,13 +164,54 @@ class LowRankLinearW8(torch.nn.Module):
 
 
 _W4_FORMAT = "mxfp4"
-_W4_BLOCK = _torch_ops.W4_BLOCK
 _W6_FORMAT = "mxfp6_e2m3"
-_W6_BLOCK = _torch_ops.W6_BLOCK
+_MX_BLOCK = _torch_ops.W4_BLOCK      # (= W6_BLOCK: weights per scale byte, whatever the element type)
 _QUANT_FORMATS = tuple(_W8_FORMATS) + (_W4_FORMAT, _W6_FORMAT)
 
 
-class LowRankLinearW4(torch.nn.Module):
+class _LowRankLinearMX(_QuantizedPair):
+    """An MX pair whatever the element type: uint8 code rows of ``_code_cols(n)`` bytes per n weights, one e8m0 scale
+    byte per block of 32.  A subclass names its format (``_mx_name``, for the messages) and supplies ``_code_cols``,
+    the custom op (``_forward_op``) and the torch expression of the same semantics (``_expression``)."""
+
+    def __init__(self, in_features: int, rank: int, out_features: int, bias: bool = True,
+                 dtype: torch.dtype = torch.bfloat16, device=None) -> None:
+        super().__init__()
+        cls = type(self).__name__
+        if dtype not in _W8_DTYPES:
+            raise ValueError(f"{cls}: the activation dtype must be bfloat16 or float16, got {dtype}")
+        if in_features % _MX_BLOCK or rank % _MX_BLOCK or rank < _MX_BLOCK or in_features < _MX_BLOCK:
+            raise ValueError(f"{cls}: in_features and rank must be positive multiples of {_MX_BLOCK}, got "
+                             f"{in_features} and {rank}")
+        self.in_features, self.rank, self.out_features = int(in_features), int(rank), int(out_features)
+        self._dtype = dtype
+
+        def zeros(rows, cols, fill=0):
+            return torch.full((rows, cols), fill, dtype=torch.uint8, device=device)
+
+        self.register_buffer("weight_a_q", zeros(rank, self._code_cols(in_features)))
+        self.register_buffer("scale_a", zeros(rank, in_features // _MX_BLOCK, 127))
+        self.register_buffer("weight_b_q", zeros(out_features, self._code_cols(rank)))
+        self.register_buffer("scale_b", zeros(out_features, rank // _MX_BLOCK, 127))
+        self.register_buffer("bias", torch.zeros(out_features, dtype=dtype, device=device) if bias else None)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        operands = (self.weight_a_q, self.scale_a, self.weight_b_q, self.scale_b, self.bias)
+        wants_grad = torch.is_grad_enabled() and x.requires_grad
+        if not (x.is_cuda and x.dtype == self._dtype and not wants_grad):
+            cls = type(self).__name__
+            why = ("a gradient with respect to x" if x.is_cuda and x.dtype == self._dtype else
+                   "a CPU tensor" if not x.is_cuda else f"input dtype {x.dtype} with activation dtype {self._dtype}")
+            warn_once(f"{cls}:{why}", f"ptdeco_amd.{cls}: {why} is not served by the HIP {self._mx_name} kernels "
+                                      "(bf16 / f16 inference on a ROCm device); evaluating the torch expression "
+                                      "on 16-bit copies of the factors instead")
+            return self._expression(x, *operands)
+        x2d = x.reshape(-1, self.in_features)
+        y = self._forward_op(x2d, *operands)
+        return y.reshape(*x.shape[:-1], self.out_features)
+
+
+class LowRankLinearW4(_LowRankLinearMX):
     """A rank-r pair with OCP MXFP4 factors (weight-only quantisation, 4.25 bits per weight): ``weight_a_q``
     [rank, in_features / 2] and ``weight_b_q`` [out_features, rank / 2] hold packed e2m1 codes (two per byte, the low
     nibble the even k), ``scale_a`` [rank, in_features / 32] and ``scale_b`` [out_features, rank / 32] one e8m0 scale
@@ -188,60 +237,16 @@ class LowRankLinearW4(torch.nn.Module):
     cast (``.half()``, ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the packed buffers
     as they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place``, or empty for ``load_state_dict``."""
 
-    def __init__(self, in_features: int, rank: int, out_features: int, bias: bool = True,
-                 dtype: torch.dtype = torch.bfloat16, device=None) -> None:
-        super().__init__()
-        if dtype not in _W8_DTYPES:
-            raise ValueError(f"LowRankLinearW4: the activation dtype must be bfloat16 or float16, got {dtype}")
-        if in_features % _W4_BLOCK or rank % _W4_BLOCK or rank < _W4_BLOCK or in_features < _W4_BLOCK:
-            raise ValueError(f"LowRankLinearW4: in_features and rank must be positive multiples of {_W4_BLOCK}, got "
-                             f"{in_features} and {rank}")
-        self.in_features, self.rank, self.out_features = int(in_features), int(rank), int(out_features)
-        self._dtype = dtype
+    _mx_name = "MXFP4"
+    _forward_op = staticmethod(_lowrank_forward_w4)
+    _expression = staticmethod(_torch_ops.lowrank_w4_expression)
 
-        def zeros(rows, cols, fill=0):
-            return torch.full((rows, cols), fill, dtype=torch.uint8, device=device)
-
-        self.register_buffer("weight_a_q", zeros(rank, in_features // 2))
-        self.register_buffer("scale_a", zeros(rank, in_features // _W4_BLOCK, 127))
-        self.register_buffer("weight_b_q", zeros(out_features, rank // 2))
-        self.register_buffer("scale_b", zeros(out_features, rank // _W4_BLOCK, 127))
-        self.register_buffer("bias", torch.zeros(out_features, dtype=dtype, device=device) if bias else None)
-
-    @property
-    def dtype(self) -> torch.dtype:
-        """The activation dtype D: what x must be for the HIP kernels, and what the bias is held in."""
-        return self._dtype
-
-    def _apply(self, fn, *args, **kwargs):
-        super()._apply(fn, *args, **kwargs)      # (a dtype cast leaves integer buffers alone: the packed bytes stay)
-        cast = fn(torch.empty(0, dtype=self._dtype)).dtype
-        if cast in _W8_DTYPES:
-            self._dtype = cast
-        if self.bias is not None and self.bias.dtype != self._dtype:
-            self._buffers["bias"] = self.bias.to(self._dtype)
-        return self
-
-    def extra_repr(self) -> str:
-        return (f"in_features={self.in_features}, rank={self.rank}, out_features={self.out_features}, "
-                f"bias={self.bias is not None}, dtype={self._dtype}")
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        operands = (self.weight_a_q, self.scale_a, self.weight_b_q, self.scale_b, self.bias)
-        wants_grad = torch.is_grad_enabled() and x.requires_grad
-        if not (x.is_cuda and x.dtype == self._dtype and not wants_grad):
-            why = ("a gradient with respect to x" if x.is_cuda and x.dtype == self._dtype else
-                   "a CPU tensor" if not x.is_cuda else f"input dtype {x.dtype} with activation dtype {self._dtype}")
-            warn_once(f"LowRankLinearW4:{why}", f"ptdeco_amd.LowRankLinearW4: {why} is not served by the HIP MXFP4 kernels "
-                                                "(bf16 / f16 inference on a ROCm device); evaluating the torch expression "
-                                                "on 16-bit copies of the factors instead")
-            return _torch_ops.lowrank_w4_expression(x, *operands)
-        x2d = x.reshape(-1, self.in_features)
-        y = _lowrank_forward_w4(x2d, *operands)
-        return y.reshape(*x.shape[:-1], self.out_features)
+    @staticmethod
+    def _code_cols(n: int) -> int:
+        return n // 2
 
 
-class LowRankLinearW6(torch.nn.Module):
+class LowRankLinearW6(_LowRankLinearMX):
     """A rank-r pair with OCP MXFP6 factors, e2m3 elements (weight-only quantisation, 6.25 bits per weight):
     ``weight_a_q`` [rank, 3 in_features / 4] and ``weight_b_q`` [out_features, 3 rank / 4] hold packed 6-bit codes (a
     block of 32 codes is 24 bytes read as one little-endian integer, the code of k = 32 b + j at its bits
@@ -267,57 +272,13 @@ class LowRankLinearW6(torch.nn.Module):
     ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the packed buffers as they are.
     Built by ``quantize_pair`` / ``quantize_pairs_in_place`` with ``"mxfp6_e2m3"``, or empty for ``load_state_dict``."""
 
-    def __init__(self, in_features: int, rank: int, out_features: int, bias: bool = True,
-                 dtype: torch.dtype = torch.bfloat16, device=None) -> None:
-        super().__init__()
-        if dtype not in _W8_DTYPES:
-            raise ValueError(f"LowRankLinearW6: the activation dtype must be bfloat16 or float16, got {dtype}")
-        if in_features % _W6_BLOCK or rank % _W6_BLOCK or rank < _W6_BLOCK or in_features < _W6_BLOCK:
-            raise ValueError(f"LowRankLinearW6: in_features and rank must be positive multiples of {_W6_BLOCK}, got "
-                             f"{in_features} and {rank}")
-        self.in_features, self.rank, self.out_features = int(in_features), int(rank), int(out_features)
-        self._dtype = dtype
+    _mx_name = "MXFP6"
+    _forward_op = staticmethod(_lowrank_forward_w6)
+    _expression = staticmethod(_torch_ops.lowrank_w6_expression)
 
-        def zeros(rows, cols, fill=0):
-            return torch.full((rows, cols), fill, dtype=torch.uint8, device=device)
-
-        self.register_buffer("weight_a_q", zeros(rank, 3 * in_features // 4))
-        self.register_buffer("scale_a", zeros(rank, in_features // _W6_BLOCK, 127))
-        self.register_buffer("weight_b_q", zeros(out_features, 3 * rank // 4))
-        self.register_buffer("scale_b", zeros(out_features, rank // _W6_BLOCK, 127))
-        self.register_buffer("bias", torch.zeros(out_features, dtype=dtype, device=device) if bias else None)
-
-    @property
-    def dtype(self) -> torch.dtype:
-        """The activation dtype D: what x must be for the HIP kernels, and what the bias is held in."""
-        return self._dtype
-
-    def _apply(self, fn, *args, **kwargs):
-        super()._apply(fn, *args, **kwargs)      # (a dtype cast leaves integer buffers alone: the packed bytes stay)
-        cast = fn(torch.empty(0, dtype=self._dtype)).dtype
-        if cast in _W8_DTYPES:
-            self._dtype = cast
-        if self.bias is not None and self.bias.dtype != self._dtype:
-            self._buffers["bias"] = self.bias.to(self._dtype)
-        return self
-
-    def extra_repr(self) -> str:
-        return (f"in_features={self.in_features}, rank={self.rank}, out_features={self.out_features}, "
-                f"bias={self.bias is not None}, dtype={self._dtype}")
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        operands = (self.weight_a_q, self.scale_a, self.weight_b_q, self.scale_b, self.bias)
-        wants_grad = torch.is_grad_enabled() and x.requires_grad
-        if not (x.is_cuda and x.dtype == self._dtype and not wants_grad):
-            why = ("a gradient with respect to x" if x.is_cuda and x.dtype == self._dtype else
-                   "a CPU tensor" if not x.is_cuda else f"input dtype {x.dtype} with activation dtype {self._dtype}")
-            warn_once(f"LowRankLinearW6:{why}", f"ptdeco_amd.LowRankLinearW6: {why} is not served by the HIP MXFP6 kernels "
-                                                "(bf16 / f16 inference on a ROCm device); evaluating the torch expression "
-                                                "on 16-bit copies of the factors instead")
-            return _torch_ops.lowrank_w6_expression(x, *operands)
-        x2d = x.reshape(-1, self.in_features)
-        y = _lowrank_forward_w6(x2d, *operands)
-        return y.reshape(*x.shape[:-1], self.out_features)
+    @staticmethod
+    def _code_cols(n: int) -> int:
+        return 3 * n // 4
 
 
 def _quantize_rows(w: torch.Tensor, qdtype: torch.dtype, qmax: float):
@@ -332,6 +293,25 @@ def _quantize_rows(w: torch.Tensor, qdtype: torch.dtype, qmax: float):
     return q.contiguous(), s.contiguous()
 
 
+def _mx_block_exponents(w: torch.Tensor, name: str, e_min: int):
+    """The prologue of the MX quantisers: w [rows, cols] as f32 blocks of 32 consecutive weights of a row, per block the
+    exponent e = clamp(floor(log2 amax) - 2, e_min, 13) (0 for a block of zeros).  Returns (v = blocks / 2^e, exact,
+    [rows, cols / 32, 32]; e [rows, cols / 32], integer)."""
+    rows, cols = w.shape
+    if cols % _MX_BLOCK:
+        raise ValueError(f"quantize_pair: {name} needs rows of a multiple of {_MX_BLOCK} weights, got {cols}")
+    blocks = w.detach().float().reshape(rows, cols // _MX_BLOCK, _MX_BLOCK)
+    amax = blocks.abs().amax(dim=-1)
+    if not bool(torch.isfinite(amax).all()):
+        raise ValueError("quantize_pair: the factors hold non-finite values")
+    if bool((amax >= 2.0 ** 16).any()):
+        raise ValueError(f"quantize_pair: a block of 32 weights reaches 2^16, beyond what {name} with block exponents "
+                         "up to 13 represents")
+    _, exponent = torch.frexp(amax)          # amax = m 2^exponent with 0.5 <= m < 1: floor(log2 amax) = exponent - 1
+    e = torch.where(amax > 0, (exponent - 3).clamp(e_min, 13), torch.zeros_like(exponent))
+    return torch.ldexp(blocks, -e[:, :, None]), e
+
+
 # 2 |v| for the e2m1 magnitudes v = 0, .5, 1, 1.5, 2, 3, 4, 6 -> the three low bits of the code
 _E2M1_CODE_OF_TWICE = (0, 1, 2, 3, 4, 0, 5, 0, 6, 0, 0, 0, 7)
 
@@ -344,18 +324,7 @@ def _quantize_mxfp4(w: torch.Tensor):
     2 * 2^e (an error of at most 2^e <= amax / 4), and a weight beyond 6 * 2^e errs by less than amax - 6 * 2^e <
     amax / 4.  Returns (codes [rows, cols / 2], scales [rows, cols / 32]), uint8."""
     rows, cols = w.shape
-    if cols % _W4_BLOCK:
-        raise ValueError(f"quantize_pair: mxfp4 needs rows of a multiple of {_W4_BLOCK} weights, got {cols}")
-    blocks = w.detach().float().reshape(rows, cols // _W4_BLOCK, _W4_BLOCK)
-    amax = blocks.abs().amax(dim=-1)
-    if not bool(torch.isfinite(amax).all()):
-        raise ValueError("quantize_pair: the factors hold non-finite values")
-    if bool((amax >= 2.0 ** 16).any()):
-        raise ValueError("quantize_pair: a block of 32 weights reaches 2^16, beyond what mxfp4 with block exponents "
-                         "up to 13 represents")
-    _, exponent = torch.frexp(amax)          # amax = m 2^exponent with 0.5 <= m < 1: floor(log2 amax) = exponent - 1
-    e = torch.where(amax > 0, (exponent - 3).clamp(-13, 13), torch.zeros_like(exponent))
-    v = torch.ldexp(blocks, -e[:, :, None])  # exact
+    v, e = _mx_block_exponents(w, _W4_FORMAT, -13)
     a = v.abs().clamp(max=6.0)
     # round to nearest, ties to even, on the grid's three step sizes (.5 below 2, 1 below 4, 2 up to 6): torch.round is
     # ties-to-even, and an even multiple of the step is the code with mantissa bit 0
@@ -384,18 +353,7 @@ def _quantize_mxfp6_e2m3(w: torch.Tensor):
     weight beyond 7.5 * 2^e errs by less than 8 * 2^e - 7.5 * 2^e = 0.5 * 2^e <= amax / 8.  Returns
     (codes [rows, 3 cols / 4], scales [rows, cols / 32]), uint8."""
     rows, cols = w.shape
-    if cols % _W6_BLOCK:
-        raise ValueError(f"quantize_pair: mxfp6_e2m3 needs rows of a multiple of {_W6_BLOCK} weights, got {cols}")
-    blocks = w.detach().float().reshape(rows, cols // _W6_BLOCK, _W6_BLOCK)
-    amax = blocks.abs().amax(dim=-1)
-    if not bool(torch.isfinite(amax).all()):
-        raise ValueError("quantize_pair: the factors hold non-finite values")
-    if bool((amax >= 2.0 ** 16).any()):
-        raise ValueError("quantize_pair: a block of 32 weights reaches 2^16, beyond what mxfp6_e2m3 with block exponents "
-                         "up to 13 represents")
-    _, exponent = torch.frexp(amax)          # amax = m 2^exponent with 0.5 <= m < 1: floor(log2 amax) = exponent - 1
-    e = torch.where(amax > 0, (exponent - 3).clamp(-11, 13), torch.zeros_like(exponent))
-    v = torch.ldexp(blocks, -e[:, :, None])  # exact
+    v, e = _mx_block_exponents(w, _W6_FORMAT, -11)
     a = v.abs().clamp(max=7.5)
     # round to nearest, ties to even, on the grid's three step sizes (.125 below 2, .25 below 4, .5 up to 7.5):
     # torch.round is ties-to-even, and an even multiple of the step is a code with an even mantissa
@@ -409,9 +367,9 @@ def _quantize_mxfp6_e2m3(w: torch.Tensor):
 
 def _quantize_pair_mx(first, second, dtype, cls, quantize, name):
     n_i, r, n_o = first.in_features, first.out_features, second.out_features
-    if n_i % _W4_BLOCK:
-        raise ValueError(f"quantize_pair: {name} needs in_features to be a multiple of {_W4_BLOCK}, got {n_i}")
-    stored = -(-r // _W4_BLOCK) * _W4_BLOCK      # zero rows of A and zero columns of B up to a whole block: no result changes
+    if n_i % _MX_BLOCK:
+        raise ValueError(f"quantize_pair: {name} needs in_features to be a multiple of {_MX_BLOCK}, got {n_i}")
+    stored = -(-r // _MX_BLOCK) * _MX_BLOCK      # zero rows of A and zero columns of B up to a whole block: no result changes
     wa, wb = first.weight.detach(), second.weight.detach()
     if stored != r:
         wa = torch.cat([wa, wa.new_zeros(stored - r, n_i)], 0)

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import dataclasses
 import os
 from typing import Optional, Sequence
 
@@ -497,11 +498,86 @@ def lowrank_decode_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq:
     return y
 
 
-# The pair with OCP MXFP4 factors (packed e2m1 codes, one e8m0 scale byte per 32 weights of a row) at decode shapes runs
-# on ptd_lowrank_decode_w4: the same two weight-streaming kernels on a quarter of the 16-bit pair's bytes.
-# PTD_LOWRANK_DECODE_W4=0 sends every shape through the torch expression of torch.ops.ptdeco_amd.lowrank_forward_w4.
+# The pair with OCP MX factors at decode shapes -- MXFP4 (packed e2m1 codes, 16 bytes per block of 32 weights) on
+# ptd_lowrank_decode_w4, MXFP6 (e2m3, packed 6-bit codes, 24 bytes per block) on ptd_lowrank_decode_w6, one e8m0 scale
+# byte per block in both: the same two weight-streaming kernels on a quarter / on 0.39 of the 16-bit pair's bytes.
+# PTD_LOWRANK_DECODE_W4=0 / PTD_LOWRANK_DECODE_W6=0 sends every shape of that format through the torch expression of
+# torch.ops.ptdeco_amd.lowrank_forward_w4 / _w6.
 _DECODE_W4 = os.environ.get("PTD_LOWRANK_DECODE_W4", "1") != "0"
+_DECODE_W6 = os.environ.get("PTD_LOWRANK_DECODE_W6", "1") != "0"
 W4_MXFP4 = 0
+W6_MXFP6_E2M3 = 0
+
+
+@dataclasses.dataclass(frozen=True)
+class _MxFormat:
+    """What differs between the MX decode entries (the formats of csrc/lowrank_w4.h and csrc/lowrank_w6.h)."""
+    name: str            # for messages
+    entry: str           # ptd_<entry> and ptd_<entry>_workspace_bytes
+    block_bytes: int     # code bytes per 32 weights
+    pitch: int           # a code row's pitch is a multiple of this many bytes
+    align: int           # the codes' base address is a multiple of this many bytes
+    code: int            # w_format of the entry
+    switch: str          # the module attribute (read from the environment once, at import) that enables the entry
+
+    def row_bytes(self, n: int) -> int:
+        return n // 32 * self.block_bytes
+
+
+_MXFP4 = _MxFormat("MXFP4", "lowrank_decode_w4", 16, 16, 16, W4_MXFP4, "_DECODE_W4")
+_MXFP6 = _MxFormat("MXFP6", "lowrank_decode_w6", 24, 8, 8, W6_MXFP6_E2M3, "_DECODE_W6")
+
+
+def _mx_decode_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
+    if not globals()[fmt.switch]:
+        return False
+    ts = (x2d, Aq, ea, Bq, eb) if bias is None else (x2d, Aq, ea, Bq, eb, bias)
+    for t in ts:
+        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
+            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
+    if any(t.dim() != 2 for t in (x2d, Aq, ea, Bq, eb)) or any(t.dtype != torch.uint8 for t in (Aq, ea, Bq, eb)):
+        return False
+    if x2d.dtype not in (torch.bfloat16, torch.float16):
+        return False
+    (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
+    if not 1 <= T <= _DECODE_MAX_T or n_o < 1 or r < 32 or n_i < 32 or n_i % 32 or r % 32:
+        return False
+    if (tuple(Aq.shape) != (r, fmt.row_bytes(n_i)) or tuple(ea.shape) != (r, n_i // 32)
+            or tuple(Bq.shape) != (n_o, fmt.row_bytes(r)) or tuple(eb.shape) != (n_o, r // 32)):
+        return False
+    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o or bias.dtype != x2d.dtype
+                             or (n_o > 1 and bias.stride(0) != 1)):
+        return False
+    for t, vec, align in ((x2d, 8, 16), (Aq, fmt.pitch, fmt.align), (Bq, fmt.pitch, fmt.align)):
+        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % align:
+            return False
+    for e in (ea, eb):
+        if (e.shape[1] > 1 and e.stride(1) != 1) or e.stride(0) < e.shape[1]:
+            return False
+    return True
+
+
+def _mx_decode(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> torch.Tensor:
+    _dev(x2d, Aq, ea, Bq, eb, bias)
+    x2d, Aq, ea, Bq, eb = _rows2d(x2d), _rows2d(Aq), _rows2d(ea), _rows2d(Bq), _rows2d(eb)
+    T, n_i = x2d.shape
+    r, n_o = Aq.shape[0], Bq.shape[0]
+    assert all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)) and n_i % 32 == 0 and r % 32 == 0
+    assert Aq.shape == (r, fmt.row_bytes(n_i)) and ea.shape == (r, n_i // 32)
+    assert Bq.shape == (n_o, fmt.row_bytes(r)) and eb.shape == (n_o, r // 32)
+    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
+    lib = _hip.load()
+    ws_bytes = getattr(lib, f"ptd_{fmt.entry}_workspace_bytes")(T, n_i, r, _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+    if bias is not None:
+        bias = bias.to(x2d.dtype).contiguous()
+    with torch.cuda.device(x2d.device):
+        rc = getattr(lib, f"ptd_{fmt.entry}")(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0),
+                                              ea.data_ptr(), ea.stride(0), r, Bq.data_ptr(), Bq.stride(0), eb.data_ptr(),
+                                              eb.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o, ws.data_ptr(), ws_bytes,
+                                              _code(x2d), fmt.code, _stream(x2d))
+    _hip.check(rc, f"ptd_{fmt.entry}")
+    return y
 
 
 def lowrank_decode_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -511,32 +587,7 @@ def lowrank_decode_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tens
     [n_o, r / 2] and eb [n_o, r / 32] uint8, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, code row pitches
     multiples of 16 bytes, x2d's a multiple of 8 elements, unit inner strides, x2d and the codes 16-byte aligned (the
     scale rows need no alignment)."""
-    if not _DECODE_W4:
-        return False
-    ts = (x2d, Aq, ea, Bq, eb) if bias is None else (x2d, Aq, ea, Bq, eb, bias)
-    for t in ts:
-        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
-            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
-    if any(t.dim() != 2 for t in (x2d, Aq, ea, Bq, eb)) or any(t.dtype != torch.uint8 for t in (Aq, ea, Bq, eb)):
-        return False
-    if x2d.dtype not in (torch.bfloat16, torch.float16):
-        return False
-    (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
-    if not 1 <= T <= _DECODE_MAX_T or n_o < 1 or r < 32 or n_i < 32 or n_i % 32 or r % 32:
-        return False
-    if (tuple(Aq.shape) != (r, n_i // 2) or tuple(ea.shape) != (r, n_i // 32) or tuple(Bq.shape) != (n_o, r // 2)
-            or tuple(eb.shape) != (n_o, r // 32)):
-        return False
-    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o or bias.dtype != x2d.dtype
-                             or (n_o > 1 and bias.stride(0) != 1)):
-        return False
-    for t, vec in ((x2d, 8), (Aq, 16), (Bq, 16)):
-        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % 16:
-            return False
-    for e in (ea, eb):
-        if (e.shape[1] > 1 and e.stride(1) != 1) or e.stride(0) < e.shape[1]:
-            return False
-    return True
+    return _mx_decode_serves(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_decode_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -546,33 +597,7 @@ def lowrank_decode_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq:
     scales clamped to [114, 140], all uint8): ptd_lowrank_decode_w4 (sums in f32, each rounded once to x2d's dtype).
     Operands the entry does not serve (``lowrank_decode_w4_serves``) raise; row t of the result depends on row t of x2d
     alone."""
-    _dev(x2d, Aq, ea, Bq, eb, bias)
-    x2d, Aq, ea, Bq, eb = _rows2d(x2d), _rows2d(Aq), _rows2d(ea), _rows2d(Bq), _rows2d(eb)
-    T, n_i = x2d.shape
-    r, n_o = Aq.shape[0], Bq.shape[0]
-    assert all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)) and n_i % 32 == 0 and r % 32 == 0
-    assert Aq.shape == (r, n_i // 2) and ea.shape == (r, n_i // 32) and Bq.shape == (n_o, r // 2) and eb.shape == (n_o, r // 32)
-    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
-    lib = _hip.load()
-    ws_bytes = lib.ptd_lowrank_decode_w4_workspace_bytes(T, n_i, r, _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    if bias is not None:
-        bias = bias.to(x2d.dtype).contiguous()
-    with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_decode_w4(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0), ea.data_ptr(),
-                                       ea.stride(0), r, Bq.data_ptr(), Bq.stride(0), eb.data_ptr(), eb.stride(0), n_o,
-                                       _ptr(bias), y.data_ptr(), n_o, ws.data_ptr(), ws_bytes, _code(x2d), W4_MXFP4,
-                                       _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_decode_w4")
-    return y
-
-
-# The pair with OCP MXFP6 (e2m3) factors (packed 6-bit codes, 24 bytes per block of 32 weights, one e8m0 scale byte per
-# block) at decode shapes runs on ptd_lowrank_decode_w6: the same two weight-streaming kernels on 0.39 of the 16-bit
-# pair's bytes.  PTD_LOWRANK_DECODE_W6=0 sends every shape through the torch expression of
-# torch.ops.ptdeco_amd.lowrank_forward_w6.
-_DECODE_W6 = os.environ.get("PTD_LOWRANK_DECODE_W6", "1") != "0"
-W6_MXFP6_E2M3 = 0
+    return _mx_decode(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_decode_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -582,32 +607,7 @@ def lowrank_decode_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tens
     [n_o, 3 r / 4] and eb [n_o, r / 32] uint8, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, code row pitches
     multiples of 8 bytes, x2d's a multiple of 8 elements, unit inner strides, x2d 16-byte and the codes 8-byte aligned
     (the scale rows need no alignment)."""
-    if not _DECODE_W6:
-        return False
-    ts = (x2d, Aq, ea, Bq, eb) if bias is None else (x2d, Aq, ea, Bq, eb, bias)
-    for t in ts:
-        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
-            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
-    if any(t.dim() != 2 for t in (x2d, Aq, ea, Bq, eb)) or any(t.dtype != torch.uint8 for t in (Aq, ea, Bq, eb)):
-        return False
-    if x2d.dtype not in (torch.bfloat16, torch.float16):
-        return False
-    (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
-    if not 1 <= T <= _DECODE_MAX_T or n_o < 1 or r < 32 or n_i < 32 or n_i % 32 or r % 32:
-        return False
-    if (tuple(Aq.shape) != (r, 3 * n_i // 4) or tuple(ea.shape) != (r, n_i // 32) or tuple(Bq.shape) != (n_o, 3 * r // 4)
-            or tuple(eb.shape) != (n_o, r // 32)):
-        return False
-    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o or bias.dtype != x2d.dtype
-                             or (n_o > 1 and bias.stride(0) != 1)):
-        return False
-    for t, vec, align in ((x2d, 8, 16), (Aq, 8, 8), (Bq, 8, 8)):
-        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % align:
-            return False
-    for e in (ea, eb):
-        if (e.shape[1] > 1 and e.stride(1) != 1) or e.stride(0) < e.shape[1]:
-            return False
-    return True
+    return _mx_decode_serves(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_decode_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -617,26 +617,7 @@ def lowrank_decode_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq:
     e8m0 block scales clamped to [116, 140], all uint8): ptd_lowrank_decode_w6 (sums in f32, each rounded once to x2d's
     dtype).  Operands the entry does not serve (``lowrank_decode_w6_serves``) raise; row t of the result depends on row
     t of x2d alone."""
-    _dev(x2d, Aq, ea, Bq, eb, bias)
-    x2d, Aq, ea, Bq, eb = _rows2d(x2d), _rows2d(Aq), _rows2d(ea), _rows2d(Bq), _rows2d(eb)
-    T, n_i = x2d.shape
-    r, n_o = Aq.shape[0], Bq.shape[0]
-    assert all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)) and n_i % 32 == 0 and r % 32 == 0
-    assert Aq.shape == (r, 3 * n_i // 4) and ea.shape == (r, n_i // 32)
-    assert Bq.shape == (n_o, 3 * r // 4) and eb.shape == (n_o, r // 32)
-    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
-    lib = _hip.load()
-    ws_bytes = lib.ptd_lowrank_decode_w6_workspace_bytes(T, n_i, r, _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    if bias is not None:
-        bias = bias.to(x2d.dtype).contiguous()
-    with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_decode_w6(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0), ea.data_ptr(),
-                                       ea.stride(0), r, Bq.data_ptr(), Bq.stride(0), eb.data_ptr(), eb.stride(0), n_o,
-                                       _ptr(bias), y.data_ptr(), n_o, ws.data_ptr(), ws_bytes, _code(x2d), W6_MXFP6_E2M3,
-                                       _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_decode_w6")
-    return y
+    return _mx_decode(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
 
 
 # Pairs that read one input at decode shapes (q / k / v, gate / up) run on ptd_lowrank_decode_group: two launches for the

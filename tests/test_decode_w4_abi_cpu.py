@@ -476,16 +476,18 @@ def test_w4_kernels_use_no_scratch_and_convert_in_registers(tmp_path):
     hipcc = shutil.which(os.environ.get("HIPCC", "hipcc"))
     if hipcc is None:
         pytest.skip("hipcc not on PATH")
-    out = tmp_path / "lowrank_decode_w4.s"
+    out = tmp_path / "lowrank_decode_mx.s"
     subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out),
-                    os.path.join(ROOT, "ptdeco_amd", "csrc", "lowrank_decode_w4.hip")], check=True, capture_output=True,
+                    os.path.join(ROOT, "ptdeco_amd", "csrc", "lowrank_decode_mx.hip")], check=True, capture_output=True,
                    timeout=600)
     text = out.read_text()
-    sizes = re.findall(r"\.set (\S*decode_w4_(?:xa|hb)_kernel\S*)\.private_seg_size, (\d+)", text)
-    assert len(sizes) >= 4, sizes           # two kernels x two element types (x the weight-load policy and the step)
     every = re.findall(r"\.set (\S+)\.private_seg_size, (\d+)", text)
+    # one kernel template, two formats: two kernels x two element types of each (x the weight-load policy and the step)
+    for fmt in ("MxFp4", "MxFp6"):
+        found = [name for name, _ in every if re.search(rf"decode_mx_(?:xa|hb)_kernel\S*{fmt}", name)]
+        assert len(found) >= 4, (fmt, found)
     for name, size in every:
         assert int(size) == 0, f"{name} keeps {size} bytes of scratch"
     for needed in ("v_mfma_f32_16x16x32_bf16", "v_mfma_f32_16x16x32_f16", "v_cvt_scalef32_pk_bf16_fp4",
-                   "v_cvt_scalef32_pk_f16_fp4"):
+                   "v_cvt_scalef32_pk_f16_fp4", "v_cvt_scalef32_pk32_bf16_fp6", "v_cvt_scalef32_pk32_f16_fp6"):
         assert needed in text, needed

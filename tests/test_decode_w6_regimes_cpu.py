@@ -21,7 +21,7 @@ def test_header_declares_the_family_and_keeps_the_fields():
 
 
 def test_plan_of_known_shapes():
-    """Figures worked out by hand from w4_xa_split, w4_xa_blocks and w4_hb_blocks, whose block size this format shares."""
+    """Figures worked out by hand from mx_xa_split, mx_xa_blocks and mx_hb_blocks, which MXFP4 shares."""
     bf16 = torch.bfloat16
     p = pw.plan(16, 64, 32, 7, bf16)            # one slab of 512: waves of 128, the first holds the row's two blocks
     assert (p["nslabs"], p["kchunk"], p["xa_grid_x"], p["xa_grid_y"], p["xa_grid_z"]) == (1, 512, 2, 1, 1)

@@ -43,7 +43,7 @@ def test_library_exports_the_entry_and_it_needs_no_device():
 
 
 def test_plan_of_known_shapes():
-    """Figures worked out by hand from the rules (xa_split, hb_grid, the 2 KB chunk of h, launch_w4's U)."""
+    """Figures worked out by hand from the rules (xa_split, hb_grid, the 2 KB chunk of h, launch_mx's U)."""
     bf16, f32 = torch.bfloat16, torch.float32
     p = pr.plan("decode", 4, 4096, 1024, 4096, bf16)      # 64 row tiles: four slabs of 1024; 256 tiles, one each
     assert (p["nslabs"], p["kchunk"], p["xa_grid_x"], p["xa_grid_y"], p["xa_grid_z"]) == (4, 1024, 64, 4, 1)

@@ -21,7 +21,7 @@ def test_header_declares_the_family_and_keeps_the_fields():
 
 
 def test_plan_of_known_shapes():
-    """Figures worked out by hand from sk_xa_split and w4_sk_scale_bytes."""
+    """Figures worked out by hand from sk_xa_split and mx_sk_scale_bytes."""
     bf16 = torch.bfloat16
     p = pw.plan(33, 224, 32, 7, bf16)           # one slab of 256: waves of 64, the last holds 32 k; seven blocks
     assert (p["nslabs"], p["kchunk"], p["xa_grid_x"], p["xa_grid_y"], p["xa_grid_z"]) == (1, 256, 1, 1, 1)
