@@ -155,10 +155,15 @@ int ptd_cov_finalize(const void* E, int64_t ldE, int E_dtype, const void* ey, in
  *     which is an eigenvector of the cluster.  Refused -- and handed to the solver below -- only when requested
  *     eigenvalues elsewhere are closer than 1e-13 |A| (PTD_EIGH_LONG_CHAINS=0, PTD_EIGH_NULL_COMPLETION=0:
  *     the earlier, stricter rule);
- *   one-sided block Jacobi on the f64 matrix cores: any PSD matrix.
+ *   one-sided block Jacobi on the f64 matrix cores: any PSD matrix.  It diagonalises A^2, so an indefinite A (told
+ *     from a semi-definite one by sum |lambda_i| - trace(A) > 16 n eps sum |lambda_i|) is solved a second time as
+ *     A + s I, s just above |A|, and the eigenvalues are shifted back: absolute accuracy eps (|A| + s) for a matrix
+ *     the test detects.  Below its threshold it is blind: negative eigenvalues whose moduli sum to less than
+ *     8 n eps sum |lambda_i| pass for the rounding of a semi-definite matrix and are returned as + |lambda| (up to
+ *     ~4e-11 |A| at n = 130).  The tridiagonal route needs no sign.
  * NOT fully asynchronous: synchronises `stream` to read small decisions back (cluster
  * check, Jacobi convergence flag).  sweeps_out (host pointer, may be NULL) receives the number
- * of Jacobi sweeps (0 for the tridiagonal route).
+ * of Jacobi sweeps (0 for the tridiagonal route; the sum of both passes, up to 80, for an indefinite matrix).
  * Replaces `torch.linalg.eigh`: dwain.py:162, falor.py:207. */
 size_t ptd_eigh_workspace_bytes(int64_t n);
 int ptd_eigh(const double* A, int64_t lda, int64_t n, double* evals, double* evecs, int64_t ldv,

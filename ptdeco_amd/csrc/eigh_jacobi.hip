@@ -393,7 +393,7 @@ __global__ __launch_bounds__(256) void jac_update_kernel(double* __restrict__ G,
 // ---------------------------------------------------------------------------
 // post-processing: eigenvalue = row norm, ascending order, eigenvectors to columns
 __global__ void jac_norm_kernel(const double* __restrict__ G, int np, int n, double* __restrict__ norms,
-                                double* __restrict__ lambdas, int squared) {
+                                double* __restrict__ lambdas, int squared, double shift) {
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= n) return;
   const int lane = threadIdx.x & 63;
@@ -405,8 +405,15 @@ __global__ void jac_norm_kernel(const double* __restrict__ G, int np, int n, dou
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   if (lane == 0) {
     norms[row] = sqrt(s);
-    lambdas[row] = squared ? s : sqrt(s);  // rows of L^T carry sqrt(lambda), rows of A carry lambda
+    // rows of L^T carry sqrt(lambda), rows of A carry lambda (of A + shift I in the second pass of an indefinite A)
+    lambdas[row] = (squared ? s : sqrt(s)) - shift;
   }
+}
+
+// G += shift I on the n rows of the matrix (the padding keeps the identity jac_gather_kernel put there)
+__global__ void jac_shift_kernel(double* __restrict__ G, int np, int n, double shift) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) G[(int64_t)i * np + i] += shift;
 }
 
 __global__ void jac_rank_kernel(const double* __restrict__ norms, const double* __restrict__ lambdas, int n,
@@ -577,40 +584,90 @@ int eigh_jacobi(const double* A, int64_t lda, int64_t n, int64_t k, double* eval
   }
   PTD_CHECK_LAUNCH("jac_setup");
 
-  int sweeps = 0;
+  int sweeps = 0;   // of both passes together where an indefinite matrix takes a second one
   bool converged = false;
-  for (; sweeps < max_sweeps && !converged;) {
-    PTD_CHECK_HIP(hipMemsetAsync(conv, 0, 8, st));
-    for (int r = 0; r < p.nb - 1; ++r) {
-      mark(r, 0);
-      hipLaunchKernelGGL(jac_gram_kernel, dim3(p.ksplit, p.pairs), dim3(256), 0, st, G, p.np, p.nb, r, p.kcols,
-                         Sp);
-      mark(r, 1);
-      hipLaunchKernelGGL(jac_inner_kernel, dim3(p.pairs), dim3(IN_T), 0, st, Sp, p.ksplit, tol, inner_sweeps,
-                         (cross_only && r > 0) ? 1 : 0, Q, skip, conv);
-      mark(r, 2);
-      hipLaunchKernelGGL(jac_update_kernel, dim3(p.chunks, p.pairs), dim3(256), 0, st, G, p.np, p.nb, r,
-                         p.tiles_per_wg, Q, skip);
-      mark(r, 3);
+  // up to max_sweeps sweeps over G; sets `converged`
+  auto run_sweeps = [&]() -> int {
+    const int sweeps_end = sweeps + max_sweeps;
+    converged = false;
+    for (; sweeps < sweeps_end && !converged;) {
+      PTD_CHECK_HIP(hipMemsetAsync(conv, 0, 8, st));
+      for (int r = 0; r < p.nb - 1; ++r) {
+        mark(r, 0);
+        hipLaunchKernelGGL(jac_gram_kernel, dim3(p.ksplit, p.pairs), dim3(256), 0, st, G, p.np, p.nb, r, p.kcols,
+                           Sp);
+        mark(r, 1);
+        hipLaunchKernelGGL(jac_inner_kernel, dim3(p.pairs), dim3(IN_T), 0, st, Sp, p.ksplit, tol, inner_sweeps,
+                           (cross_only && r > 0) ? 1 : 0, Q, skip, conv);
+        mark(r, 2);
+        hipLaunchKernelGGL(jac_update_kernel, dim3(p.chunks, p.pairs), dim3(256), 0, st, G, p.np, p.nb, r,
+                           p.tiles_per_wg, Q, skip);
+        mark(r, 3);
+      }
+      PTD_CHECK_LAUNCH("jacobi sweep");
+      double h_conv = 0.0;
+      PTD_CHECK_HIP(hipMemcpyAsync(&h_conv, conv, 8, hipMemcpyDeviceToHost, st));
+      PTD_CHECK_HIP(hipStreamSynchronize(st));
+      ++sweeps;
+      converged = (h_conv <= quad);
+      if (debug) fprintf(stderr, "[ptd_eigh] n=%lld sweep %d max scaled off-diagonal %.3e\n", (long long)n, sweeps, h_conv);
+      if (stats) {
+        for (int r = 0; r < p.nb - 1; ++r)
+          for (int k = 0; k < 3; ++k) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[(size_t)4 * r + k], ev[(size_t)4 * r + k + 1]);
+            stats->ms[k] += ms;
+            stats->launches[k] += 1;
+          }
+        const double pair_flops = 2.0 * JP * JP * (double)p.np;  // one 64 x 64 x np product
+        stats->work[0] += (double)(p.nb - 1) * p.pairs * pair_flops;
+        stats->work[2] += (double)(p.nb - 1) * p.pairs * pair_flops;  // upper bound: skipped pairs do none
+      }
     }
-    PTD_CHECK_LAUNCH("jacobi sweep");
-    double h_conv = 0.0;
-    PTD_CHECK_HIP(hipMemcpyAsync(&h_conv, conv, 8, hipMemcpyDeviceToHost, st));
+    return PTD_OK;
+  };
+  {
+    const int rc = run_sweeps();
+    if (rc != PTD_OK) return rc;
+  }
+  // The rotations diagonalise G G^T = A^2, so what the rows carry is |lambda_i|: right for the positive semi-definite
+  // matrices this solver was written for, silently wrong for an indefinite one (and where lambda and -lambda' have
+  // nearly the same modulus not even the vectors are eigenvectors of A).  A matrix that failed the Cholesky test may
+  // be either; the trace tells them apart: sum |lambda_i| - trace(A) is twice the sum of the negative eigenvalues'
+  // moduli, and rounding alone (~sqrt(n) eps a term) when there are none.  An indefinite A is solved again as
+  // A + s I with s just above max |lambda_i| = |A| (known from the first pass): positive definite, same eigenvectors,
+  // eigenvalues back by - s, absolute accuracy eps (|A| + s).  The test is blind below its threshold: negative
+  // eigenvalues whose moduli sum to less than 8 n_pad eps sum |lambda_i| (about 4e-11 |A| at n = 130 when all
+  // eigenvalues are of the size of |A|) pass for the rounding of a semi-definite matrix and come back as + |lambda|,
+  // mixed with a positive eigenvalue of the same modulus if there is one.  The threshold cannot go below the rounding
+  // of the two sums, ~sqrt(n) eps each, without sending semi-definite matrices through a second pass.
+  double shift = 0.0;
+  if (!use_chol && converged) {
+    double* dg = Q;   // (n doubles of scratch: the rotation matrices are dead between sweeps)
+    hipLaunchKernelGGL(jac_norm_kernel, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, st, G, p.np, (int)n, norms,
+                       lambdas, 0, 0.0);
+    hipLaunchKernelGGL(jac_diag_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, A, lda, (int)n, dg);
+    PTD_CHECK_LAUNCH("jacobi sign test");
+    std::vector<double> h((size_t)2 * n);
+    PTD_CHECK_HIP(hipMemcpyAsync(h.data(), norms, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    PTD_CHECK_HIP(hipMemcpyAsync(h.data() + n, dg, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     PTD_CHECK_HIP(hipStreamSynchronize(st));
-    ++sweeps;
-    converged = (h_conv <= quad);
-    if (debug) fprintf(stderr, "[ptd_eigh] n=%lld sweep %d max scaled off-diagonal %.3e\n", (long long)n, sweeps, h_conv);
-    if (stats) {
-      for (int r = 0; r < p.nb - 1; ++r)
-        for (int k = 0; k < 3; ++k) {
-          float ms = 0.f;
-          (void)hipEventElapsedTime(&ms, ev[(size_t)4 * r + k], ev[(size_t)4 * r + k + 1]);
-          stats->ms[k] += ms;
-          stats->launches[k] += 1;
-        }
-      const double pair_flops = 2.0 * JP * JP * (double)p.np;  // one 64 x 64 x np product
-      stats->work[0] += (double)(p.nb - 1) * p.pairs * pair_flops;
-      stats->work[2] += (double)(p.nb - 1) * p.pairs * pair_flops;  // upper bound: skipped pairs do none
+    double sum_abs = 0.0, trace = 0.0, top = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+      sum_abs += h[(size_t)i];
+      trace += h[(size_t)(n + i)];
+      top = std::max(top, h[(size_t)i]);
+    }
+    if (sum_abs - trace > 16.0 * (double)p.np * 2.220446049250313e-16 * sum_abs) {
+      shift = top * (1.0 + 1e-6);
+      if (debug)
+        fprintf(stderr, "[ptd_eigh] n=%lld indefinite (sum |lambda| %.17g, trace %.17g): again with A + %.6g I\n",
+                (long long)n, sum_abs, trace, shift);
+      hipLaunchKernelGGL(jac_gather_kernel, dim3(2048), dim3(256), 0, st, A, lda, (int)n, perm, G, p.np);
+      hipLaunchKernelGGL(jac_shift_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, G, p.np, (int)n, shift);
+      PTD_CHECK_LAUNCH("jacobi shifted restart");
+      const int rc = run_sweeps();
+      if (rc != PTD_OK) return rc;
     }
   }
   if (stats) {
@@ -626,7 +683,7 @@ int eigh_jacobi(const double* A, int64_t lda, int64_t n, int64_t k, double* eval
   if (sweeps_out) *sweeps_out = sweeps;
 
   hipLaunchKernelGGL(jac_norm_kernel, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, st, G, p.np, (int)n, norms,
-                     lambdas, use_chol ? 1 : 0);
+                     lambdas, use_chol ? 1 : 0, shift);
   hipLaunchKernelGGL(jac_rank_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, norms, lambdas, (int)n,
                      inv, evals);
   hipLaunchKernelGGL(jac_scatter_kernel, dim3((unsigned)ceil_div(k, 32), (unsigned)ceil_div(n, 32)), dim3(256), 0,

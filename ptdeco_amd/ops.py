@@ -145,7 +145,8 @@ EIGH_PROFILE: Optional[list] = None
 
 
 def eigh(A: torch.Tensor, k: Optional[int] = None, all_values: bool = True) -> tuple[torch.Tensor, torch.Tensor]:
-    """(eigenvalues [n] ascending, eigenvectors in columns) of a symmetric PSD f64 (or f32: f32 results, f64 arithmetic) matrix.
+    """(eigenvalues [n] ascending, eigenvectors in columns) of a symmetric f64 (or f32: f32 results, f64 arithmetic) matrix
+    -- positive semi-definite in the drivers; an indefinite one costs the Jacobi route a second pass.
 
     With ``k`` only the eigenvectors of the k largest eigenvalues are formed: the second result is
     [n, k] and its column c belongs to eigenvalue n - k + c, so ``v[:, v.shape[1] - r:]`` is the
