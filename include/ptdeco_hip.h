@@ -48,7 +48,8 @@ extern "C" {
                              *    ptd_lowrank_decode_w4_workspace_bytes, ptd_lowrank_decode_w4,
                              *    ptd_lowrank_plan,
                              *    ptd_lowrank_skinny_w4_workspace_bytes, ptd_lowrank_skinny_w4,
-                             *    ptd_lowrank_decode_w6_workspace_bytes, ptd_lowrank_decode_w6) */
+                             *    ptd_lowrank_decode_w6_workspace_bytes, ptd_lowrank_decode_w6,
+                             *    ptd_lowrank_skinny_w6_workspace_bytes, ptd_lowrank_skinny_w6) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -516,6 +517,27 @@ int ptd_lowrank_decode_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                           const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
                           void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 
+/* The pair with OCP MXFP6 (e2m3) factors (arguments, formats and semantics of ptd_lowrank_decode_w6, clamp to
+ * [116, 140] included: h and y from f32 sums, each rounded ONCE; no per-row scales) for 32 <= T <=
+ * PTD_LOWRANK_SKINNY_W6_MAX_T tokens, with the structure of ptd_lowrank_skinny_w4 -- the same kernel template: three
+ * launches on the caller's stream (first product into f32 slabs of a K split that depends on (n_i, r) alone, slab sum
+ * into a 16-bit h, second product with the bias).  A lane's 12-byte load is half an MX block (16 six-bit codes),
+ * converted to D in registers by one instruction that applies the clamped block scale; no dequantised copy is kept; row
+ * t of y depends on row t of x alone, bit for bit, whatever T is.  Served: dtype bf16 / f16, w_format
+ * PTD_W6_MXFP6_E2M3, 32 <= T <= PTD_LOWRANK_SKINNY_W6_MAX_T, r >= 32, n_i and r multiples of 32, lda and ldb multiples
+ * of 8 bytes (lda >= 3 n_i / 4, ldb >= 3 r / 4), ldsa >= n_i / 32 and ldsb >= r / 32 (the scale rows need no alignment),
+ * ldx a multiple of 8, x 16-byte aligned, Aq and Bq 8-byte aligned, bias 2-byte aligned and optional, n_i < 2^30,
+ * r < 2^27, 1 <= n_o < 2^30.  Anything else returns PTD_ERR_UNSUPPORTED before a kernel is launched; null pointers, a
+ * leading dimension below its row length or a misaligned workspace PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.
+ * The workspace holds the slabs and h (the formula of ptd_lowrank_skinny_w4_workspace_bytes).  The cap is measured
+ * (profiles/pair_skinny_w6.json).  No reference counterpart. */
+#define PTD_LOWRANK_SKINNY_W6_MAX_T 96
+size_t ptd_lowrank_skinny_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int ptd_lowrank_skinny_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                          const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
+                          const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
+                          void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+
 /* The gated pair of a decomposed MLP at the same 32 <= T <= 96 tokens in bf16 / f16, y = act(gate(x)) * up(x) (arguments
  * and activations as ptd_lowrank_decode_gated), in three launches on the caller's stream: both first products, both
  * slab sums, then a kernel that forms both second products for the same 32 rows and 64 tokens and applies the activation
@@ -542,7 +564,8 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
  * ptd_lowrank_skinny_gated take the plan of that member alone), PTD_PLAN_SKINNY_W8, PTD_PLAN_SKINNY_W4 (xa_u and hb_u:
  * the scale bytes of one load, 1 or 2; the tail fields: blocks of a row % that -- non-zero: the last block's scale byte
  * comes out of the clamped, shifted load), PTD_PLAN_DECODE_W6 (ptd_lowrank_decode_w6: every field with the meaning
- * PTD_PLAN_DECODE_W4 gives it, "MXFP4" below read as "MXFP4 and MXFP6").  Writes out[PTD_PLAN_*] for the
+ * PTD_PLAN_DECODE_W4 gives it, "MXFP4" below read as "MXFP4 and MXFP6"), PTD_PLAN_SKINNY_W6 (ptd_lowrank_skinny_w6: every
+ * field with the meaning PTD_PLAN_SKINNY_W4 gives it -- the two share one kernel template).  Writes out[PTD_PLAN_*] for the
  * PTD_PLAN_LEN indices below and returns PTD_PLAN_LEN; PTD_ERR_UNSUPPORTED where the family does not serve the shape or
  * the family is unknown, PTD_ERR_INVALID for a null `out` or cap < PTD_PLAN_LEN.  "First product" is x A^T into K slabs,
  * "second" h B^T.  A wave's "load step" is the k its 64 lanes cover with one 16-byte load each (32 for bf16 / f16, 16 for
@@ -555,6 +578,7 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
 #define PTD_PLAN_SKINNY_W8 4
 #define PTD_PLAN_SKINNY_W4 5
 #define PTD_PLAN_DECODE_W6 6
+#define PTD_PLAN_SKINNY_W6 7
 #define PTD_PLAN_NSLABS 0             /* K slabs of the first product */
 #define PTD_PLAN_KCHUNK 1             /* k of one slab (four wave ranges of kchunk / 4) */
 #define PTD_PLAN_XA_GRID_X 2          /* first product: row tiles, */

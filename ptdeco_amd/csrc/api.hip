@@ -739,6 +739,25 @@ int ptd_lowrank_skinny_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                            static_cast<hipStream_t>(stream));
 }
 
+size_t ptd_lowrank_skinny_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
+  return lowrank_skinny_w6_workspace_bytes(T, n_i, r, dtype);
+}
+
+int ptd_lowrank_skinny_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                          const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                          int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
+                          int dtype, int w_format, void* stream) {
+  const int rc = mx_entry_checks("ptd_lowrank_skinny_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
+                                 ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4),
+                                 lowrank_skinny_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                 "PTD_W6_MXFP6_E2M3, 32 <= T <= " PTD_STR(PTD_LOWRANK_SKINNY_W6_MAX_T)
+                                 ", r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
+                                 lowrank_skinny_w6_workspace_bytes(T, n_i, r, dtype));
+  if (rc != PTD_OK) return rc;
+  return lowrank_skinny_w6(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
+                           static_cast<hipStream_t>(stream));
+}
+
 int ptd_lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap) {
   PTD_REQUIRE(out, "ptd_lowrank_plan: null pointer");
   PTD_REQUIRE(cap >= PTD_PLAN_LEN, "ptd_lowrank_plan: out holds %d values, the plan has %d", cap, PTD_PLAN_LEN);

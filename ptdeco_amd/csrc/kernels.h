@@ -132,13 +132,22 @@ int lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const 
                       int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
                       int64_t ldy, void* ws, int dtype, hipStream_t st);
 
-// lowrank_skinny_w4.hip: the MXFP4 pair of lowrank_decode_mx.hip at 32 <= T <= PTD_LOWRANK_SKINNY_W4_MAX_T tokens with the
+// lowrank_skinny_w4.hip (the kernel bodies: lowrank_skinny_mx.h): the MXFP4 pair of lowrank_decode_mx.hip at 32 <= T <= PTD_LOWRANK_SKINNY_W4_MAX_T tokens with the
 // structure of lowrank_skinny_w8.hip: three launches, a lane's 8-byte load is half a block, converted in registers with
 // its block scale (ptd_lowrank_skinny_w4)
 bool lowrank_skinny_w4_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
                               int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias);
 size_t lowrank_skinny_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
 int lowrank_skinny_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea,
+                      int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
+                      const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
+
+// lowrank_skinny_w6.hip: the same kernel bodies on the MXFP6 pair at 32 <= T <= PTD_LOWRANK_SKINNY_W6_MAX_T tokens: a
+// lane's 12-byte load is half a block, converted by one instruction with its block scale (ptd_lowrank_skinny_w6)
+bool lowrank_skinny_w6_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
+                              int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias);
+size_t lowrank_skinny_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype);
+int lowrank_skinny_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea,
                       int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
                       const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 

@@ -119,7 +119,7 @@ void plan_skinny(int* out, int64_t T, int64_t n_i, int64_t r, int64_t n_o) {
   out[PTD_PLAN_TOKEN_TILES] = tiles;
 }
 
-// lowrank_skinny_w4.hip: the skinny split and grids; the variant of each product is the scale bytes of one load
+// lowrank_skinny_mx.h (MXFP4 and MXFP6 alike): the skinny split and grids; the variant of each product is the scale bytes of one load
 void plan_skinny_w4(int* out, int64_t T, int64_t n_i, int64_t r, int64_t n_o) {
   plan_skinny(out, T, n_i, r, n_o);
   const int ua = mx_sk_scale_bytes(n_i), ub = mx_sk_scale_bytes(r);
@@ -169,6 +169,11 @@ int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int
       return PTD_OK;
     case PTD_PLAN_SKINNY_W4:
       if (!lowrank_skinny_w4_serves(T, n_i, r, n_o, dtype, PTD_W4_MXFP4, p, n_i, p, n_i / 2, p, r / 2, p))
+        return PTD_ERR_UNSUPPORTED;
+      plan_skinny_w4(out, T, n_i, r, n_o);
+      return PTD_OK;
+    case PTD_PLAN_SKINNY_W6:
+      if (!lowrank_skinny_w6_serves(T, n_i, r, n_o, dtype, PTD_W6_MXFP6_E2M3, p, n_i, p, 3 * (n_i / 4), p, 3 * (r / 4), p))
         return PTD_ERR_UNSUPPORTED;
       plan_skinny_w4(out, T, n_i, r, n_o);
       return PTD_OK;

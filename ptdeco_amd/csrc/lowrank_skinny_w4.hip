@@ -1,295 +1,56 @@
-// The low-rank pair at small batches (32 <= T <= SKW4_MAX_T tokens) with OCP MXFP4 factors (packed e2m1 codes, one e8m0
-// scale byte per 32 consecutive weights of a row): the structure of lowrank_skinny_w8.hip on the weight bytes and
-// semantics of lowrank_decode_mx.hip.
-//
-//   W^[i, k]                       = e2m1(code(W, i, k)) * 2^(clamp(e[i, k >> 5], 114, 140) - 127)
-//   skinny_w4_product<.., true>    slab_s[t, i] = sum_{k in K range s} x[t, k] A^[i, k]         (f32 partial sums, workspace)
-//   skinny_w4_combine              h[t, i] = round(slab_0 + slab_1 + ...)                       (slab order; 16-bit, workspace)
-//   skinny_w4_product<.., false>   y[t, o] = round(sum_j h[t, j] B^[o, j] + bias[o])            -> ptd_lowrank_skinny_w4
-//
-// Mapping.  The geometry of skinny_w8_product_kernel: a workgroup of four waves takes 32 weight rows (two 16-row
-// fragments per wave), a tile of 64 tokens (blockIdx.z) and one K range (blockIdx.y); its waves take a quarter of that
-// range each, in steps of SK_KW = 64 k, and are added through LDS in wave order.  The lane's k layout is the fp8
-// kernel's too: lane l holds row l & 15 and the 16 weights k = 16 (l >> 4) + 0..15 of the step.  In MXFP4 those are 8
-// bytes, half an MX block: ONE global_load_dwordx2 per row fragment and step, each dword of it the eight codes of one
-// v_mfma_f32_16x16x32 operand, converted in the lane by four v_cvt_scalef32_pk_{bf16,f16}_fp4 with the clamped block
-// scale as their scale operand (lowrank_w4.h; exact).  No dequantised copy of a factor exists anywhere.  The token
-// operand (x, then h) comes through the LDS image of lowrank_skinny.hip ([64 tokens][4 waves x 64 k], SK_PITCH bytes per
-// token), staged the same way, one step ahead.
-//
-// The token read.  The lane needs the same 32 contiguous bytes at 16 (l >> 4) elements of its token's line as in the fp8
-// kernel, so the read derived there carries over as it is: four ds_read_b64, in the order 0 1 2 3 where l >> 4 is even
-// and 1 0 3 2 where it is odd, every one conflict-free on this pitch ("MXFP4 factors at small batches").  The
-// k order inside an MFMA is free as long as both operands agree: the odd lane groups swap the 16-bit halves of each code
-// dword (k 4..7 before k 0..3: one v_alignbit per dword, before the conversion).
-//
-// The scales.  A step of a wave is two MX blocks: lane groups 0 and 1 use the scale of the first, 2 and 3 that of the
-// second.  The two bytes are one unaligned 16-bit load per fragment and step (scale rows have byte alignment only); its
-// address is clamped so that both bytes lie inside the row and the value is shifted accordingly -- reached where the
-// row's block count is odd.  A row of a single block (n_i = 32, r = 32) takes the one-byte instance: the choice is
-// mx_sk_scale_bytes of lowrank_mx.h, a function of the row length alone.  The clamp to [114, 140] is applied in the lane.
-//
-// Split, order and rounding.  sk_xa_split / slab_bytes of lowrank_skinny.h as they are: the slab count and every K range
-// depend on (n_i, r) alone, never on T, and a column of the MFMA's B operand only reaches the same column of its result,
-// so row t of y is a function of row t of x, bit for bit.  h and y are rounded once each.  Three plain launches on the
-// caller's stream, no floating-point atomics, one writer per output element.  No load sits under a branch: a weight
-// piece, scale or token piece outside the K range, the matrix or the token count is fetched from an address that exists
-// and replaced by zeros in registers (a zeroed code dword is 0.0 under any clamped scale; n_i and every K range are
-// multiples of 32, so a lane's 16-k piece is wholly inside or wholly outside).
-#include "common.h"
-#include "elem16.h"
-#include "kernels.h"
-#include "lowrank_skinny.h"
+// ptd_lowrank_skinny_w4: the MXFP4 instance of lowrank_skinny_mx.h -- the format's skinny trait (what a lane's piece
+// is in memory and how it becomes the two MFMA operands of a step), the names of its kernels and its C++ entry.
+// The piece is 8 bytes: ONE global_load_dwordx2 per row fragment and step, each dword of it the eight codes of one
+// v_mfma_f32_16x16x32 operand, converted by four v_cvt_scalef32_pk_{bf16,f16}_fp4 with the clamped block scale.
+#define SKINNY_MX_PRODUCT_KERNEL skinny_w4_product_kernel
+#define SKINNY_MX_COMBINE_KERNEL skinny_w4_combine_kernel
+#include "lowrank_skinny_mx.h"
 #include "lowrank_w4.h"
 
 namespace ptd {
 
 namespace {
 
-constexpr int SKW4_MAX_T = PTD_LOWRANK_SKINNY_W4_MAX_T;      // the cap of the MXFP4 route (measured: profiles/pair_skinny_w4.json)
+// What a lane's piece (16 codes, half an MX block) is in memory and how it becomes the A operands of the step's two
+// MFMAs, w[j] holding k = 8 j + 0..7 of the piece -- k 4..7 before k 0..3 in the odd lane groups.
+struct SkMxFp4 : MxFp4 {
+  static constexpr int MAX_T = PTD_LOWRANK_SKINNY_W4_MAX_T;      // the cap of the route (measured: profiles/pair_skinny_w4.json)
+  typedef u32x2 piece;                                           // 8 bytes: dword j the codes of operand j
+  static constexpr const char* XA_LAUNCH = "ptd_lowrank_skinny_w4 (first product)";      // (the launch trace's labels)
+  static constexpr const char* SUM_LAUNCH = "ptd_lowrank_skinny_w4 (slab sum)";
+  static constexpr const char* HB_LAUNCH = "ptd_lowrank_skinny_w4";
 
-static_assert(SK_KW == 2 * MX_BLOCK, "a wave's step is two MX blocks: 8 code bytes per lane");
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-// out[t, i] over the K range of blockIdx.y for rows 32 blockIdx.x + 0..31 and tokens 64 blockIdx.z + 0..63; W [R, K / 2]
-// code bytes with row pitch ldw, E [R, K / 32] scale bytes with row pitch ldse, U scale bytes per load (mx_sk_scale_bytes).
-// SLAB: f32 sums to out_f32[(blockIdx.y T + t) R + i]; otherwise round(sum + bias[i]) to y[t ldy + i].
-template <typename EL, bool SLAB, int U>
-__global__ __launch_bounds__(SK_THREADS) void skinny_w4_product_kernel(const elem* __restrict__ X, const int64_t ldx,
-                                                                       const int T, const int K,
-                                                                       const unsigned char* __restrict__ W,
-                                                                       const int64_t ldw,
-                                                                       const unsigned char* __restrict__ E,
-                                                                       const int64_t ldse, const int R, const int kchunk,
-                                                                       float* __restrict__ out_f32,
-                                                                       const elem* __restrict__ bias,
-                                                                       elem* __restrict__ y, const int64_t ldy) {
-  __shared__ __attribute__((aligned(16))) char lds[SK_LDS_BYTES];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int kw = kchunk >> 2;                         // a multiple of SK_KW
-  const int nsteps = kw / SK_KW;
-  const int kbase = blockIdx.y * kchunk;
-  const int kend = min(kbase + kchunk, K);            // (K, kchunk multiples of 32: a lane's 16 k are inside or outside)
-  const int tok0 = blockIdx.z * SK_TOK;
-  const int nblk = K / MX_BLOCK;                      // (>= U: mx_sk_scale_bytes)
-
-  // weights: this wave's k range, rows f * 16 + (lane & 15), 16 codes (8 bytes) per lane and step
-  int wk0, wkend;
-  xa_wave_range((int)blockIdx.y, kchunk, wave, K, wk0, wkend);
-  const int kl = 16 * (lane >> 4);
-  const bool swap = (lane >> 4) & 1;
-  const unsigned int rot = swap ? 16u : 0u;           // the odd groups' half-dword swap as a rotate
-  const int eb = (lane >> 5) & (U - 1);               // which of the step's two blocks this lane group is in
-  const unsigned char* wp[2];
-  const unsigned char* ep[2];
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    const int row = blockIdx.x * SK_ROWS + f * 16 + (lane & 15);
-    wp[f] = W + (int64_t)(row < R ? row : 0) * ldw;
-    ep[f] = E + (int64_t)(row < R ? row : 0) * ldse;
-  }
-  // token pieces: piece p = threadIdx.x + 256 q is token p >> 5 (= 8 q + threadIdx.x >> 5), wave range (p >> 3) & 3 and
-  // 16-byte piece p & 7 (both the same for every q)
-  const int xwr = (threadIdx.x >> 3) & 3;
-  const int xk0 = kbase + xwr * kw + 8 * (threadIdx.x & 7), xkend = min(kbase + (xwr + 1) * kw, kend);
-  const elem* xp[SK_PIECES];
-  bool xtok[SK_PIECES];
-#pragma unroll
-  for (int q = 0; q < SK_PIECES; ++q) {
-    const int t = tok0 + 8 * q + (int)(threadIdx.x >> 5);
-    xtok[q] = t < T;
-    xp[q] = X + (int64_t)(xtok[q] ? t : 0) * ldx;
+  // the piece that holds k (a multiple of 16) of the row at p
+  static __device__ __forceinline__ piece load(const unsigned char* p, const int k) {
+    return *reinterpret_cast<const u32x2*>(p + (k >> 1));
   }
 
-  u32x2 wn[2];
-  unsigned int en[2];
-  s16x8 xn[SK_PIECES];
-  auto issue = [&](int step) {          // every load is issued; what lies outside is fetched from k = 0 and zeroed
-    const int ks = wk0 + step * SK_KW;
-    // the step's U scale bytes in one load that stays inside the row (blocks ks / 32 + 0 .. U - 1; where the row's
-    // block count is odd its last block is the second byte of the load one block back: shifted down)
-    const int b = ks / MX_BLOCK, bl = min(b, nblk - U);
-    const int sh = 8 * (min(b - bl, U - 1) + eb);
+  template <typename EL>
+  static __device__ __forceinline__ void operands(const piece v, const float scale, const unsigned int rot, s16x8 (&w)[2]) {
 #pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const int k = ks + kl;
-      const bool ok = k < wkend;
-      const u32x2 v = *reinterpret_cast<const u32x2*>(wp[f] + ((ok ? k : 0) >> 1));
-      wn[f] = ok ? v : u32x2{};          // (code 0 is +0 under every clamped scale)
-      en[f] = mx_load_scales<U>(ep[f] + bl) >> sh;
-    }
-#pragma unroll
-    for (int q = 0; q < SK_PIECES; ++q) {
-      const int k = xk0 + step * SK_KW;
-      const bool ok = k < xkend;
-      const s16x8 v = *reinterpret_cast<const s16x8*>(xp[q] + (ok ? k : 0));
-      xn[q] = ok && xtok[q] ? v : s16x8{};
-    }
-  };
-
-  f32x4 acc[2][4];
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) acc[f][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // this lane's 32 bytes of a token's line as 8-byte pieces, read i at xo[i].  The four offsets are made opaque to the
-  // compiler one by one: knowing that two of them differ by 16 it fuses the pair into ds_read2_b64, which is banked
-  // modulo 32 dwords and costs four times the cycles of the ds_read_b64 the argument above is made for.
-  int xo[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    xo[i] = (lane & 15) * SK_PITCH + wave * (SK_KW * 2) + 2 * kl + 8 * (i ^ (int)swap);
-    asm volatile("" : "+v"(xo[i]));
+    for (int j = 0; j < 2; ++j) w[j] = w4_operand<EL>(__builtin_amdgcn_alignbit(v[j], v[j], rot), scale);
   }
-
-  issue(0);
-  for (int step = 0; step < nsteps; ++step) {
-    s16x8 w[2][2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const float scale = mx_scale<MxFp4>(en[f]);
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        w[f][j] = w4_operand<EL>(__builtin_amdgcn_alignbit(wn[f][j], wn[f][j], rot), scale);
-    }
-#pragma unroll
-    for (int q = 0; q < SK_PIECES; ++q) {
-      const int p = (int)threadIdx.x + SK_THREADS * q;
-      *reinterpret_cast<s16x8*>(lds + (p >> 5) * SK_PITCH + (p & 31) * 16) = xn[q];
-    }
-    __syncthreads();
-    issue(step + 1 < nsteps ? step + 1 : step);      // (the last step fetches itself again: no load under a branch)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      const int off = tt * 16 * SK_PITCH;
-      u32x2 p[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) p[i] = *reinterpret_cast<const u32x2*>(lds + xo[i] + off);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const u32x4 xv = {p[2 * j][0], p[2 * j][1], p[2 * j + 1][0], p[2 * j + 1][1]};
-#pragma unroll
-        for (int f = 0; f < 2; ++f) acc[f][tt] = EL::mfma16(w[f][j], __builtin_bit_cast(s16x8, xv), acc[f][tt]);
-      }
-    }
-    __syncthreads();
-  }
-
-  // the four waves' sums, added in wave order: wave w finishes accumulators 2 w and 2 w + 1 (a = 4 f + tt)
-  f32x4* red = reinterpret_cast<f32x4*>(lds);
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) red[(wave * 8 + f * 4 + tt) * 64 + lane] = acc[f][tt];
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int a = 2 * wave + i, f = a >> 2, tt = a & 3;
-    f32x4 sum = red[a * 64 + lane];
-    sum += red[(8 + a) * 64 + lane];
-    sum += red[(16 + a) * 64 + lane];
-    sum += red[(24 + a) * 64 + lane];
-    // result layout: column (token) = lane & 15, rows 4 (lane >> 4) + 0..3 -- R is a multiple of 32 for the slabs
-    const int t = tok0 + tt * 16 + (lane & 15);
-    const int row0 = blockIdx.x * SK_ROWS + f * 16 + 4 * (lane >> 4);
-    if (SLAB) {
-      if (t < T && row0 < R) *reinterpret_cast<f32x4*>(out_f32 + ((int64_t)blockIdx.y * T + t) * R + row0) = sum;
-    } else {
-      float bv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j)                     // (rows beyond R read the last row's bias; never stored)
-        bv[j] = bias ? EL::to_f32(bias[min(row0 + j, R - 1)]) : 0.f;
-      if (t < T) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (row0 + j < R) y[(int64_t)t * ldy + row0 + j] = EL::from_f32(sum[j] + bv[j]);
-      }
-    }
-  }
-}
-
-// h = round(slab_0 + slab_1 + ...), four elements per thread (r is a multiple of 4: the four share a token)
-template <typename EL>
-__global__ __launch_bounds__(SK_THREADS) void skinny_w4_combine_kernel(const float* __restrict__ slabs, const int nslabs,
-                                                                       const int64_t items, elem* __restrict__ h) {
-  const int64_t i = (int64_t)blockIdx.x * SK_THREADS + threadIdx.x;
-  const int64_t ic = min(i, items - 1);
-  f32x4 v[SK_MAX_SLABS];
-#pragma unroll
-  for (int s = 0; s < SK_MAX_SLABS; ++s)      // (all in flight together; a slab that does not exist: the last one again)
-    v[s] = *reinterpret_cast<const f32x4*>(slabs + ((int64_t)min(s, nslabs - 1) * items + ic) * 4);
-  f32x4 sum = v[0];
-#pragma unroll
-  for (int s = 1; s < SK_MAX_SLABS; ++s)
-    if (s < nslabs) sum += v[s];
-  if (i < items) {
-    uint2 p;
-    p.x = EL::pack2(sum[0], sum[1]);
-    p.y = EL::pack2(sum[2], sum[3]);
-    *reinterpret_cast<uint2*>(h + i * 4) = p;
-  }
-}
-
-template <typename EL>
-int launch_skinny_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea,
-                     int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
-                     const void* bias, void* y, int64_t ldy, void* ws, hipStream_t st) {
-  int nslabs, kchunk;
-  sk_xa_split(n_i, r, nslabs, kchunk);
-  float* slabs = static_cast<float*>(ws);
-  elem* h = reinterpret_cast<elem*>(static_cast<char*>(ws) + slab_bytes(T, r));
-  const unsigned tiles = (unsigned)ceil_div(T, SK_TOK);
-  const dim3 blk(SK_THREADS);
-  const dim3 g1((unsigned)ceil_div(r, SK_ROWS), (unsigned)nslabs, tiles);
-  auto xa = mx_sk_scale_bytes(n_i) == 2 ? skinny_w4_product_kernel<EL, true, 2> : skinny_w4_product_kernel<EL, true, 1>;
-  hipLaunchKernelGGL(xa, g1, blk, 0, st, static_cast<const elem*>(x), ldx, (int)T, (int)n_i,
-                     static_cast<const unsigned char*>(Aq), lda, static_cast<const unsigned char*>(ea), ldsa, (int)r,
-                     kchunk, slabs, (const elem*)nullptr, (elem*)nullptr, (int64_t)0);
-  PTD_CHECK_LAUNCH("ptd_lowrank_skinny_w4 (first product)");
-  const int64_t items = T * r / 4;
-  hipLaunchKernelGGL((skinny_w4_combine_kernel<EL>), dim3((unsigned)ceil_div(items, SK_THREADS)), blk, 0, st, slabs,
-                     nslabs, items, h);
-  PTD_CHECK_LAUNCH("ptd_lowrank_skinny_w4 (slab sum)");
-  const dim3 g2((unsigned)ceil_div(n_o, SK_ROWS), 1, tiles);
-  auto hb = mx_sk_scale_bytes(r) == 2 ? skinny_w4_product_kernel<EL, false, 2> : skinny_w4_product_kernel<EL, false, 1>;
-  hipLaunchKernelGGL(hb, g2, blk, 0, st, h, r, (int)T, (int)r, static_cast<const unsigned char*>(Bq), ldb,
-                     static_cast<const unsigned char*>(eb), ldsb, (int)n_o,
-                     (int)align_up((size_t)r, (size_t)SK_QUANTUM), (float*)nullptr, static_cast<const elem*>(bias),
-                     static_cast<elem*>(y), ldy);
-  PTD_CHECK_LAUNCH("ptd_lowrank_skinny_w4");
-  return PTD_OK;
-}
+  // what `operands` takes for the lane's swap: the odd groups' half-dword swap as a rotate
+  static __device__ __forceinline__ unsigned int swap_arg(const bool swap) { return swap ? 16u : 0u; }
+};
 
 }  // namespace
 
 bool lowrank_skinny_w4_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
                               int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias) {
-  if (dtype != PTD_BF16 && dtype != PTD_F16) return false;
-  if (w_format != PTD_W4_MXFP4) return false;
-  if (T < SK_MIN_T || T > SKW4_MAX_T || n_o < 1 || r < MX_BLOCK || n_i < MX_BLOCK) return false;
-  if (n_i % MX_BLOCK || r % MX_BLOCK || ldx % 8 || lda % 8 || ldb % 8) return false;
-  if (n_i >= (1ll << 30) || r >= (1ll << 27) || n_o >= (1ll << 30)) return false;      // (lowrank_skinny_serves' limits)
-  if (reinterpret_cast<uintptr_t>(bias) & 1) return false;
-  if ((reinterpret_cast<uintptr_t>(Aq) & 7) || (reinterpret_cast<uintptr_t>(Bq) & 7)) return false;
-  return aligned16(x);
+  return skinny_mx_serves<SkMxFp4>(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias);
 }
 
 size_t lowrank_skinny_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
   (void)n_i;
   (void)dtype;
-  if (T < 1 || r < 1) return 0;
-  // (the 16-bit entry's formula -- the bound over every split, then the 16-bit h: monotone in T and r)
-  return slab_bytes(T, r) + align_up((size_t)T * (size_t)r * 2, 256);
+  return skinny_mx_workspace_bytes(T, r);
 }
 
 int lowrank_skinny_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea,
                       int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
                       const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st) {
-  if (dtype == PTD_BF16)
-    return launch_skinny_w4<Bf16>(x, ldx, T, n_i, Aq, lda, ea, ldsa, r, Bq, ldb, eb, ldsb, n_o, bias, y, ldy, ws, st);
-  return launch_skinny_w4<F16>(x, ldx, T, n_i, Aq, lda, ea, ldsa, r, Bq, ldb, eb, ldsb, n_o, bias, y, ldy, ws, st);
+  return skinny_mx<SkMxFp4>(x, ldx, T, n_i, Aq, lda, ea, ldsa, r, Bq, ldb, eb, ldsb, n_o, bias, y, ldy, ws, dtype, st);
 }
 
 }  // namespace ptd

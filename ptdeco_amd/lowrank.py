@@ -264,13 +264,15 @@ class LowRankLinearW6(_LowRankLinearMX):
 
     On a ROCm device, for x of the module's dtype and no gradient wanted, ``forward`` calls
     ``torch.ops.ptdeco_amd.lowrank_forward_w6``: at 1 to 16 tokens the HIP kernels of ptd_lowrank_decode_w6 (0.39 of
-    the factor bytes of the 16-bit pair, 0.78 of the fp8 pair's, converted in registers), at any other token count the
-    torch expression on transient 16-bit copies of the factors.  Anything else (a CPU copy, another input dtype,
-    ``x.requires_grad``) evaluates that expression directly and says so once, at WARNING.  The format keeps fp8's three
-    mantissa bits: round to nearest gives a noise-to-signal ratio of about 1.6e-3 on Gaussian factors, fp8's class
-    (1.3 .. 1.5e-3) and a sixteenth of MXFP4's.  ``.to(device)`` moves the module; a dtype cast (``.half()``,
-    ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the packed buffers as they are.
-    Built by ``quantize_pair`` / ``quantize_pairs_in_place`` with ``"mxfp6_e2m3"``, or empty for ``load_state_dict``."""
+    the factor bytes of the 16-bit pair, 0.78 of the fp8 pair's, converted in registers), at 32 to
+    PTD_LOWRANK_SKINNY_W6_MAX_T tokens the three launches of ptd_lowrank_skinny_w6 on the same bytes (no dequantised
+    copy, capturable in a CUDA graph), at any other token count the torch expression on transient 16-bit copies of the
+    factors.  Both HIP routes give row t of y from row t of x alone, bit for bit.  Anything else (a CPU copy, another
+    input dtype, ``x.requires_grad``) evaluates that expression directly and says so once, at WARNING.  The format
+    keeps fp8's three mantissa bits: round to nearest gives a noise-to-signal ratio of about 1.6e-3 on Gaussian
+    factors, fp8's class (1.3 .. 1.5e-3) and a sixteenth of MXFP4's.  ``.to(device)`` moves the module; a dtype cast
+    (``.half()``, ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the packed buffers as
+    they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place`` with ``"mxfp6_e2m3"``, or empty for ``load_state_dict``."""
 
     _mx_name = "MXFP6"
     _forward_op = staticmethod(_lowrank_forward_w6)

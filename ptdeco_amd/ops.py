@@ -512,21 +512,26 @@ W6_MXFP6_E2M3 = 0
 
 @dataclasses.dataclass(frozen=True)
 class _MxFormat:
-    """What differs between the MX decode entries (the formats of csrc/lowrank_w4.h and csrc/lowrank_w6.h)."""
+    """What differs between the MX entries, decode and skinny (the formats of csrc/lowrank_w4.h and csrc/lowrank_w6.h)."""
     name: str            # for messages
-    entry: str           # ptd_<entry> and ptd_<entry>_workspace_bytes
+    entry: str           # ptd_<entry> and ptd_<entry>_workspace_bytes: the decode entry
     block_bytes: int     # code bytes per 32 weights
-    pitch: int           # a code row's pitch is a multiple of this many bytes
-    align: int           # the codes' base address is a multiple of this many bytes
-    code: int            # w_format of the entry
-    switch: str          # the module attribute (read from the environment once, at import) that enables the entry
+    pitch: int           # a code row's pitch is a multiple of this many bytes (decode; skinny: 8 for both formats)
+    align: int           # the codes' base address is a multiple of this many bytes (decode; skinny: 8)
+    code: int            # w_format of the entries
+    switch: str          # the module attribute (read from the environment once, at import) that enables the decode entry
+    skinny_entry: str    # ptd_<skinny_entry> and ptd_<skinny_entry>_workspace_bytes: the small-batch entry,
+    skinny_switch: str   #   the module attribute that enables it
+    skinny_cap: str      #   and the one that holds its largest T
 
     def row_bytes(self, n: int) -> int:
         return n // 32 * self.block_bytes
 
 
-_MXFP4 = _MxFormat("MXFP4", "lowrank_decode_w4", 16, 16, 16, W4_MXFP4, "_DECODE_W4")
-_MXFP6 = _MxFormat("MXFP6", "lowrank_decode_w6", 24, 8, 8, W6_MXFP6_E2M3, "_DECODE_W6")
+_MXFP4 = _MxFormat("MXFP4", "lowrank_decode_w4", 16, 16, 16, W4_MXFP4, "_DECODE_W4",
+                   "lowrank_skinny_w4", "_SKINNY_W4", "_SKINNY_W4_MAX_T")
+_MXFP6 = _MxFormat("MXFP6", "lowrank_decode_w6", 24, 8, 8, W6_MXFP6_E2M3, "_DECODE_W6",
+                   "lowrank_skinny_w6", "_SKINNY_W6", "_SKINNY_W6_MAX_T")
 
 
 def _mx_decode_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
@@ -846,24 +851,21 @@ def lowrank_skinny_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq:
     return y
 
 
-# The MXFP4 pair of lowrank_decode_w4 at small batches (32 <= T <= _SKINNY_W4_MAX_T tokens) runs on ptd_lowrank_skinny_w4:
-# lowrank_skinny's three launches on packed e2m1 codes and e8m0 block scales, the once-rounded semantics of the decode-w4
-# kernels.  PTD_LOWRANK_SKINNY_W4=0 sends these shapes through the torch expression of
-# torch.ops.ptdeco_amd.lowrank_forward_w4 again.  The cap is a constant of its own (PTD_LOWRANK_SKINNY_W4_MAX_T of the
-# header) and is measured, profiles/pair_skinny_w4.json: the largest T of the probe's list up to which every MXFP4 run
-# beats every run of the expression, by more than the expression's run-to-run spread, in every bf16 cell.
+# The MX pairs of lowrank_decode_w4 / lowrank_decode_w6 at small batches (32 <= T <= the format's cap) run on
+# ptd_lowrank_skinny_w4 / ptd_lowrank_skinny_w6: lowrank_skinny's three launches on packed codes and e8m0 block scales,
+# the once-rounded semantics of the decode kernels, one kernel template for both formats.  PTD_LOWRANK_SKINNY_W4=0 /
+# PTD_LOWRANK_SKINNY_W6=0 sends these shapes through the torch expression of torch.ops.ptdeco_amd.lowrank_forward_w4 /
+# _w6 again.  Each cap is a constant of its own (PTD_LOWRANK_SKINNY_W4_MAX_T / _W6_MAX_T of the header) and is measured,
+# profiles/pair_skinny_w4.json / pair_skinny_w6.json: the largest T of the probe's list up to which every run of the
+# entry beats every run of the expression, by more than the expression's run-to-run spread, in every bf16 cell.
 _SKINNY_W4 = os.environ.get("PTD_LOWRANK_SKINNY_W4", "1") != "0"
 _SKINNY_W4_MAX_T = 96
+_SKINNY_W6 = os.environ.get("PTD_LOWRANK_SKINNY_W6", "1") != "0"
+_SKINNY_W6_MAX_T = 96
 
 
-def lowrank_skinny_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
-                             bias: Optional[torch.Tensor]) -> bool:
-    """Whether ``lowrank_skinny_w4`` takes these operands as they lie (the rule of ptd_lowrank_skinny_w4, without
-    loading the library): real tensors on a ROCm device, x2d bf16 / f16, Aq [r, n_i / 2], ea [r, n_i / 32], Bq
-    [n_o, r / 2] and eb [n_o, r / 32] uint8, _SKINNY_MIN_T <= T <= _SKINNY_W4_MAX_T, r >= 32, n_i and r multiples of 32,
-    code row pitches multiples of 8 bytes, x2d's a multiple of 8 elements, unit inner strides, x2d 16-byte and the codes
-    8-byte aligned (the scale rows need no alignment)."""
-    if not _SKINNY_W4:
+def _mx_skinny_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
+    if not globals()[fmt.skinny_switch]:
         return False
     ts = (x2d, Aq, ea, Bq, eb) if bias is None else (x2d, Aq, ea, Bq, eb, bias)
     for t in ts:
@@ -874,17 +876,17 @@ def lowrank_skinny_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tens
     if x2d.dtype not in (torch.bfloat16, torch.float16):
         return False
     (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
-    if not _SKINNY_MIN_T <= T <= _SKINNY_W4_MAX_T or n_o < 1 or r < 32 or n_i < 32 or n_i % 32 or r % 32:
+    if not _SKINNY_MIN_T <= T <= globals()[fmt.skinny_cap] or n_o < 1 or r < 32 or n_i < 32 or n_i % 32 or r % 32:
         return False
     if n_i >= 1 << 30 or r >= 1 << 27 or n_o >= 1 << 30:
         return False
-    if (tuple(Aq.shape) != (r, n_i // 2) or tuple(ea.shape) != (r, n_i // 32) or tuple(Bq.shape) != (n_o, r // 2)
-            or tuple(eb.shape) != (n_o, r // 32)):
+    if (tuple(Aq.shape) != (r, fmt.row_bytes(n_i)) or tuple(ea.shape) != (r, n_i // 32)
+            or tuple(Bq.shape) != (n_o, fmt.row_bytes(r)) or tuple(eb.shape) != (n_o, r // 32)):
         return False
     if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o or bias.dtype != x2d.dtype
                              or (n_o > 1 and bias.stride(0) != 1)):
         return False
-    for t, vec, align in ((x2d, 8, 16), (Aq, 8, 8), (Bq, 8, 8)):
+    for t, vec, align in ((x2d, 8, 16), (Aq, 8, 8), (Bq, 8, 8)):      # (a lane's piece is half a block: both formats)
         if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % align:
             return False
     for e in (ea, eb):
@@ -893,31 +895,65 @@ def lowrank_skinny_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tens
     return True
 
 
+def _mx_skinny(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> torch.Tensor:
+    _dev(x2d, Aq, ea, Bq, eb, bias)
+    x2d, Aq, ea, Bq, eb = _rows2d(x2d), _rows2d(Aq), _rows2d(ea), _rows2d(Bq), _rows2d(eb)
+    T, n_i = x2d.shape
+    r, n_o = Aq.shape[0], Bq.shape[0]
+    assert all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)) and n_i % 32 == 0 and r % 32 == 0
+    assert Aq.shape == (r, fmt.row_bytes(n_i)) and ea.shape == (r, n_i // 32)
+    assert Bq.shape == (n_o, fmt.row_bytes(r)) and eb.shape == (n_o, r // 32)
+    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
+    lib = _hip.load()
+    ws_bytes = getattr(lib, f"ptd_{fmt.skinny_entry}_workspace_bytes")(T, n_i, r, _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+    if bias is not None:
+        bias = bias.to(x2d.dtype).contiguous()
+    with torch.cuda.device(x2d.device):
+        rc = getattr(lib, f"ptd_{fmt.skinny_entry}")(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0),
+                                                     ea.data_ptr(), ea.stride(0), r, Bq.data_ptr(), Bq.stride(0),
+                                                     eb.data_ptr(), eb.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o,
+                                                     ws.data_ptr(), ws_bytes, _code(x2d), fmt.code, _stream(x2d))
+    _hip.check(rc, f"ptd_{fmt.skinny_entry}")
+    return y
+
+
+def lowrank_skinny_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                             bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``lowrank_skinny_w4`` takes these operands as they lie (the rule of ptd_lowrank_skinny_w4, without
+    loading the library): real tensors on a ROCm device, x2d bf16 / f16, Aq [r, n_i / 2], ea [r, n_i / 32], Bq
+    [n_o, r / 2] and eb [n_o, r / 32] uint8, _SKINNY_MIN_T <= T <= _SKINNY_W4_MAX_T, r >= 32, n_i and r multiples of 32,
+    code row pitches multiples of 8 bytes, x2d's a multiple of 8 elements, unit inner strides, x2d 16-byte and the codes
+    8-byte aligned (the scale rows need no alignment)."""
+    return _mx_skinny_serves(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+
+
 def lowrank_skinny_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
                       bias: Optional[torch.Tensor]) -> torch.Tensor:
     """round(h @ B^^T + bias) with h = round(x2d @ A^^T) for 32 <= T <= _SKINNY_W4_MAX_T rows of x2d (bf16 / f16), A^ and
     B^ the MXFP4 factors of ``lowrank_decode_w4``: ptd_lowrank_skinny_w4 (sums in f32, each rounded once to x2d's
     dtype).  Operands the entry does not serve (``lowrank_skinny_w4_serves``) raise; row t of the result depends on row
     t of x2d alone."""
-    _dev(x2d, Aq, ea, Bq, eb, bias)
-    x2d, Aq, ea, Bq, eb = _rows2d(x2d), _rows2d(Aq), _rows2d(ea), _rows2d(Bq), _rows2d(eb)
-    T, n_i = x2d.shape
-    r, n_o = Aq.shape[0], Bq.shape[0]
-    assert all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)) and n_i % 32 == 0 and r % 32 == 0
-    assert Aq.shape == (r, n_i // 2) and ea.shape == (r, n_i // 32) and Bq.shape == (n_o, r // 2) and eb.shape == (n_o, r // 32)
-    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
-    lib = _hip.load()
-    ws_bytes = lib.ptd_lowrank_skinny_w4_workspace_bytes(T, n_i, r, _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    if bias is not None:
-        bias = bias.to(x2d.dtype).contiguous()
-    with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_skinny_w4(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0), ea.data_ptr(),
-                                       ea.stride(0), r, Bq.data_ptr(), Bq.stride(0), eb.data_ptr(), eb.stride(0), n_o,
-                                       _ptr(bias), y.data_ptr(), n_o, ws.data_ptr(), ws_bytes, _code(x2d), W4_MXFP4,
-                                       _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_skinny_w4")
-    return y
+    return _mx_skinny(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_skinny_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                             bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``lowrank_skinny_w6`` takes these operands as they lie (the rule of ptd_lowrank_skinny_w6, without
+    loading the library): real tensors on a ROCm device, x2d bf16 / f16, Aq [r, 3 n_i / 4], ea [r, n_i / 32], Bq
+    [n_o, 3 r / 4] and eb [n_o, r / 32] uint8, _SKINNY_MIN_T <= T <= _SKINNY_W6_MAX_T, r >= 32, n_i and r multiples of
+    32, code row pitches multiples of 8 bytes, x2d's a multiple of 8 elements, unit inner strides, x2d 16-byte and the
+    codes 8-byte aligned (the scale rows need no alignment)."""
+    return _mx_skinny_serves(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_skinny_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                      bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """round(h @ B^^T + bias) with h = round(x2d @ A^^T) for 32 <= T <= _SKINNY_W6_MAX_T rows of x2d (bf16 / f16), A^ and
+    B^ the MXFP6 (e2m3) factors of ``lowrank_decode_w6``: ptd_lowrank_skinny_w6 (sums in f32, each rounded once to
+    x2d's dtype).  Operands the entry does not serve (``lowrank_skinny_w6_serves``) raise; row t of the result depends
+    on row t of x2d alone."""
+    return _mx_skinny(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
 
 
 # The gated pair of an MLP at small batches, act(gate(x)) * up(x), runs on ptd_lowrank_skinny_gated: three launches (both
