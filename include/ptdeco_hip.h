@@ -49,7 +49,10 @@ extern "C" {
                              *    ptd_lowrank_plan,
                              *    ptd_lowrank_skinny_w4_workspace_bytes, ptd_lowrank_skinny_w4,
                              *    ptd_lowrank_decode_w6_workspace_bytes, ptd_lowrank_decode_w6,
-                             *    ptd_lowrank_skinny_w6_workspace_bytes, ptd_lowrank_skinny_w6) */
+                             *    ptd_lowrank_skinny_w6_workspace_bytes, ptd_lowrank_skinny_w6,
+                             *    ptd_lowrank_dequant_w4, ptd_lowrank_dequant_w6,
+                             *    ptd_lowrank_tile_w4_workspace_bytes, ptd_lowrank_tile_w4,
+                             *    ptd_lowrank_tile_w6_workspace_bytes, ptd_lowrank_tile_w6) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -537,6 +540,50 @@ int ptd_lowrank_skinny_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                           const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
                           const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
                           void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+
+/* An OCP MX factor written out as its 16-bit values: codes [rows, cols / 2] (MXFP4, ptd_lowrank_dequant_w4) or
+ * [rows, 3 cols / 4] (MXFP6 e2m3, ptd_lowrank_dequant_w6) bytes with row pitch ldq, scales [rows, cols / 32] e8m0 bytes
+ * with row pitch lds, out [rows, cols] elements of dtype D = bf16 or f16 with row pitch ldo (in elements):
+ *   out[i, k] = W^[i, k] = val(code(W, i, k)) * 2^(clamp(scale[i, k >> 5], E_MIN, 140) - 127)
+ * with code, val and the clamp (E_MIN = 114 / 116) of ptd_lowrank_decode_w4 / _w6.  EXACT: the clamp makes every W^ a
+ * normal number (or zero) of bf16 and of f16, so nothing is rounded and out equals torch's dequantisation of the same
+ * bytes bit for bit.  One launch on the caller's stream; a lane takes one MX block (its 16- or 24-byte code load, one
+ * scale byte, the conversion instructions of the decode kernels, four 16-byte stores); nothing is written outside
+ * [rows, cols] of out.  Null pointers, rows < 1, ldq below a row's code bytes, lds < cols / 32 or ldo < cols:
+ * PTD_ERR_INVALID.  A dtype other than bf16 / f16, an unknown w_format, cols not a positive multiple of 32, code rows
+ * that are not 8-byte aligned (address and ldq), output rows that are not 16-byte aligned (address, ldo a multiple of
+ * 8), or more than 2^38 blocks: PTD_ERR_UNSUPPORTED before anything is launched.  No reference counterpart. */
+int ptd_lowrank_dequant_w4(const void* codes, int64_t ldq, const void* scales, int64_t lds, int64_t rows, int64_t cols,
+                           void* out, int64_t ldo, int dtype, int w_format, void* stream);
+int ptd_lowrank_dequant_w6(const void* codes, int64_t ldq, const void* scales, int64_t lds, int64_t rows, int64_t cols,
+                           void* out, int64_t ldo, int dtype, int w_format, void* stream);
+
+/* The pair with OCP MX factors at ANY token count T >= 1 (arguments, formats and semantics of ptd_lowrank_skinny_w4 /
+ * _w6, clamp included): ONE launch dequantises both factors into the workspace (the kernel of ptd_lowrank_dequant_w4 /
+ * _w6, A's blocks and then B's in one grid; exact), then ptd_lowrank_forward runs on (x, A^, B^, bias) with the rest of
+ * the workspace -- the 16-bit tile products, untouched.  The result is, bit for bit, what ptd_lowrank_forward returns
+ * on the dequantised factors (contiguous, pitch = row length): f32 sums, h rounded ONCE to D, y once -- the rounding
+ * points of the decode and skinny MX entries (the order of the f32 additions is the tile products', so the last bit may
+ * differ from theirs).  No dequantised copy outlives the call.  Everything runs on the caller's stream without a host
+ * read or an allocation: the call can be captured in a graph.  Served: the operands of ptd_lowrank_skinny_w4 / _w6 (dtype
+ * bf16 / f16, r >= 32, n_i and r multiples of 32, lda and ldb multiples of 8 bytes, ldsa >= n_i / 32, ldsb >= r / 32,
+ * ldx a multiple of 8, x 16-byte aligned, Aq and Bq 8-byte aligned, bias 2-byte aligned and optional, n_i < 2^30,
+ * r < 2^27, 1 <= n_o < 2^30) at any T >= 1, at most 2^38 blocks in both factors.  Anything else returns
+ * PTD_ERR_UNSUPPORTED before a kernel is launched; null pointers, a leading dimension below its row length or a
+ * misaligned workspace PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  The workspace is
+ *   align256(2 r n_i) + align256(2 n_o r) + ptd_lowrank_forward_workspace_bytes(T, n_i, r, dtype)
+ * bytes: A^ [r, n_i], B^ [n_o, r], then the 16-bit entry's own (the query takes n_o for B^).  Which T the Python package
+ * sends here is measured (profiles/pair_tile_mx.json).  No reference counterpart. */
+size_t ptd_lowrank_tile_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype);
+int ptd_lowrank_tile_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                        const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
+                        const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
+                        void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+size_t ptd_lowrank_tile_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype);
+int ptd_lowrank_tile_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                        const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
+                        const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
+                        void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 
 /* The gated pair of a decomposed MLP at the same 32 <= T <= 96 tokens in bf16 / f16, y = act(gate(x)) * up(x) (arguments
  * and activations as ptd_lowrank_decode_gated), in three launches on the caller's stream: both first products, both

@@ -112,6 +112,18 @@ SIGNATURES = {
     "ptd_lowrank_skinny_w6": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
                                       c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                       c_size_t, c_int, c_int, c_void_p]),
+    "ptd_lowrank_dequant_w4": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
+                                       c_int, c_void_p]),
+    "ptd_lowrank_dequant_w6": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
+                                       c_int, c_void_p]),
+    "ptd_lowrank_tile_w4_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
+    "ptd_lowrank_tile_w4": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                    c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                    c_size_t, c_int, c_int, c_void_p]),
+    "ptd_lowrank_tile_w6_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
+    "ptd_lowrank_tile_w6": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                    c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                    c_size_t, c_int, c_int, c_void_p]),
     "ptd_lowrank_skinny_gated_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
     "ptd_lowrank_skinny_gated": (c_int, [c_void_p, c_int64, c_int64, c_int64,
                                          c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,

@@ -25,14 +25,18 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
                                                              the pair with OCP MXFP4 factors (packed e2m1 codes, e8m0
                                                              block scales): ops.lowrank_decode_w4 where
                                                              ops.lowrank_decode_w4_serves (T <= 16), ops.lowrank_skinny_w4
-                                                             where ops.lowrank_skinny_w4_serves (32 ... 96), else the
-                                                             torch expression on 16-bit copies
+                                                             where ops.lowrank_skinny_w4_serves (32 ... 96),
+                                                             ops.lowrank_tile_w4 where ops.lowrank_tile_w4_serves
+                                                             (above 96; 17 ... 31 where measured to win),
+                                                             else the torch expression on 16-bit copies
     lowrank_forward_w6(Tensor x2d, Tensor Aq, Tensor ea, Tensor Bq, Tensor eb, Tensor? bias) -> Tensor
                                                              the pair with OCP MXFP6 (e2m3) factors (packed 6-bit codes,
                                                              e8m0 block scales): ops.lowrank_decode_w6 where
                                                              ops.lowrank_decode_w6_serves (T <= 16), ops.lowrank_skinny_w6
-                                                             where ops.lowrank_skinny_w6_serves (32 ... 96), else the
-                                                             torch expression on 16-bit copies
+                                                             where ops.lowrank_skinny_w6_serves (32 ... 96),
+                                                             ops.lowrank_tile_w6 where ops.lowrank_tile_w6_serves
+                                                             (above 96; 17 ... 31 where measured to win),
+                                                             else the torch expression on 16-bit copies
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -263,13 +267,17 @@ def lowrank_forward_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq
     ea [r, n_i / 32] and eb [n_o, r / 32] e8m0 block scales (all uint8), bias [n_o] of x2d's dtype or None; y [T, n_o]
     contiguous, y = round(h B^^T + bias) with h = round(x2d A^^T).  At decode shapes (1 <= T <= 16, aligned operands:
     ops.lowrank_decode_w4_serves) on the weight-streaming kernels of ptd_lowrank_decode_w4, at small batches (32 <= T <=
-    96: ops.lowrank_skinny_w4_serves) on the skinny products of ptd_lowrank_skinny_w4; both keep the sums in f32 and
+    96: ops.lowrank_skinny_w4_serves) on the skinny products of ptd_lowrank_skinny_w4, where ops.lowrank_tile_w4_serves
+    (above 96 tokens, and at 17 ... 31 on the layers it is measured to win) on ptd_lowrank_tile_w4, one launch that
+    dequantises both factors into the workspace and the 16-bit tile pair on them; all three keep the sums in f32 and
     round h and y once each.  Elsewhere ``lowrank_w4_expression``: torch's products on transient 16-bit copies of the
     factors.  Inference only: no autograd formula."""
     if ops.lowrank_decode_w4_serves(x2d, Aq, ea, Bq, eb, bias):
         return ops.lowrank_decode_w4(x2d, Aq, ea, Bq, eb, bias)
     if ops.lowrank_skinny_w4_serves(x2d, Aq, ea, Bq, eb, bias):
         return ops.lowrank_skinny_w4(x2d, Aq, ea, Bq, eb, bias)
+    if ops.lowrank_tile_w4_serves(x2d, Aq, ea, Bq, eb, bias):
+        return ops.lowrank_tile_w4(x2d, Aq, ea, Bq, eb, bias)
     return lowrank_w4_expression(x2d, Aq, ea, Bq, eb, bias).contiguous()
 
 
@@ -330,13 +338,17 @@ def lowrank_forward_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq
     6-bit codes, ea [r, n_i / 32] and eb [n_o, r / 32] e8m0 block scales (all uint8), bias [n_o] of x2d's dtype or None;
     y [T, n_o] contiguous, y = round(h B^^T + bias) with h = round(x2d A^^T).  At decode shapes (1 <= T <= 16, aligned
     operands: ops.lowrank_decode_w6_serves) on the weight-streaming kernels of ptd_lowrank_decode_w6, at small batches
-    (32 <= T <= 96: ops.lowrank_skinny_w6_serves) on the skinny products of ptd_lowrank_skinny_w6; both keep the sums in
-    f32 and round h and y once each.  Elsewhere ``lowrank_w6_expression``: torch's products on transient 16-bit copies
-    of the factors.  Inference only: no autograd formula."""
+    (32 <= T <= 96: ops.lowrank_skinny_w6_serves) on the skinny products of ptd_lowrank_skinny_w6, where
+    ops.lowrank_tile_w6_serves (above 96 tokens, and at 17 ... 31 on the layers it is measured to win) on
+    ptd_lowrank_tile_w6, one launch that dequantises both factors into the workspace and the 16-bit tile pair on them;
+    all three keep the sums in f32 and round h and y once each.  Elsewhere ``lowrank_w6_expression``: torch's products on transient 16-bit copies of the factors.  Inference
+    only: no autograd formula."""
     if ops.lowrank_decode_w6_serves(x2d, Aq, ea, Bq, eb, bias):
         return ops.lowrank_decode_w6(x2d, Aq, ea, Bq, eb, bias)
     if ops.lowrank_skinny_w6_serves(x2d, Aq, ea, Bq, eb, bias):
         return ops.lowrank_skinny_w6(x2d, Aq, ea, Bq, eb, bias)
+    if ops.lowrank_tile_w6_serves(x2d, Aq, ea, Bq, eb, bias):
+        return ops.lowrank_tile_w6(x2d, Aq, ea, Bq, eb, bias)
     return lowrank_w6_expression(x2d, Aq, ea, Bq, eb, bias).contiguous()
 
 

@@ -758,6 +758,95 @@ int ptd_lowrank_skinny_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                            static_cast<hipStream_t>(stream));
 }
 
+// One MX factor as its 16-bit values (ptd_lowrank_dequant_w4 / _w6): `code_cols` code bytes per row
+static int mx_dequant_entry(const char* name, const void* codes, int64_t ldq, const void* scales, int64_t lds, int64_t rows,
+                            int64_t cols, const void* out, int64_t ldo, int dtype, int w_format, int64_t code_cols,
+                            bool served) {
+  PTD_REQUIRE(codes && scales && out, "%s: null pointer", name);
+  PTD_REQUIRE(rows >= 1, "%s: rows must be positive", name);
+  PTD_REQUIRE(ldq >= code_cols && lds >= cols / 32 && ldo >= cols, "%s: bad leading dimension", name);
+  if (!served) {
+    set_error("%s: not served (rows=%lld cols=%lld dtype=%d w_format=%d: bf16 / f16, cols a positive multiple of 32, "
+              "8-byte aligned code rows, 16-byte aligned output rows)", name, (long long)rows, (long long)cols, dtype,
+              w_format);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  return PTD_OK;
+}
+
+int ptd_lowrank_dequant_w4(const void* codes, int64_t ldq, const void* scales, int64_t lds, int64_t rows, int64_t cols,
+                           void* out, int64_t ldo, int dtype, int w_format, void* stream) {
+  const int rc = mx_dequant_entry("ptd_lowrank_dequant_w4", codes, ldq, scales, lds, rows, cols, out, ldo, dtype, w_format,
+                                  cols / 2, lowrank_dequant_w4_serves(codes, ldq, rows, cols, out, ldo, dtype, w_format));
+  if (rc != PTD_OK) return rc;
+  return lowrank_dequant_w4(codes, ldq, scales, lds, rows, cols, out, ldo, dtype, static_cast<hipStream_t>(stream));
+}
+
+int ptd_lowrank_dequant_w6(const void* codes, int64_t ldq, const void* scales, int64_t lds, int64_t rows, int64_t cols,
+                           void* out, int64_t ldo, int dtype, int w_format, void* stream) {
+  const int rc = mx_dequant_entry("ptd_lowrank_dequant_w6", codes, ldq, scales, lds, rows, cols, out, ldo, dtype, w_format,
+                                  3 * (cols / 4), lowrank_dequant_w6_serves(codes, ldq, rows, cols, out, ldo, dtype, w_format));
+  if (rc != PTD_OK) return rc;
+  return lowrank_dequant_w6(codes, ldq, scales, lds, rows, cols, out, ldo, dtype, static_cast<hipStream_t>(stream));
+}
+
+// The MX pair on the tile products (ptd_lowrank_tile_w4 / _w6): A^ and B^ in front of the 16-bit entry's own workspace
+static size_t lowrank_tile_mx_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype) {
+  if (T < 1 || n_i < 1 || r < 1 || n_o < 1) return 0;
+  return lowrank_tile_mx_factor_bytes(r, n_i) + lowrank_tile_mx_factor_bytes(n_o, r) +
+         ptd_lowrank_forward_workspace_bytes(T, n_i, r, dtype);
+}
+
+// ptd_lowrank_forward on the factors the dequantisation launch has just left at the head of the workspace
+static int lowrank_tile_mx_products(const void* x, int64_t ldx, int64_t T, int64_t n_i, int64_t r, int64_t n_o,
+                                    const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype,
+                                    void* stream) {
+  const size_t a_bytes = lowrank_tile_mx_factor_bytes(r, n_i), b_bytes = lowrank_tile_mx_factor_bytes(n_o, r);
+  char* const a_hat = static_cast<char*>(ws);
+  return ptd_lowrank_forward(x, ldx, T, n_i, a_hat, n_i, r, a_hat + a_bytes, r, n_o, bias, y, ldy, a_hat + a_bytes + b_bytes,
+                             ws_bytes - a_bytes - b_bytes, dtype, stream);
+}
+
+size_t ptd_lowrank_tile_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype) {
+  return lowrank_tile_mx_workspace_bytes(T, n_i, r, n_o, dtype);
+}
+
+int ptd_lowrank_tile_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                        const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                        int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
+                        int dtype, int w_format, void* stream) {
+  int rc = mx_entry_checks("ptd_lowrank_tile_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, y,
+                           ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2,
+                           lowrank_tile_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                           "PTD_W4_MXFP4, T >= 1, r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
+                           lowrank_tile_mx_workspace_bytes(T, n_i, r, n_o, dtype));
+  if (rc != PTD_OK) return rc;
+  rc = lowrank_tile_w4_dequant(Aq, lda, scale_a, ldsa, n_i, r, Bq, ldb, scale_b, ldsb, n_o, ws, dtype,
+                               static_cast<hipStream_t>(stream));
+  if (rc != PTD_OK) return rc;
+  return lowrank_tile_mx_products(x, ldx, T, n_i, r, n_o, bias, y, ldy, ws, ws_bytes, dtype, stream);
+}
+
+size_t ptd_lowrank_tile_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype) {
+  return lowrank_tile_mx_workspace_bytes(T, n_i, r, n_o, dtype);
+}
+
+int ptd_lowrank_tile_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                        const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                        int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
+                        int dtype, int w_format, void* stream) {
+  int rc = mx_entry_checks("ptd_lowrank_tile_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, y,
+                           ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4),
+                           lowrank_tile_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                           "PTD_W6_MXFP6_E2M3, T >= 1, r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
+                           lowrank_tile_mx_workspace_bytes(T, n_i, r, n_o, dtype));
+  if (rc != PTD_OK) return rc;
+  rc = lowrank_tile_w6_dequant(Aq, lda, scale_a, ldsa, n_i, r, Bq, ldb, scale_b, ldsb, n_o, ws, dtype,
+                               static_cast<hipStream_t>(stream));
+  if (rc != PTD_OK) return rc;
+  return lowrank_tile_mx_products(x, ldx, T, n_i, r, n_o, bias, y, ldy, ws, ws_bytes, dtype, stream);
+}
+
 int ptd_lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap) {
   PTD_REQUIRE(out, "ptd_lowrank_plan: null pointer");
   PTD_REQUIRE(cap >= PTD_PLAN_LEN, "ptd_lowrank_plan: out holds %d values, the plan has %d", cap, PTD_PLAN_LEN);

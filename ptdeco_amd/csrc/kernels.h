@@ -151,6 +151,30 @@ int lowrank_skinny_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const 
                       int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
                       const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_dequant_mx.hip: an MX factor (MXFP4 / MXFP6 codes and e8m0 block scales) written out as its exact 16-bit
+// values, one block per lane (ptd_lowrank_dequant_w4 / _w6), and both factors of a pair in one launch into the workspace
+// of ptd_lowrank_tile_w4 / _w6: A^ [r, n_i] at ws, B^ [n_o, r] lowrank_tile_mx_factor_bytes(r, n_i) behind it, both
+// contiguous.  *_serves: the skinny MX rule on the operands at any T >= 1
+size_t lowrank_tile_mx_factor_bytes(int64_t rows, int64_t cols);
+bool lowrank_dequant_w4_serves(const void* q, int64_t ldq, int64_t rows, int64_t cols, const void* out, int64_t ldo,
+                               int dtype, int w_format);
+bool lowrank_dequant_w6_serves(const void* q, int64_t ldq, int64_t rows, int64_t cols, const void* out, int64_t ldo,
+                               int dtype, int w_format);
+int lowrank_dequant_w4(const void* q, int64_t ldq, const void* e, int64_t lde, int64_t rows, int64_t cols, void* out,
+                       int64_t ldo, int dtype, hipStream_t st);
+int lowrank_dequant_w6(const void* q, int64_t ldq, const void* e, int64_t lde, int64_t rows, int64_t cols, void* out,
+                       int64_t ldo, int dtype, hipStream_t st);
+bool lowrank_tile_w4_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
+                            int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias);
+bool lowrank_tile_w6_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
+                            int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias);
+int lowrank_tile_w4_dequant(const void* Aq, int64_t lda, const void* ea, int64_t ldsa, int64_t n_i, int64_t r,
+                            const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o, void* ws, int dtype,
+                            hipStream_t st);
+int lowrank_tile_w6_dequant(const void* Aq, int64_t lda, const void* ea, int64_t ldsa, int64_t n_i, int64_t r,
+                            const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o, void* ws, int dtype,
+                            hipStream_t st);
+
 // lowrank_plan.hip: what a launch of one serving family would do, from the host rules the launchers call (ptd_lowrank_plan);
 // fills out[PTD_PLAN_*], PTD_OK or PTD_ERR_UNSUPPORTED
 int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out);

@@ -58,6 +58,11 @@ struct MxFp4 {
     return load_weights<u32x4, NT>(reinterpret_cast<const u32x4*>(p));
   }
 
+  // the same block from a row that is only 8-byte aligned (lowrank_dequant_mx.hip, on the operands of the skinny
+  // entry): one global_load_dwordx4 all the same -- gfx950 loads unaligned vectors from global memory
+  typedef u32x4 raw_a8 __attribute__((aligned(8)));
+  static __device__ __forceinline__ raw load_a8(const unsigned char* p) { return *reinterpret_cast<const raw_a8*>(p); }
+
   // keeps the raw dwords and converts dword q when MFMA q asks for it
   template <typename EL>
   struct Cvt {

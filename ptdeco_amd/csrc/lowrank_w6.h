@@ -63,6 +63,9 @@ struct MxFp6 {
     return raw{a[0], a[1], a[2], a[3], b[0], b[1]};
   }
 
+  // (the name MxFp4 gives its load from an 8-byte aligned row: here every load is one)
+  static __device__ __forceinline__ raw load_a8(const unsigned char* p) { return load<false>(p); }
+
   // converts the block once; dwords 4 q .. 4 q + 3 of the result (k = 8 q + 0..7 of the block) are the A operand of MFMA q
   template <typename EL>
   struct Cvt {

@@ -229,8 +229,13 @@ class LowRankLinearW4(_LowRankLinearMX):
 
     On a ROCm device, for x of the module's dtype and no gradient wanted, ``forward`` calls
     ``torch.ops.ptdeco_amd.lowrank_forward_w4``: at 1 to 16 tokens the HIP kernels of ptd_lowrank_decode_w4 (a quarter
-    of the factor bytes of the 16-bit pair, converted in registers), at any other token count the torch expression on
-    transient 16-bit copies of the factors.  Anything else (a CPU copy, another input dtype, ``x.requires_grad``)
+    of the factor bytes of the 16-bit pair, converted in registers), at 32 to PTD_LOWRANK_SKINNY_W4_MAX_T tokens the
+    three launches of ptd_lowrank_skinny_w4 on the same bytes, above the cap (prompt processing) ptd_lowrank_tile_w4
+    -- one HIP launch writes both factors out as their exact 16-bit values into the call's workspace and the 16-bit
+    tile pair runs on them, the bits of the 16-bit module on the dequantised factors; no copy outlives the call and
+    every route can be captured in a CUDA graph.  At 17 to 31 tokens that entry serves the layers it is measured to win
+    (out_features >= 2 in_features); the others evaluate the torch expression on transient 16-bit copies of the
+    factors there.  Anything else (a CPU copy, another input dtype, ``x.requires_grad``)
     evaluates that expression directly and says so once, at WARNING.  The format is coarse -- round to nearest gives a
     noise-to-signal ratio of about 2.5e-2 on Gaussian factors, against 1.4e-3 for fp8 -- so it is meant to be chosen
     layer by layer (``quantize_pairs_in_place(model, "mxfp4", names=...)``).  ``.to(device)`` moves the module; a dtype
@@ -266,8 +271,12 @@ class LowRankLinearW6(_LowRankLinearMX):
     ``torch.ops.ptdeco_amd.lowrank_forward_w6``: at 1 to 16 tokens the HIP kernels of ptd_lowrank_decode_w6 (0.39 of
     the factor bytes of the 16-bit pair, 0.78 of the fp8 pair's, converted in registers), at 32 to
     PTD_LOWRANK_SKINNY_W6_MAX_T tokens the three launches of ptd_lowrank_skinny_w6 on the same bytes (no dequantised
-    copy, capturable in a CUDA graph), at any other token count the torch expression on transient 16-bit copies of the
-    factors.  Both HIP routes give row t of y from row t of x alone, bit for bit.  Anything else (a CPU copy, another
+    copy, capturable in a CUDA graph), above the cap (prompt processing) ptd_lowrank_tile_w6 -- one HIP launch writes
+    both factors out as their exact 16-bit values into the call's workspace and the 16-bit tile pair runs on them, the
+    bits of the 16-bit module on the dequantised factors; no copy outlives the call, and it is capturable too.  At 17
+    to 31 tokens that entry serves the layers it is measured to win (out_features >= in_features); the others evaluate
+    the torch expression on transient 16-bit copies of the factors there.  The decode and skinny routes give row t of y
+    from row t of x alone, bit for bit.  Anything else (a CPU copy, another
     input dtype, ``x.requires_grad``) evaluates that expression directly and says so once, at WARNING.  The format
     keeps fp8's three mantissa bits: round to nearest gives a noise-to-signal ratio of about 1.6e-3 on Gaussian
     factors, fp8's class (1.3 .. 1.5e-3) and a sixteenth of MXFP4's.  ``.to(device)`` moves the module; a dtype cast

@@ -523,15 +523,20 @@ class _MxFormat:
     skinny_entry: str    # ptd_<skinny_entry> and ptd_<skinny_entry>_workspace_bytes: the small-batch entry,
     skinny_switch: str   #   the module attribute that enables it
     skinny_cap: str      #   and the one that holds its largest T
+    tile_entry: str      # ptd_<tile_entry> and ptd_<tile_entry>_workspace_bytes: every other T, on the tile products,
+    tile_switch: str     #   the module attribute that enables it
+    dequant_entry: str   #   and ptd_<dequant_entry>: one factor as its 16-bit values
 
     def row_bytes(self, n: int) -> int:
         return n // 32 * self.block_bytes
 
 
 _MXFP4 = _MxFormat("MXFP4", "lowrank_decode_w4", 16, 16, 16, W4_MXFP4, "_DECODE_W4",
-                   "lowrank_skinny_w4", "_SKINNY_W4", "_SKINNY_W4_MAX_T")
+                   "lowrank_skinny_w4", "_SKINNY_W4", "_SKINNY_W4_MAX_T",
+                   "lowrank_tile_w4", "_TILE_W4", "lowrank_dequant_w4")
 _MXFP6 = _MxFormat("MXFP6", "lowrank_decode_w6", 24, 8, 8, W6_MXFP6_E2M3, "_DECODE_W6",
-                   "lowrank_skinny_w6", "_SKINNY_W6", "_SKINNY_W6_MAX_T")
+                   "lowrank_skinny_w6", "_SKINNY_W6", "_SKINNY_W6_MAX_T",
+                   "lowrank_tile_w6", "_TILE_W6", "lowrank_dequant_w6")
 
 
 def _mx_decode_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
@@ -864,9 +869,8 @@ _SKINNY_W6 = os.environ.get("PTD_LOWRANK_SKINNY_W6", "1") != "0"
 _SKINNY_W6_MAX_T = 96
 
 
-def _mx_skinny_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
-    if not globals()[fmt.skinny_switch]:
-        return False
+def _mx_skinny_operands(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
+    """The rule of the skinny MX entries on everything but the token count (the tile MX entries take the same operands)."""
     ts = (x2d, Aq, ea, Bq, eb) if bias is None else (x2d, Aq, ea, Bq, eb, bias)
     for t in ts:
         if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
@@ -876,7 +880,7 @@ def _mx_skinny_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
     if x2d.dtype not in (torch.bfloat16, torch.float16):
         return False
     (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
-    if not _SKINNY_MIN_T <= T <= globals()[fmt.skinny_cap] or n_o < 1 or r < 32 or n_i < 32 or n_i % 32 or r % 32:
+    if T < 1 or n_o < 1 or r < 32 or n_i < 32 or n_i % 32 or r % 32:
         return False
     if n_i >= 1 << 30 or r >= 1 << 27 or n_o >= 1 << 30:
         return False
@@ -893,6 +897,14 @@ def _mx_skinny_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
         if (e.shape[1] > 1 and e.stride(1) != 1) or e.stride(0) < e.shape[1]:
             return False
     return True
+
+
+def _mx_skinny_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
+    if not globals()[fmt.skinny_switch]:
+        return False
+    if not _mx_skinny_operands(fmt, x2d, Aq, ea, Bq, eb, bias):
+        return False
+    return _SKINNY_MIN_T <= x2d.shape[0] <= globals()[fmt.skinny_cap]
 
 
 def _mx_skinny(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> torch.Tensor:
@@ -954,6 +966,127 @@ def lowrank_skinny_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq:
     x2d's dtype).  Operands the entry does not serve (``lowrank_skinny_w6_serves``) raise; row t of the result depends
     on row t of x2d alone."""
     return _mx_skinny(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+
+
+# The MX pairs at every other token count (17 <= T < _SKINNY_MIN_T and T above the format's skinny cap: prompt
+# processing) run on ptd_lowrank_tile_w4 / ptd_lowrank_tile_w6: one HIP launch writes both factors out as their exact
+# 16-bit values into the call's workspace, then the 16-bit tile pair (ptd_lowrank_forward) runs on them -- the bits of
+# lowrank_forward on torch's dequantisation, h and y rounded once each, capturable in a graph.  PTD_LOWRANK_TILE_W4=0 /
+# PTD_LOWRANK_TILE_W6=0 sends these T through the torch expression again.  The rule is on T and the shapes alone,
+# whatever the decode and skinny switches say: with one of those off its T keep the expression.  Measured
+# (profiles/pair_tile_mx.json): above the skinny cap every cell is won, at 0.16-0.35 of the expression's time.  At
+# 17 <= T < 32 the 16-bit tile products themselves are slow -- their first product costs 130-160 us per layer at
+# n_i = 4096 and 430-450 us at n_i = 14336 whatever the rank -- while the expression's cost grows with the number of
+# weights, r (n_i + n_o): the class is won only where the output is wide against the input.  MXFP4 (whose expression is
+# the cheaper one) wins at n_o / n_i = 3.5 and loses at 1 and 0.29; MXFP6 wins at 3.5 and 1 and loses at 0.29.  So at
+# these T the rule asks for n_o >= _TILE_MX_SMALL_T_RATIO[format] * n_i; what it excludes keeps the expression (the C
+# entries serve it all the same).
+_TILE_W4 = os.environ.get("PTD_LOWRANK_TILE_W4", "1") != "0"
+_TILE_W6 = os.environ.get("PTD_LOWRANK_TILE_W6", "1") != "0"
+_TILE_MX_MIN_T = _DECODE_MAX_T + 1
+_TILE_MX_SMALL_T_RATIO = {"MXFP4": 2, "MXFP6": 1}
+
+
+def _tile_mx_takes(fmt: _MxFormat, T: int, n_i: int, n_o: int) -> bool:
+    """The (T, shape) cells the tile MX entries own: T above the format's skinny cap, and 17 <= T < _SKINNY_MIN_T where
+    the layer's output is wide enough against its input for the entry to beat the expression (measured, above)."""
+    if T > globals()[fmt.skinny_cap]:
+        return True
+    return _TILE_MX_MIN_T <= T < _SKINNY_MIN_T and n_o >= _TILE_MX_SMALL_T_RATIO[fmt.name] * n_i
+
+
+def _mx_tile_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
+    if not globals()[fmt.tile_switch]:
+        return False
+    if not _mx_skinny_operands(fmt, x2d, Aq, ea, Bq, eb, bias):
+        return False
+    return _tile_mx_takes(fmt, x2d.shape[0], x2d.shape[1], Bq.shape[0])
+
+
+def _mx_tile(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> torch.Tensor:
+    _dev(x2d, Aq, ea, Bq, eb, bias)
+    x2d, Aq, ea, Bq, eb = _rows2d(x2d), _rows2d(Aq), _rows2d(ea), _rows2d(Bq), _rows2d(eb)
+    T, n_i = x2d.shape
+    r, n_o = Aq.shape[0], Bq.shape[0]
+    assert all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)) and n_i % 32 == 0 and r % 32 == 0
+    assert Aq.shape == (r, fmt.row_bytes(n_i)) and ea.shape == (r, n_i // 32)
+    assert Bq.shape == (n_o, fmt.row_bytes(r)) and eb.shape == (n_o, r // 32)
+    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
+    lib = _hip.load()
+    ws_bytes = getattr(lib, f"ptd_{fmt.tile_entry}_workspace_bytes")(T, n_i, r, n_o, _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+    if bias is not None:
+        bias = bias.to(x2d.dtype).contiguous()
+    with torch.cuda.device(x2d.device):
+        rc = getattr(lib, f"ptd_{fmt.tile_entry}")(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0),
+                                                   ea.data_ptr(), ea.stride(0), r, Bq.data_ptr(), Bq.stride(0),
+                                                   eb.data_ptr(), eb.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o,
+                                                   ws.data_ptr(), ws_bytes, _code(x2d), fmt.code, _stream(x2d))
+    _hip.check(rc, f"ptd_{fmt.tile_entry}")
+    return y
+
+
+def _mx_dequant(fmt: _MxFormat, q, e, dtype) -> torch.Tensor:
+    _dev(q, e)
+    q, e = _rows2d(q), _rows2d(e)
+    assert q.dtype == torch.uint8 and e.dtype == torch.uint8 and dtype in (torch.bfloat16, torch.float16)
+    rows, cols = q.shape[0], e.shape[1] * 32
+    assert rows >= 1 and cols >= 32 and q.shape == (rows, fmt.row_bytes(cols)) and e.shape[0] == rows
+    out = torch.empty((rows, cols), dtype=dtype, device=q.device)
+    lib = _hip.load()
+    with torch.cuda.device(q.device):
+        rc = getattr(lib, f"ptd_{fmt.dequant_entry}")(q.data_ptr(), q.stride(0), e.data_ptr(), e.stride(0), rows, cols,
+                                                      out.data_ptr(), cols, _DT[dtype], fmt.code, _stream(q))
+    _hip.check(rc, f"ptd_{fmt.dequant_entry}")
+    return out
+
+
+def lowrank_dequant_w4(q: torch.Tensor, e: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """The MXFP4 factor W^ [rows, cols] in ``dtype`` (bf16 / f16) from its packed codes q [rows, cols / 2] and its block
+    scales e [rows, cols / 32] (uint8, on a ROCm device; code rows 8-byte aligned): ptd_lowrank_dequant_w4, the bits of
+    ``_torch_ops.lowrank_w4_dequant`` (the values are exact in both types)."""
+    return _mx_dequant(_MXFP4, q, e, dtype)
+
+
+def lowrank_dequant_w6(q: torch.Tensor, e: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """The MXFP6 (e2m3) factor W^ [rows, cols] in ``dtype`` (bf16 / f16) from its packed codes q [rows, 3 cols / 4] and
+    its block scales e [rows, cols / 32] (uint8, on a ROCm device; code rows 8-byte aligned): ptd_lowrank_dequant_w6,
+    the bits of ``_torch_ops.lowrank_w6_dequant`` (the values are exact in both types)."""
+    return _mx_dequant(_MXFP6, q, e, dtype)
+
+
+def lowrank_tile_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                           bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``lowrank_tile_w4`` takes these operands as they lie (without loading the library): the operands of
+    ``lowrank_skinny_w4_serves`` at T > _SKINNY_W4_MAX_T, and at 17 <= T < _SKINNY_MIN_T where n_o >= 2 n_i (measured:
+    ``_tile_mx_takes``) -- by T and the shapes alone, whatever the decode and skinny switches say."""
+    return _mx_tile_serves(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_tile_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                    bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """round(h @ B^^T + bias) with h = round(x2d @ A^^T) for any number of rows of x2d (bf16 / f16), A^ and B^ the MXFP4
+    factors of ``lowrank_decode_w4``: ptd_lowrank_tile_w4 -- one launch dequantises both factors into the workspace
+    (exactly), the 16-bit tile pair runs on them.  The bits of ``lowrank_forward(x2d, A^, B^, bias)``.  Operands the C
+    entry does not serve raise."""
+    return _mx_tile(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_tile_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                           bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``lowrank_tile_w6`` takes these operands as they lie (without loading the library): the operands of
+    ``lowrank_skinny_w6_serves`` at T > _SKINNY_W6_MAX_T, and at 17 <= T < _SKINNY_MIN_T where n_o >= n_i (measured:
+    ``_tile_mx_takes``) -- by T and the shapes alone, whatever the decode and skinny switches say."""
+    return _mx_tile_serves(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_tile_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                    bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """round(h @ B^^T + bias) with h = round(x2d @ A^^T) for any number of rows of x2d (bf16 / f16), A^ and B^ the MXFP6
+    (e2m3) factors of ``lowrank_decode_w6``: ptd_lowrank_tile_w6 -- one launch dequantises both factors into the
+    workspace (exactly), the 16-bit tile pair runs on them.  The bits of ``lowrank_forward(x2d, A^, B^, bias)``.
+    Operands the C entry does not serve raise."""
+    return _mx_tile(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
 
 
 # The gated pair of an MLP at small batches, act(gate(x)) * up(x), runs on ptd_lowrank_skinny_gated: three launches (both
