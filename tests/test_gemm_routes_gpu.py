@@ -12,7 +12,7 @@ that must still be 0xFF.  After the call a case asserts, in this order so that a
   (d) reads:  no NaN in C[:, :N];
   (b) result: C[:, :N] equals the reference bit for bit (small integers: torch's f32 product of the same integers is
               exact, every partial sum stays below 2^24; it is rounded once with .to(dtype)).
-The expected labels were read off the router in gemm_bf16.hip / gemm_f32.hip; the trace assert is the arbiter, and
+The expected labels were read off the routers in gemm16_route.h / gemm_f32.hip; the trace assert is the arbiter, and
 where a shape first thought to reach a family does not, the comment beside the case says so."""
 # label -> case   (16-bit labels: each case runs in bf16 AND f16; checked against the sources by test_launch_trace_cpu.py)
 #   "gemm_bf16 (128 x 64 tiles)"                          -> GEMM16 t64

@@ -1,4 +1,4 @@
-"""x A^T at the decomposed forward's rank 256 (16384 x 256 x 4096, bf16): five-buffer ring against four (PTD_GEMM_DEEP)."""
+"""x A^T at the decomposed forward's rank 256 (16384 x 256 x 4096, bf16): one buffer against rotating buffers, and the pair."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
@@ -13,4 +13,4 @@ for r in (128, 256):
     it = iter(range(10 ** 9))
     t2 = min(bench.time_events(lambda: ops.matmul(xs[next(it) % 4], a.T), iters=30) for _ in range(3))
     t3 = min(bench.time_events(lambda: ops.lowrank_forward(xs[0], a, b, None), iters=30) for _ in range(3))
-    print(f"PTD_GEMM_DEEP={os.environ.get('PTD_GEMM_DEEP', '5')} r={r}: x A^T {t1 * 1e6:.1f} us (one buffer) {t2 * 1e6:.1f} us (rotating), pair {t3 * 1e6:.1f} us", flush=True)
+    print(f"r={r}: x A^T {t1 * 1e6:.1f} us (one buffer) {t2 * 1e6:.1f} us (rotating), pair {t3 * 1e6:.1f} us", flush=True)
