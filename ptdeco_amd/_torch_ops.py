@@ -166,6 +166,16 @@ def _(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
     return x2d.new_empty((x2d.shape[0], Bg.shape[0]))
 
 
+def _route_q(tag, regimes, expression, x2d, *w):
+    """The body of a quantised pair's operator: the first of the format's regimes whose rule takes the operands as they
+    lie (ops.lowrank_<regime>_<tag>_serves, then ops.lowrank_<regime>_<tag>; both looked up when the body runs), else the
+    torch expression."""
+    for regime in regimes:
+        if getattr(ops, f"lowrank_{regime}_{tag}_serves")(x2d, *w):
+            return getattr(ops, f"lowrank_{regime}_{tag}")(x2d, *w)
+    return expression(x2d, *w).contiguous()
+
+
 def lowrank_w8_expression(x: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
                           bias: Optional[torch.Tensor]) -> torch.Tensor:
     """The semantics of the fp8 pair in torch, D = x.dtype: h = round_D(sa * (x Aq^T)), y = round_D(sb * (h Bq^T) + bias),
@@ -189,11 +199,7 @@ def lowrank_forward_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq
     96: ops.lowrank_skinny_w8_serves) on the skinny products of ptd_lowrank_skinny_w8; both keep the sums in f32 and
     round h and y once each.  Elsewhere ``lowrank_w8_expression``: torch's products on transient 16-bit copies of the
     factors, which round once more than the kernels do, inside ``F.linear``.  Inference only: no autograd formula."""
-    if ops.lowrank_decode_w8_serves(x2d, Aq, sa, Bq, sb, bias):
-        return ops.lowrank_decode_w8(x2d, Aq, sa, Bq, sb, bias)
-    if ops.lowrank_skinny_w8_serves(x2d, Aq, sa, Bq, sb, bias):
-        return ops.lowrank_skinny_w8(x2d, Aq, sa, Bq, sb, bias)
-    return lowrank_w8_expression(x2d, Aq, sa, Bq, sb, bias).contiguous()
+    return _route_q("w8", ("decode", "skinny"), lowrank_w8_expression, x2d, Aq, sa, Bq, sb, bias)
 
 
 @lowrank_forward_w8.register_fake
@@ -272,13 +278,7 @@ def lowrank_forward_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq
     dequantises both factors into the workspace and the 16-bit tile pair on them; all three keep the sums in f32 and
     round h and y once each.  Elsewhere ``lowrank_w4_expression``: torch's products on transient 16-bit copies of the
     factors.  Inference only: no autograd formula."""
-    if ops.lowrank_decode_w4_serves(x2d, Aq, ea, Bq, eb, bias):
-        return ops.lowrank_decode_w4(x2d, Aq, ea, Bq, eb, bias)
-    if ops.lowrank_skinny_w4_serves(x2d, Aq, ea, Bq, eb, bias):
-        return ops.lowrank_skinny_w4(x2d, Aq, ea, Bq, eb, bias)
-    if ops.lowrank_tile_w4_serves(x2d, Aq, ea, Bq, eb, bias):
-        return ops.lowrank_tile_w4(x2d, Aq, ea, Bq, eb, bias)
-    return lowrank_w4_expression(x2d, Aq, ea, Bq, eb, bias).contiguous()
+    return _route_q("w4", ("decode", "skinny", "tile"), lowrank_w4_expression, x2d, Aq, ea, Bq, eb, bias)
 
 
 @lowrank_forward_w4.register_fake
@@ -343,13 +343,7 @@ def lowrank_forward_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq
     ptd_lowrank_tile_w6, one launch that dequantises both factors into the workspace and the 16-bit tile pair on them;
     all three keep the sums in f32 and round h and y once each.  Elsewhere ``lowrank_w6_expression``: torch's products on transient 16-bit copies of the factors.  Inference
     only: no autograd formula."""
-    if ops.lowrank_decode_w6_serves(x2d, Aq, ea, Bq, eb, bias):
-        return ops.lowrank_decode_w6(x2d, Aq, ea, Bq, eb, bias)
-    if ops.lowrank_skinny_w6_serves(x2d, Aq, ea, Bq, eb, bias):
-        return ops.lowrank_skinny_w6(x2d, Aq, ea, Bq, eb, bias)
-    if ops.lowrank_tile_w6_serves(x2d, Aq, ea, Bq, eb, bias):
-        return ops.lowrank_tile_w6(x2d, Aq, ea, Bq, eb, bias)
-    return lowrank_w6_expression(x2d, Aq, ea, Bq, eb, bias).contiguous()
+    return _route_q("w6", ("decode", "skinny", "tile"), lowrank_w6_expression, x2d, Aq, ea, Bq, eb, bias)
 
 
 @lowrank_forward_w6.register_fake

@@ -507,45 +507,21 @@ int ptd_lowrank_decode(const void* x, int64_t ldx, int64_t T, int64_t n_i, const
   return lowrank_decode(x, ldx, T, n_i, A, lda, r, B, ldb, n_o, bias, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
 }
 
-size_t ptd_lowrank_decode_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
-  return lowrank_decode_w8_workspace_bytes(T, n_i, r, dtype);
-}
-
-int ptd_lowrank_decode_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
-                          const float* scale_a, int64_t r, const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o,
-                          const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format,
-                          void* stream) {
-  PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "ptd_lowrank_decode_w8: null pointer");
-  PTD_REQUIRE(ldx >= n_i && lda >= n_i && ldb >= r && ldy >= n_o, "ptd_lowrank_decode_w8: bad leading dimension");
-  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_decode_w8: the workspace must be 16-byte aligned");
-  // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
-  if (!lowrank_decode_w8_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, scale_a, Bq, ldb, scale_b, bias)) {
-    set_error("ptd_lowrank_decode_w8: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d w_format=%d: bf16 / f16, "
-              "PTD_W8_FP8_E4M3, 1 <= T <= 16, r >= 16, n_i and r multiples of 16, 16-byte aligned rows)", (long long)T,
-              (long long)n_i, (long long)r, (long long)n_o, dtype, w_format);
-    return PTD_ERR_UNSUPPORTED;
-  }
-  if (ws_bytes < lowrank_decode_w8_workspace_bytes(T, n_i, r, dtype)) {
-    set_error("ptd_lowrank_decode_w8: workspace %zu < required %zu bytes", ws_bytes,
-              lowrank_decode_w8_workspace_bytes(T, n_i, r, dtype));
-    return PTD_ERR_WORKSPACE;
-  }
-  return lowrank_decode_w8(x, ldx, T, n_i, Aq, lda, scale_a, r, Bq, ldb, scale_b, n_o, bias, y, ldy, ws, dtype,
-                           static_cast<hipStream_t>(stream));
-}
-
-// What precedes a launch of an MX entry `name`, in the order it is reported: null pointers, leading dimensions (lda, ldb,
-// ldsa and ldsb in bytes: code_a / code_b code bytes per row of A / B -- n / 2 for MXFP4, 3 (n / 4) for MXFP6 -- and one
-// scale byte per 32 weights), the workspace's alignment, what the kernels serve (`served`: the entry's *_serves; `rule`:
+// What precedes a launch of the quantised-pair entry `name`, in the order it is reported: null pointers, leading
+// dimensions (lda and ldb in bytes: code_a / code_b code bytes per row of A / B -- n for fp8, n / 2 for MXFP4, 3 (n / 4)
+// for MXFP6; with `block_scales`, the MX formats, ldsa and ldsb too: one scale byte per 32 weights -- fp8's row scales have
+// no pitch), the workspace's alignment, what the kernels serve (`served`: the entry's *_serves; `rule`:
 // what it asks for, for the message) and the workspace's size (`need`: the entry's *_workspace_bytes).
 #define PTD_STR_(v) #v
 #define PTD_STR(v) PTD_STR_(v)
-static int mx_entry_checks(const char* name, const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
-                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
-                           int64_t ldsb, int64_t n_o, const void* y, int64_t ldy, const void* ws, size_t ws_bytes, int dtype,
-                           int w_format, int64_t code_a, int64_t code_b, bool served, const char* rule, size_t need) {
+static int q_entry_checks(const char* name, const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                          const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                          int64_t ldsb, int64_t n_o, const void* y, int64_t ldy, const void* ws, size_t ws_bytes, int dtype,
+                          int w_format, int64_t code_a, int64_t code_b, bool block_scales, bool served, const char* rule,
+                          size_t need) {
   PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "%s: null pointer", name);
-  PTD_REQUIRE(ldx >= n_i && lda >= code_a && ldb >= code_b && ldsa >= n_i / 32 && ldsb >= r / 32 && ldy >= n_o,
+  PTD_REQUIRE(ldx >= n_i && lda >= code_a && ldb >= code_b && (!block_scales || (ldsa >= n_i / 32 && ldsb >= r / 32)) &&
+                  ldy >= n_o,
               "%s: bad leading dimension", name);
   PTD_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", name);
   // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
@@ -561,6 +537,25 @@ static int mx_entry_checks(const char* name, const void* x, int64_t ldx, int64_t
   return PTD_OK;
 }
 
+size_t ptd_lowrank_decode_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
+  return lowrank_decode_w8_workspace_bytes(T, n_i, r, dtype);
+}
+
+int ptd_lowrank_decode_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                          const float* scale_a, int64_t r, const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o,
+                          const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format,
+                          void* stream) {
+  const int rc = q_entry_checks("ptd_lowrank_decode_w8", x, ldx, T, n_i, Aq, lda, scale_a, 0, r, Bq, ldb, scale_b, 0, n_o, y,
+                                ldy, ws, ws_bytes, dtype, w_format, n_i, r, false,
+                                lowrank_decode_w8_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, scale_a, Bq, ldb,
+                                                         scale_b, bias),
+                                "PTD_W8_FP8_E4M3, 1 <= T <= 16, r >= 16, n_i and r multiples of 16, 16-byte aligned rows",
+                                lowrank_decode_w8_workspace_bytes(T, n_i, r, dtype));
+  if (rc != PTD_OK) return rc;
+  return lowrank_decode_w8(x, ldx, T, n_i, Aq, lda, scale_a, r, Bq, ldb, scale_b, n_o, bias, y, ldy, ws, dtype,
+                           static_cast<hipStream_t>(stream));
+}
+
 size_t ptd_lowrank_decode_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
   return lowrank_decode_w4_workspace_bytes(T, n_i, r, dtype);
 }
@@ -569,11 +564,11 @@ int ptd_lowrank_decode_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
                           int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
                           int dtype, int w_format, void* stream) {
-  const int rc = mx_entry_checks("ptd_lowrank_decode_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
-                                 ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2,
-                                 lowrank_decode_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
-                                 "PTD_W4_MXFP4, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, 16-byte aligned rows",
-                                 lowrank_decode_w4_workspace_bytes(T, n_i, r, dtype));
+  const int rc = q_entry_checks("ptd_lowrank_decode_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
+                                ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2, true,
+                                lowrank_decode_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                "PTD_W4_MXFP4, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, 16-byte aligned rows",
+                                lowrank_decode_w4_workspace_bytes(T, n_i, r, dtype));
   if (rc != PTD_OK) return rc;
   return lowrank_decode_w4(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
                            static_cast<hipStream_t>(stream));
@@ -587,11 +582,11 @@ int ptd_lowrank_decode_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
                           int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
                           int dtype, int w_format, void* stream) {
-  const int rc = mx_entry_checks("ptd_lowrank_decode_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
-                                 ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4),
-                                 lowrank_decode_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
-                                 "PTD_W6_MXFP6_E2M3, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, 8-byte aligned rows",
-                                 lowrank_decode_w6_workspace_bytes(T, n_i, r, dtype));
+  const int rc = q_entry_checks("ptd_lowrank_decode_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
+                                ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4), true,
+                                lowrank_decode_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                "PTD_W6_MXFP6_E2M3, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, 8-byte aligned rows",
+                                lowrank_decode_w6_workspace_bytes(T, n_i, r, dtype));
   if (rc != PTD_OK) return rc;
   return lowrank_decode_w6(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
                            static_cast<hipStream_t>(stream));
@@ -701,21 +696,14 @@ int ptd_lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                           const float* scale_a, int64_t r, const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o,
                           const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format,
                           void* stream) {
-  PTD_REQUIRE(x && Aq && scale_a && Bq && scale_b && y && ws, "ptd_lowrank_skinny_w8: null pointer");
-  PTD_REQUIRE(ldx >= n_i && lda >= n_i && ldb >= r && ldy >= n_o, "ptd_lowrank_skinny_w8: bad leading dimension");
-  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_skinny_w8: the workspace must be 16-byte aligned");
-  // (nothing is launched for what the kernels do not serve: the caller evaluates the expression on 16-bit copies)
-  if (!lowrank_skinny_w8_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, scale_a, Bq, ldb, scale_b, bias)) {
-    set_error("ptd_lowrank_skinny_w8: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d w_format=%d: bf16 / f16, "
-              "PTD_W8_FP8_E4M3, 32 <= T <= %d, r >= 16, n_i and r multiples of 16, 16-byte aligned rows)", (long long)T,
-              (long long)n_i, (long long)r, (long long)n_o, dtype, w_format, PTD_LOWRANK_SKINNY_W8_MAX_T);
-    return PTD_ERR_UNSUPPORTED;
-  }
-  if (ws_bytes < lowrank_skinny_w8_workspace_bytes(T, n_i, r, dtype)) {
-    set_error("ptd_lowrank_skinny_w8: workspace %zu < required %zu bytes", ws_bytes,
-              lowrank_skinny_w8_workspace_bytes(T, n_i, r, dtype));
-    return PTD_ERR_WORKSPACE;
-  }
+  const int rc = q_entry_checks("ptd_lowrank_skinny_w8", x, ldx, T, n_i, Aq, lda, scale_a, 0, r, Bq, ldb, scale_b, 0, n_o, y,
+                                ldy, ws, ws_bytes, dtype, w_format, n_i, r, false,
+                                lowrank_skinny_w8_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, scale_a, Bq, ldb,
+                                                         scale_b, bias),
+                                "PTD_W8_FP8_E4M3, 32 <= T <= " PTD_STR(PTD_LOWRANK_SKINNY_W8_MAX_T)
+                                ", r >= 16, n_i and r multiples of 16, 16-byte aligned rows",
+                                lowrank_skinny_w8_workspace_bytes(T, n_i, r, dtype));
+  if (rc != PTD_OK) return rc;
   return lowrank_skinny_w8(x, ldx, T, n_i, Aq, lda, scale_a, r, Bq, ldb, scale_b, n_o, bias, y, ldy, ws, dtype,
                            static_cast<hipStream_t>(stream));
 }
@@ -728,12 +716,12 @@ int ptd_lowrank_skinny_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
                           int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
                           int dtype, int w_format, void* stream) {
-  const int rc = mx_entry_checks("ptd_lowrank_skinny_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
-                                 ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2,
-                                 lowrank_skinny_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
-                                 "PTD_W4_MXFP4, 32 <= T <= " PTD_STR(PTD_LOWRANK_SKINNY_W4_MAX_T)
-                                 ", r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
-                                 lowrank_skinny_w4_workspace_bytes(T, n_i, r, dtype));
+  const int rc = q_entry_checks("ptd_lowrank_skinny_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
+                                ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2, true,
+                                lowrank_skinny_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                "PTD_W4_MXFP4, 32 <= T <= " PTD_STR(PTD_LOWRANK_SKINNY_W4_MAX_T)
+                                ", r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
+                                lowrank_skinny_w4_workspace_bytes(T, n_i, r, dtype));
   if (rc != PTD_OK) return rc;
   return lowrank_skinny_w4(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
                            static_cast<hipStream_t>(stream));
@@ -747,12 +735,12 @@ int ptd_lowrank_skinny_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
                           int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
                           int dtype, int w_format, void* stream) {
-  const int rc = mx_entry_checks("ptd_lowrank_skinny_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
-                                 ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4),
-                                 lowrank_skinny_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
-                                 "PTD_W6_MXFP6_E2M3, 32 <= T <= " PTD_STR(PTD_LOWRANK_SKINNY_W6_MAX_T)
-                                 ", r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
-                                 lowrank_skinny_w6_workspace_bytes(T, n_i, r, dtype));
+  const int rc = q_entry_checks("ptd_lowrank_skinny_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b,
+                                ldsb, n_o, y, ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4), true,
+                                lowrank_skinny_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                "PTD_W6_MXFP6_E2M3, 32 <= T <= " PTD_STR(PTD_LOWRANK_SKINNY_W6_MAX_T)
+                                ", r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
+                                lowrank_skinny_w6_workspace_bytes(T, n_i, r, dtype));
   if (rc != PTD_OK) return rc;
   return lowrank_skinny_w6(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
                            static_cast<hipStream_t>(stream));
@@ -815,11 +803,11 @@ int ptd_lowrank_tile_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, cons
                         const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
                         int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
                         int dtype, int w_format, void* stream) {
-  int rc = mx_entry_checks("ptd_lowrank_tile_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, y,
-                           ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2,
-                           lowrank_tile_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
-                           "PTD_W4_MXFP4, T >= 1, r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
-                           lowrank_tile_mx_workspace_bytes(T, n_i, r, n_o, dtype));
+  int rc = q_entry_checks("ptd_lowrank_tile_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, y,
+                          ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2, true,
+                          lowrank_tile_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                          "PTD_W4_MXFP4, T >= 1, r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
+                          lowrank_tile_mx_workspace_bytes(T, n_i, r, n_o, dtype));
   if (rc != PTD_OK) return rc;
   rc = lowrank_tile_w4_dequant(Aq, lda, scale_a, ldsa, n_i, r, Bq, ldb, scale_b, ldsb, n_o, ws, dtype,
                                static_cast<hipStream_t>(stream));
@@ -835,11 +823,11 @@ int ptd_lowrank_tile_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, cons
                         const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
                         int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
                         int dtype, int w_format, void* stream) {
-  int rc = mx_entry_checks("ptd_lowrank_tile_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, y,
-                           ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4),
-                           lowrank_tile_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
-                           "PTD_W6_MXFP6_E2M3, T >= 1, r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
-                           lowrank_tile_mx_workspace_bytes(T, n_i, r, n_o, dtype));
+  int rc = q_entry_checks("ptd_lowrank_tile_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, y,
+                          ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4), true,
+                          lowrank_tile_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                          "PTD_W6_MXFP6_E2M3, T >= 1, r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
+                          lowrank_tile_mx_workspace_bytes(T, n_i, r, n_o, dtype));
   if (rc != PTD_OK) return rc;
   rc = lowrank_tile_w6_dequant(Aq, lda, scale_a, ldsa, n_i, r, Bq, ldb, scale_b, ldsb, n_o, ws, dtype,
                                static_cast<hipStream_t>(stream));

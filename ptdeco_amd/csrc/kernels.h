@@ -122,8 +122,9 @@ int lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i, con
                          const void* Bu, int64_t ldb_u, const void* bias_u, int64_t n_o, int act, void* y, int64_t ldy,
                          void* ws, int dtype, hipStream_t st);
 
-// lowrank_skinny_w8.hip: the fp8 pair of lowrank_decode_w8.hip at 32 <= T <= 96 tokens with the structure of
-// lowrank_skinny.hip: three launches, weights converted in registers (ptd_lowrank_skinny_w8)
+// lowrank_skinny_w8.hip (the kernel bodies of every quantised skinny pair: lowrank_skinny_q.h): the fp8 pair of
+// lowrank_decode_w8.hip at 32 <= T <= PTD_LOWRANK_SKINNY_W8_MAX_T tokens with the structure of lowrank_skinny.hip: three
+// launches, a lane's 16-byte load converted in registers, row scales where the sums are complete (ptd_lowrank_skinny_w8)
 bool lowrank_skinny_w8_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
                               int64_t ldx, const void* Aq, int64_t lda, const float* sa, const void* Bq, int64_t ldb,
                               const float* sb, const void* bias);
@@ -132,8 +133,8 @@ int lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const 
                       int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
                       int64_t ldy, void* ws, int dtype, hipStream_t st);
 
-// lowrank_skinny_w4.hip (the kernel bodies: lowrank_skinny_mx.h): the MXFP4 pair of lowrank_decode_mx.hip at 32 <= T <= PTD_LOWRANK_SKINNY_W4_MAX_T tokens with the
-// structure of lowrank_skinny_w8.hip: three launches, a lane's 8-byte load is half a block, converted in registers with
+// lowrank_skinny_w4.hip: the same kernel bodies on the MXFP4 pair of lowrank_decode_mx.hip at 32 <= T <=
+// PTD_LOWRANK_SKINNY_W4_MAX_T tokens: three launches, a lane's 8-byte load is half a block, converted in registers with
 // its block scale (ptd_lowrank_skinny_w4)
 bool lowrank_skinny_w4_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
                               int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias);

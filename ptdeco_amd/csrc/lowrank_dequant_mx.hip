@@ -102,7 +102,7 @@ int dequant(const void* q, int64_t ldq, const void* e, int64_t lde, int64_t rows
   return launch_dequant<F>(dq_side(q, ldq, e, lde, rows, cols, out, ldo), none, dtype, what, st);
 }
 
-// the skinny MX rule on the operands (skinny_mx_serves of lowrank_skinny_mx.h) at any T >= 1
+// the skinny MX rule on the operands (skinny_q_serves of lowrank_skinny_q.h on an MX trait) at any T >= 1
 template <typename F>
 bool tile_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x, int64_t ldx,
                  const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias) {

@@ -43,7 +43,7 @@ inline int mx_xa_blocks(int kchunk) {
 // U of the second product: 2; 1 only where a row of B is a single block, r = 32
 inline int mx_hb_blocks(int64_t r) { return r >= 2 * MX_BLOCK ? 2 : 1; }
 
-// lowrank_skinny_w4.hip: the scale bytes a lane fetches per 64-k step of a product over rows of k_total weights (n_i in
+// lowrank_skinny_q.h on block scales: the scale bytes a lane fetches per 64-k step of a product over rows of k_total weights (n_i in
 // the first product, r in the second) -- the step's two blocks in one load; one only where a row is a single block
 inline int mx_sk_scale_bytes(int64_t k_total) { return k_total >= 2 * MX_BLOCK ? 2 : 1; }
 

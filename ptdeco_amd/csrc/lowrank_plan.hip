@@ -95,7 +95,7 @@ void plan_decode_mx(int* out, int64_t n_i, int64_t r, int64_t n_o) {
   out[PTD_PLAN_HB_U] = ub, out[PTD_PLAN_HB_TAIL_BLOCKS] = (int)(r / MX_BLOCK % ub);
 }
 
-// lowrank_skinny.hip and lowrank_skinny_w8.hip: one split, one grid rule
+// lowrank_skinny.hip and lowrank_skinny_q.h (the fp8 instance, lowrank_skinny_w8.hip, as it is): one split, one grid rule
 void plan_skinny(int* out, int64_t T, int64_t n_i, int64_t r, int64_t n_o) {
   int nslabs, kchunk;
   int asked, unused;
@@ -119,7 +119,7 @@ void plan_skinny(int* out, int64_t T, int64_t n_i, int64_t r, int64_t n_o) {
   out[PTD_PLAN_TOKEN_TILES] = tiles;
 }
 
-// lowrank_skinny_mx.h (MXFP4 and MXFP6 alike): the skinny split and grids; the variant of each product is the scale bytes of one load
+// lowrank_skinny_q.h on block scales (MXFP4 and MXFP6 alike): the skinny split and grids; the variant of each product is the scale bytes of one load
 void plan_skinny_w4(int* out, int64_t T, int64_t n_i, int64_t r, int64_t n_o) {
   plan_skinny(out, T, n_i, r, n_o);
   const int ua = mx_sk_scale_bytes(n_i), ub = mx_sk_scale_bytes(r);

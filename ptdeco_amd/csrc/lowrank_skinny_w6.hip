@@ -1,10 +1,10 @@
-// ptd_lowrank_skinny_w6: the MXFP6 (e2m3) instance of lowrank_skinny_mx.h -- the format's skinny trait (what a lane's piece
+// ptd_lowrank_skinny_w6: the MXFP6 (e2m3) instance of lowrank_skinny_q.h -- the format's skinny trait (what a lane's piece
 // is in memory and how it becomes the two MFMA operands of a step), the names of its kernels and its C++ entry.
 // The piece is 12 bytes at byte 12 (k / 16) of the row, 4-byte aligned: ONE global_load_dwordx3 per row fragment and
 // step, converted by one v_cvt_scalef32_pk32_{bf16,f16}_fp6 whose upper source half is zero.
-#define SKINNY_MX_PRODUCT_KERNEL skinny_w6_product_kernel
-#define SKINNY_MX_COMBINE_KERNEL skinny_w6_combine_kernel
-#include "lowrank_skinny_mx.h"
+#define SKINNY_Q_PRODUCT_KERNEL skinny_w6_product_kernel
+#define SKINNY_Q_COMBINE_KERNEL skinny_w6_combine_kernel
+#include "lowrank_skinny_q.h"
 #include "lowrank_w6.h"
 
 namespace ptd {
@@ -15,7 +15,7 @@ typedef unsigned int u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
 
 // What a lane's piece (16 codes, half an MX block) is in memory and how it becomes the A operands of the step's two
 // MFMAs, w[j] holding k = 8 j + 0..7 of the piece -- k 4..7 before k 0..3 in the odd lane groups.
-struct SkMxFp6 : MxFp6 {
+struct SkMxFp6 : MxFp6, SkMx {
   static constexpr int MAX_T = PTD_LOWRANK_SKINNY_W6_MAX_T;      // the cap of the route (measured: profiles/pair_skinny_w6.json)
   typedef u32x3 piece;                                           // 12 bytes: 16 six-bit codes, 4-byte aligned
   static constexpr const char* XA_LAUNCH = "ptd_lowrank_skinny_w6 (first product)";
@@ -52,19 +52,19 @@ struct SkMxFp6 : MxFp6 {
 
 bool lowrank_skinny_w6_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
                               int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias) {
-  return skinny_mx_serves<SkMxFp6>(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias);
+  return skinny_q_serves<SkMxFp6>(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, nullptr, Bq, ldb, nullptr, bias);
 }
 
 size_t lowrank_skinny_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
   (void)n_i;
   (void)dtype;
-  return skinny_mx_workspace_bytes(T, r);
+  return skinny_q_workspace_bytes(T, r);
 }
 
 int lowrank_skinny_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea,
                       int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
                       const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st) {
-  return skinny_mx<SkMxFp6>(x, ldx, T, n_i, Aq, lda, ea, ldsa, r, Bq, ldb, eb, ldsb, n_o, bias, y, ldy, ws, dtype, st);
+  return skinny_q<SkMxFp6>(x, ldx, T, n_i, Aq, lda, ea, ldsa, r, Bq, ldb, eb, ldsb, n_o, bias, y, ldy, ws, dtype, st);
 }
 
 }  // namespace ptd

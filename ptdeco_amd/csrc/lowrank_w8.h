@@ -1,7 +1,7 @@
-// What the fp8 (OCP e4m3fn) kernels of lowrank_decode_w8.hip and lowrank_skinny_w8.hip share: a lane's 16-byte load of
-// an fp8 weight row (k = 16 (l >> 4) + 0..15 of a 64-deep step) converted in the lane to the A operands of two
-// v_mfma_f32_16x16x32_{bf16,f16}.  Every e4m3 value is exact in bf16 and in f16, so the conversion (scale 1.0) rounds
-// nothing.
+// What the fp8 (OCP e4m3fn) kernels of lowrank_decode_w8.hip and lowrank_skinny_w8.hip (the fp8 trait of
+// lowrank_skinny_q.h) share: a lane's 16-byte load of an fp8 weight row (k = 16 (l >> 4) + 0..15 of a 64-deep step)
+// converted in the lane to the A operands of two v_mfma_f32_16x16x32_{bf16,f16}.  Every e4m3 value is exact in bf16 and
+// in f16, so the conversion (scale 1.0) rounds nothing.
 #pragma once
 
 #include <algorithm>

@@ -7,7 +7,7 @@ import contextlib
 import ctypes
 import dataclasses
 import os
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -382,30 +382,61 @@ _DECODE = os.environ.get("PTD_LOWRANK_DECODE", "1") != "0"
 _DECODE_MAX_T = 16
 
 
+class _Facts(NamedTuple):
+    """What a serving rule looks at of one tensor, as plain Python values."""
+    shape: Tuple[int, ...]
+    stride: Tuple[int, ...]
+    dtype: torch.dtype
+    ptr: int
+
+
+def _facts(*ts: Optional[torch.Tensor]) -> Optional[list]:
+    """The gate of every serving rule: the facts of real tensors on a ROCm device (None stays None), or None where one
+    of them is something else -- CPU, meta, FakeTensor and other subclasses have no data pointer to look at.  Loads no
+    library.  What the rule then asks of the facts is a pure function (``_pair16_rule``, ``_q_rule``): the rule of the
+    C entry, which tests/test_pair_rules_cpu.py holds against that entry fact by fact."""
+    out = []
+    for t in ts:
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
+                return None
+            t = _Facts(t.shape, t.stride(), t.dtype, t.data_ptr())
+        out.append(t)
+    return out
+
+
+def _pair16_rule(regime: str, x: _Facts, A: _Facts, B: _Facts, bias: Optional[_Facts]) -> bool:
+    """The rule of ptd_lowrank_decode (``regime`` "decode") / ptd_lowrank_skinny ("skinny") on plain facts."""
+    if len(x.shape) != 2 or len(A.shape) != 2 or len(B.shape) != 2 or not (x.dtype == A.dtype == B.dtype):
+        return False
+    if regime == "decode":
+        dtypes, lo, hi = (torch.float32, torch.bfloat16, torch.float16), 1, _DECODE_MAX_T
+    else:
+        dtypes, lo, hi = (torch.bfloat16, torch.float16), _SKINNY_MIN_T, _SKINNY_MAX_T
+    if x.dtype not in dtypes:
+        return False
+    vec = 4 if x.dtype == torch.float32 else 8
+    (T, n_i), r, n_o = x.shape, A.shape[0], B.shape[0]
+    if A.shape[1] != n_i or B.shape[1] != r or not lo <= T <= hi or n_o < 1 or r < 8 or n_i % vec or r % vec:
+        return False
+    if regime == "skinny" and n_i < 8:
+        return False
+    if bias is not None and (len(bias.shape) != 1 or bias.shape[0] != n_o):      # (the bias dtype is not looked at)
+        return False
+    for t in (x, A, B):
+        if t.stride[1] != 1 or t.stride[0] < t.shape[1] or t.stride[0] % vec or t.ptr % 16:
+            return False
+    return True
+
+
 def lowrank_decode_serves(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> bool:
     """Whether ``lowrank_decode`` takes these operands as they lie (the rule of ptd_lowrank_decode, without loading the
     library): real tensors on a ROCm device, f32 / bf16 / f16, 1 <= T <= 16, r >= 8, n_i, r and the row pitches
     multiples of 8 (f32: 4) elements, unit inner strides, 16-byte aligned data."""
     if not _DECODE:
         return False
-    ts = (x2d, A, B) if bias is None else (x2d, A, B, bias)
-    for t in ts:
-        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
-            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
-    if x2d.dim() != 2 or A.dim() != 2 or B.dim() != 2 or not (x2d.dtype == A.dtype == B.dtype):
-        return False
-    if x2d.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return False
-    vec = 4 if x2d.dtype == torch.float32 else 8
-    (T, n_i), r, n_o = x2d.shape, A.shape[0], B.shape[0]
-    if A.shape[1] != n_i or B.shape[1] != r or not 1 <= T <= _DECODE_MAX_T or n_o < 1 or r < 8 or n_i % vec or r % vec:
-        return False
-    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o):
-        return False
-    for t in (x2d, A, B):
-        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % 16:
-            return False
-    return True
+    f = _facts(x2d, A, B, bias)
+    return f is not None and _pair16_rule("decode", *f)
 
 
 def lowrank_decode(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
@@ -437,68 +468,6 @@ _DECODE_W8 = os.environ.get("PTD_LOWRANK_DECODE_W8", "1") != "0"
 W8_FP8_E4M3 = 0
 
 
-def lowrank_decode_w8_serves(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
-                             bias: Optional[torch.Tensor]) -> bool:
-    """Whether ``lowrank_decode_w8`` takes these operands as they lie (the rule of ptd_lowrank_decode_w8, without
-    loading the library): real tensors on a ROCm device, x2d bf16 / f16, Aq and Bq float8_e4m3fn, sa and sb contiguous
-    f32, 1 <= T <= 16, r >= 16, n_i and r multiples of 16, weight row pitches multiples of 16 bytes, x2d's a multiple of
-    8 elements, unit inner strides, 16-byte aligned data."""
-    if not _DECODE_W8:
-        return False
-    ts = (x2d, Aq, sa, Bq, sb) if bias is None else (x2d, Aq, sa, Bq, sb, bias)
-    for t in ts:
-        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
-            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
-    if x2d.dim() != 2 or Aq.dim() != 2 or Bq.dim() != 2 or sa.dim() != 1 or sb.dim() != 1:
-        return False
-    if x2d.dtype not in (torch.bfloat16, torch.float16) or Aq.dtype != torch.float8_e4m3fn or Bq.dtype != Aq.dtype:
-        return False
-    if sa.dtype != torch.float32 or sb.dtype != torch.float32:
-        return False
-    (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
-    if Aq.shape[1] != n_i or Bq.shape[1] != r or sa.shape[0] != r or sb.shape[0] != n_o:
-        return False
-    if not 1 <= T <= _DECODE_MAX_T or n_o < 1 or r < 16 or n_i % 16 or r % 16:
-        return False
-    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o or bias.dtype != x2d.dtype
-                             or (n_o > 1 and bias.stride(0) != 1)):
-        return False
-    for t, vec in ((x2d, 8), (Aq, 16), (Bq, 16)):
-        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % 16:
-            return False
-    for s in (sa, sb):
-        if (s.shape[0] > 1 and s.stride(0) != 1) or s.data_ptr() % 4:
-            return False
-    return True
-
-
-def lowrank_decode_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
-                      bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """round(sb * (h @ Bq^T) + bias) with h = round(sa * (x2d @ Aq^T)) for 1 <= T <= 16 rows of x2d (bf16 / f16), Aq
-    [r, n_i] and Bq [n_o, r] float8_e4m3fn, sa [r] and sb [n_o] f32: ptd_lowrank_decode_w8 (sums in f32, each rounded
-    once to x2d's dtype).  Operands the entry does not serve (``lowrank_decode_w8_serves``) raise; row t of the result
-    depends on row t of x2d alone."""
-    _dev(x2d, Aq, sa, Bq, sb, bias)
-    x2d, Aq, Bq = _rows2d(x2d), _rows2d(Aq), _rows2d(Bq)
-    T, n_i = x2d.shape
-    r, n_o = Aq.shape[0], Bq.shape[0]
-    assert Aq.shape[1] == n_i and Bq.shape[1] == r and sa.shape == (r,) and sb.shape == (n_o,)
-    assert Aq.dtype == Bq.dtype == torch.float8_e4m3fn and sa.dtype == sb.dtype == torch.float32
-    sa, sb = sa.contiguous(), sb.contiguous()
-    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
-    lib = _hip.load()
-    ws_bytes = lib.ptd_lowrank_decode_w8_workspace_bytes(T, n_i, r, _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    if bias is not None:
-        bias = bias.to(x2d.dtype).contiguous()
-    with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_decode_w8(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0), sa.data_ptr(),
-                                       r, Bq.data_ptr(), Bq.stride(0), sb.data_ptr(), n_o, _ptr(bias), y.data_ptr(), n_o,
-                                       ws.data_ptr(), ws_bytes, _code(x2d), W8_FP8_E4M3, _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_decode_w8")
-    return y
-
-
 # The pair with OCP MX factors at decode shapes -- MXFP4 (packed e2m1 codes, 16 bytes per block of 32 weights) on
 # ptd_lowrank_decode_w4, MXFP6 (e2m3, packed 6-bit codes, 24 bytes per block) on ptd_lowrank_decode_w6, one e8m0 scale
 # byte per block in both: the same two weight-streaming kernels on a quarter / on 0.39 of the 16-bit pair's bytes.
@@ -511,84 +480,141 @@ W6_MXFP6_E2M3 = 0
 
 
 @dataclasses.dataclass(frozen=True)
-class _MxFormat:
-    """What differs between the MX entries, decode and skinny (the formats of csrc/lowrank_w4.h and csrc/lowrank_w6.h)."""
-    name: str            # for messages
-    entry: str           # ptd_<entry> and ptd_<entry>_workspace_bytes: the decode entry
-    block_bytes: int     # code bytes per 32 weights
-    pitch: int           # a code row's pitch is a multiple of this many bytes (decode; skinny: 8 for both formats)
-    align: int           # the codes' base address is a multiple of this many bytes (decode; skinny: 8)
-    code: int            # w_format of the entries
-    switch: str          # the module attribute (read from the environment once, at import) that enables the decode entry
-    skinny_entry: str    # ptd_<skinny_entry> and ptd_<skinny_entry>_workspace_bytes: the small-batch entry,
-    skinny_switch: str   #   the module attribute that enables it
-    skinny_cap: str      #   and the one that holds its largest T
-    tile_entry: str      # ptd_<tile_entry> and ptd_<tile_entry>_workspace_bytes: every other T, on the tile products,
-    tile_switch: str     #   the module attribute that enables it
-    dequant_entry: str   #   and ptd_<dequant_entry>: one factor as its 16-bit values
+class _QFormat:
+    """A quantised weight format of the pair: what differs between the entries ptd_lowrank_<regime>_<tag>, their serving
+    rules and their calls (csrc/lowrank_w8.h, lowrank_w4.h, lowrank_w6.h; regimes "decode", "skinny" and, for the MX
+    formats, "tile")."""
+    name: str                  # for messages
+    tag: str                   # w8 / w4 / w6: the entries, the switches _<REGIME>_<TAG> and the cap _SKINNY_<TAG>_MAX_T
+    code: int                  # w_format of the entries
+    bits: int                  # of a code: a row of n weights is n bits / 8 bytes
+    code_dtype: torch.dtype
+    scale_dtype: torch.dtype
+    scale_rank: int            # 1: one scale per factor row (contiguous); 2: rows of one scale byte per 32 weights
+    scale_align: int           # a scale array's base address is a multiple of this many bytes
+    quantum: int               # n_i and r are multiples of it, r at least it
+    n_i_min: int               # (the fp8 rules never asked more of n_i than the multiple)
+    pitch: dict                # regime -> (a code row's pitch, the codes' base address): multiples of this many bytes
 
     def row_bytes(self, n: int) -> int:
-        return n // 32 * self.block_bytes
+        return n * self.bits // 8
+
+    def scale_shape(self, rows: int, n: int) -> tuple:
+        return (rows,) if self.scale_rank == 1 else (rows, n // 32)
+
+    def switch(self, regime: str) -> str:
+        """The module attribute (read from the environment once, at import) that enables the regime's entry."""
+        return f"_{regime.upper()}_{self.tag.upper()}"
+
+    @property
+    def skinny_cap(self) -> str:
+        """The module attribute that holds the largest T of the skinny entry."""
+        return f"_SKINNY_{self.tag.upper()}_MAX_T"
 
 
-_MXFP4 = _MxFormat("MXFP4", "lowrank_decode_w4", 16, 16, 16, W4_MXFP4, "_DECODE_W4",
-                   "lowrank_skinny_w4", "_SKINNY_W4", "_SKINNY_W4_MAX_T",
-                   "lowrank_tile_w4", "_TILE_W4", "lowrank_dequant_w4")
-_MXFP6 = _MxFormat("MXFP6", "lowrank_decode_w6", 24, 8, 8, W6_MXFP6_E2M3, "_DECODE_W6",
-                   "lowrank_skinny_w6", "_SKINNY_W6", "_SKINNY_W6_MAX_T",
-                   "lowrank_tile_w6", "_TILE_W6", "lowrank_dequant_w6")
+_FP8 = _QFormat("fp8", "w8", W8_FP8_E4M3, 8, torch.float8_e4m3fn, torch.float32, 1, 4, 16, 0,
+                {"decode": (16, 16), "skinny": (16, 16)})
+_MXFP4 = _QFormat("MXFP4", "w4", W4_MXFP4, 4, torch.uint8, torch.uint8, 2, 1, 32, 32,
+                  {"decode": (16, 16), "skinny": (8, 8), "tile": (8, 8)})      # (skinny: a lane's piece is half a block)
+_MXFP6 = _QFormat("MXFP6", "w6", W6_MXFP6_E2M3, 6, torch.uint8, torch.uint8, 2, 1, 32, 32,
+                  {"decode": (8, 8), "skinny": (8, 8), "tile": (8, 8)})
 
 
-def _mx_decode_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
-    if not globals()[fmt.switch]:
+def _q_operands(fmt: _QFormat, regime: str, x: _Facts, Aq: _Facts, ea: _Facts, Bq: _Facts, eb: _Facts,
+                bias: Optional[_Facts]) -> bool:
+    """The rule of ptd_lowrank_<regime>_<tag> on plain facts, on everything but the token count (the skinny and the tile
+    entries of a format take the same operands).  The decode rules lack the skinny rules' size limits."""
+    if len(x.shape) != 2 or len(Aq.shape) != 2 or len(Bq.shape) != 2 or any(len(e.shape) != fmt.scale_rank for e in (ea, eb)):
         return False
-    ts = (x2d, Aq, ea, Bq, eb) if bias is None else (x2d, Aq, ea, Bq, eb, bias)
-    for t in ts:
-        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
-            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
-    if any(t.dim() != 2 for t in (x2d, Aq, ea, Bq, eb)) or any(t.dtype != torch.uint8 for t in (Aq, ea, Bq, eb)):
+    if x.dtype not in (torch.bfloat16, torch.float16) or Aq.dtype != fmt.code_dtype or Bq.dtype != fmt.code_dtype:
         return False
-    if x2d.dtype not in (torch.bfloat16, torch.float16):
+    if ea.dtype != fmt.scale_dtype or eb.dtype != fmt.scale_dtype:
         return False
-    (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
-    if not 1 <= T <= _DECODE_MAX_T or n_o < 1 or r < 32 or n_i < 32 or n_i % 32 or r % 32:
+    (T, n_i), r, n_o = x.shape, Aq.shape[0], Bq.shape[0]
+    if T < 1 or n_o < 1 or r < fmt.quantum or n_i < fmt.n_i_min or n_i % fmt.quantum or r % fmt.quantum:
         return False
-    if (tuple(Aq.shape) != (r, fmt.row_bytes(n_i)) or tuple(ea.shape) != (r, n_i // 32)
-            or tuple(Bq.shape) != (n_o, fmt.row_bytes(r)) or tuple(eb.shape) != (n_o, r // 32)):
+    if regime != "decode" and (n_i >= 1 << 30 or r >= 1 << 27 or n_o >= 1 << 30):
         return False
-    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o or bias.dtype != x2d.dtype
-                             or (n_o > 1 and bias.stride(0) != 1)):
+    if (tuple(Aq.shape) != (r, fmt.row_bytes(n_i)) or tuple(ea.shape) != fmt.scale_shape(r, n_i)
+            or tuple(Bq.shape) != (n_o, fmt.row_bytes(r)) or tuple(eb.shape) != fmt.scale_shape(n_o, r)):
         return False
-    for t, vec, align in ((x2d, 8, 16), (Aq, fmt.pitch, fmt.align), (Bq, fmt.pitch, fmt.align)):
-        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % align:
+    if bias is not None and (len(bias.shape) != 1 or bias.shape[0] != n_o or bias.dtype != x.dtype
+                             or (n_o > 1 and bias.stride[0] != 1)):
+        return False
+    for t, (vec, align) in ((x, (8, 16)), (Aq, fmt.pitch[regime]), (Bq, fmt.pitch[regime])):
+        if t.stride[1] != 1 or t.stride[0] < t.shape[1] or t.stride[0] % vec or t.ptr % align:
             return False
-    for e in (ea, eb):
-        if (e.shape[1] > 1 and e.stride(1) != 1) or e.stride(0) < e.shape[1]:
+    for e in (ea, eb):      # (unit inner stride; scale rows need no alignment, row scales that of an f32)
+        if (e.shape[-1] > 1 and e.stride[-1] != 1) or (fmt.scale_rank == 2 and e.stride[0] < e.shape[1]) or e.ptr % fmt.scale_align:
             return False
     return True
 
 
-def _mx_decode(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> torch.Tensor:
+def _q_rule(fmt: _QFormat, regime: str, x: _Facts, Aq: _Facts, ea: _Facts, Bq: _Facts, eb: _Facts,
+            bias: Optional[_Facts]) -> bool:
+    """``_q_operands`` at the token counts of the regime (tile: the measured cells of ``_tile_mx_takes``, narrower than
+    the C entry, which serves every T >= 1)."""
+    if not _q_operands(fmt, regime, x, Aq, ea, Bq, eb, bias):
+        return False
+    T = x.shape[0]
+    if regime == "decode":
+        return 1 <= T <= _DECODE_MAX_T
+    if regime == "skinny":
+        return _SKINNY_MIN_T <= T <= globals()[fmt.skinny_cap]
+    return _tile_mx_takes(fmt, T, x.shape[1], Bq.shape[0])
+
+
+def _q_serves(fmt: _QFormat, regime: str, x2d, Aq, ea, Bq, eb, bias) -> bool:
+    if not globals()[fmt.switch(regime)]:
+        return False
+    f = _facts(x2d, Aq, ea, Bq, eb, bias)
+    return f is not None and _q_rule(fmt, regime, *f)
+
+
+def _q_call(fmt: _QFormat, regime: str, x2d, Aq, ea, Bq, eb, bias) -> torch.Tensor:
+    """ptd_lowrank_<regime>_<tag> on these operands: the workspace, the bias in x2d's dtype, the argument list."""
     _dev(x2d, Aq, ea, Bq, eb, bias)
-    x2d, Aq, ea, Bq, eb = _rows2d(x2d), _rows2d(Aq), _rows2d(ea), _rows2d(Bq), _rows2d(eb)
+    x2d, Aq, Bq = _rows2d(x2d), _rows2d(Aq), _rows2d(Bq)
+    ea, eb = (ea.contiguous(), eb.contiguous()) if fmt.scale_rank == 1 else (_rows2d(ea), _rows2d(eb))
     T, n_i = x2d.shape
     r, n_o = Aq.shape[0], Bq.shape[0]
-    assert all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)) and n_i % 32 == 0 and r % 32 == 0
-    assert Aq.shape == (r, fmt.row_bytes(n_i)) and ea.shape == (r, n_i // 32)
-    assert Bq.shape == (n_o, fmt.row_bytes(r)) and eb.shape == (n_o, r // 32)
+    assert Aq.dtype == Bq.dtype == fmt.code_dtype and ea.dtype == eb.dtype == fmt.scale_dtype
+    assert fmt.scale_rank == 1 or (n_i % 32 == 0 and r % 32 == 0)
+    assert Aq.shape == (r, fmt.row_bytes(n_i)) and ea.shape == fmt.scale_shape(r, n_i)
+    assert Bq.shape == (n_o, fmt.row_bytes(r)) and eb.shape == fmt.scale_shape(n_o, r)
     y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
     lib = _hip.load()
-    ws_bytes = getattr(lib, f"ptd_{fmt.entry}_workspace_bytes")(T, n_i, r, _code(x2d))
+    entry = f"ptd_lowrank_{regime}_{fmt.tag}"
+    shape = (T, n_i, r, n_o) if regime == "tile" else (T, n_i, r)      # (the tile entry holds both factors too)
+    ws_bytes = getattr(lib, entry + "_workspace_bytes")(*shape, _code(x2d))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
     if bias is not None:
         bias = bias.to(x2d.dtype).contiguous()
+    a = (Aq.data_ptr(), Aq.stride(0), ea.data_ptr()) + ((ea.stride(0),) if fmt.scale_rank == 2 else ())
+    b = (Bq.data_ptr(), Bq.stride(0), eb.data_ptr()) + ((eb.stride(0),) if fmt.scale_rank == 2 else ())
     with torch.cuda.device(x2d.device):
-        rc = getattr(lib, f"ptd_{fmt.entry}")(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0),
-                                              ea.data_ptr(), ea.stride(0), r, Bq.data_ptr(), Bq.stride(0), eb.data_ptr(),
-                                              eb.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o, ws.data_ptr(), ws_bytes,
-                                              _code(x2d), fmt.code, _stream(x2d))
-    _hip.check(rc, f"ptd_{fmt.entry}")
+        rc = getattr(lib, entry)(x2d.data_ptr(), x2d.stride(0), T, n_i, *a, r, *b, n_o, _ptr(bias), y.data_ptr(), n_o,
+                                 ws.data_ptr(), ws_bytes, _code(x2d), fmt.code, _stream(x2d))
+    _hip.check(rc, entry)
     return y
+
+
+def lowrank_decode_w8_serves(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                             bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``lowrank_decode_w8`` takes these operands as they lie (the rule of ptd_lowrank_decode_w8, without
+    loading the library): real tensors on a ROCm device, x2d bf16 / f16, Aq and Bq float8_e4m3fn, sa and sb contiguous
+    f32, 1 <= T <= 16, r >= 16, n_i and r multiples of 16, weight row pitches multiples of 16 bytes, x2d's a multiple of
+    8 elements, unit inner strides, 16-byte aligned data."""
+    return _q_serves(_FP8, "decode", x2d, Aq, sa, Bq, sb, bias)
+
+
+def lowrank_decode_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                      bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """round(sb * (h @ Bq^T) + bias) with h = round(sa * (x2d @ Aq^T)) for 1 <= T <= 16 rows of x2d (bf16 / f16), Aq
+    [r, n_i] and Bq [n_o, r] float8_e4m3fn, sa [r] and sb [n_o] f32: ptd_lowrank_decode_w8 (sums in f32, each rounded
+    once to x2d's dtype).  Operands the entry does not serve (``lowrank_decode_w8_serves``) raise; row t of the result
+    depends on row t of x2d alone."""
+    return _q_call(_FP8, "decode", x2d, Aq, sa, Bq, sb, bias)
 
 
 def lowrank_decode_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -598,7 +624,7 @@ def lowrank_decode_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tens
     [n_o, r / 2] and eb [n_o, r / 32] uint8, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, code row pitches
     multiples of 16 bytes, x2d's a multiple of 8 elements, unit inner strides, x2d and the codes 16-byte aligned (the
     scale rows need no alignment)."""
-    return _mx_decode_serves(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+    return _q_serves(_MXFP4, "decode", x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_decode_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -608,7 +634,7 @@ def lowrank_decode_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq:
     scales clamped to [114, 140], all uint8): ptd_lowrank_decode_w4 (sums in f32, each rounded once to x2d's dtype).
     Operands the entry does not serve (``lowrank_decode_w4_serves``) raise; row t of the result depends on row t of x2d
     alone."""
-    return _mx_decode(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+    return _q_call(_MXFP4, "decode", x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_decode_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -618,7 +644,7 @@ def lowrank_decode_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tens
     [n_o, 3 r / 4] and eb [n_o, r / 32] uint8, 1 <= T <= 16, r >= 32, n_i and r multiples of 32, code row pitches
     multiples of 8 bytes, x2d's a multiple of 8 elements, unit inner strides, x2d 16-byte and the codes 8-byte aligned
     (the scale rows need no alignment)."""
-    return _mx_decode_serves(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+    return _q_serves(_MXFP6, "decode", x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_decode_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -628,7 +654,7 @@ def lowrank_decode_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq:
     e8m0 block scales clamped to [116, 140], all uint8): ptd_lowrank_decode_w6 (sums in f32, each rounded once to x2d's
     dtype).  Operands the entry does not serve (``lowrank_decode_w6_serves``) raise; row t of the result depends on row
     t of x2d alone."""
-    return _mx_decode(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+    return _q_call(_MXFP6, "decode", x2d, Aq, ea, Bq, eb, bias)
 
 
 # Pairs that read one input at decode shapes (q / k / v, gate / up) run on ptd_lowrank_decode_group: two launches for the
@@ -738,25 +764,8 @@ def lowrank_skinny_serves(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, b
     pitches multiples of 8 elements, unit inner strides, 16-byte aligned data."""
     if not _SKINNY:
         return False
-    ts = (x2d, A, B) if bias is None else (x2d, A, B, bias)
-    for t in ts:
-        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
-            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
-    if x2d.dim() != 2 or A.dim() != 2 or B.dim() != 2 or not (x2d.dtype == A.dtype == B.dtype):
-        return False
-    if x2d.dtype not in (torch.bfloat16, torch.float16):
-        return False
-    (T, n_i), r, n_o = x2d.shape, A.shape[0], B.shape[0]
-    if A.shape[1] != n_i or B.shape[1] != r or not _SKINNY_MIN_T <= T <= _SKINNY_MAX_T:
-        return False
-    if n_o < 1 or r < 8 or n_i < 8 or n_i % 8 or r % 8:
-        return False
-    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o):
-        return False
-    for t in (x2d, A, B):
-        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % 8 or t.data_ptr() % 16:
-            return False
-    return True
+    f = _facts(x2d, A, B, bias)
+    return f is not None and _pair16_rule("skinny", *f)
 
 
 def lowrank_skinny(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
@@ -798,35 +807,7 @@ def lowrank_skinny_w8_serves(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tens
     loading the library): real tensors on a ROCm device, x2d bf16 / f16, Aq and Bq float8_e4m3fn, sa and sb contiguous
     f32, _SKINNY_MIN_T <= T <= _SKINNY_W8_MAX_T, r >= 16, n_i and r multiples of 16, weight row pitches multiples of 16
     bytes, x2d's a multiple of 8 elements, unit inner strides, 16-byte aligned data."""
-    if not _SKINNY_W8:
-        return False
-    ts = (x2d, Aq, sa, Bq, sb) if bias is None else (x2d, Aq, sa, Bq, sb, bias)
-    for t in ts:
-        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
-            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
-    if x2d.dim() != 2 or Aq.dim() != 2 or Bq.dim() != 2 or sa.dim() != 1 or sb.dim() != 1:
-        return False
-    if x2d.dtype not in (torch.bfloat16, torch.float16) or Aq.dtype != torch.float8_e4m3fn or Bq.dtype != Aq.dtype:
-        return False
-    if sa.dtype != torch.float32 or sb.dtype != torch.float32:
-        return False
-    (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
-    if Aq.shape[1] != n_i or Bq.shape[1] != r or sa.shape[0] != r or sb.shape[0] != n_o:
-        return False
-    if not _SKINNY_MIN_T <= T <= _SKINNY_W8_MAX_T or n_o < 1 or r < 16 or n_i % 16 or r % 16:
-        return False
-    if n_i >= 1 << 30 or r >= 1 << 27 or n_o >= 1 << 30:
-        return False
-    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o or bias.dtype != x2d.dtype
-                             or (n_o > 1 and bias.stride(0) != 1)):
-        return False
-    for t, vec in ((x2d, 8), (Aq, 16), (Bq, 16)):
-        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % 16:
-            return False
-    for s in (sa, sb):
-        if (s.shape[0] > 1 and s.stride(0) != 1) or s.data_ptr() % 4:
-            return False
-    return True
+    return _q_serves(_FP8, "skinny", x2d, Aq, sa, Bq, sb, bias)
 
 
 def lowrank_skinny_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
@@ -835,25 +816,7 @@ def lowrank_skinny_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq:
     (bf16 / f16), Aq [r, n_i] and Bq [n_o, r] float8_e4m3fn, sa [r] and sb [n_o] f32: ptd_lowrank_skinny_w8 (sums in
     f32, each rounded once to x2d's dtype).  Operands the entry does not serve (``lowrank_skinny_w8_serves``) raise; row
     t of the result depends on row t of x2d alone."""
-    _dev(x2d, Aq, sa, Bq, sb, bias)
-    x2d, Aq, Bq = _rows2d(x2d), _rows2d(Aq), _rows2d(Bq)
-    T, n_i = x2d.shape
-    r, n_o = Aq.shape[0], Bq.shape[0]
-    assert Aq.shape[1] == n_i and Bq.shape[1] == r and sa.shape == (r,) and sb.shape == (n_o,)
-    assert Aq.dtype == Bq.dtype == torch.float8_e4m3fn and sa.dtype == sb.dtype == torch.float32
-    sa, sb = sa.contiguous(), sb.contiguous()
-    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
-    lib = _hip.load()
-    ws_bytes = lib.ptd_lowrank_skinny_w8_workspace_bytes(T, n_i, r, _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    if bias is not None:
-        bias = bias.to(x2d.dtype).contiguous()
-    with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_skinny_w8(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0), sa.data_ptr(),
-                                       r, Bq.data_ptr(), Bq.stride(0), sb.data_ptr(), n_o, _ptr(bias), y.data_ptr(), n_o,
-                                       ws.data_ptr(), ws_bytes, _code(x2d), W8_FP8_E4M3, _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_skinny_w8")
-    return y
+    return _q_call(_FP8, "skinny", x2d, Aq, sa, Bq, sb, bias)
 
 
 # The MX pairs of lowrank_decode_w4 / lowrank_decode_w6 at small batches (32 <= T <= the format's cap) run on
@@ -869,67 +832,6 @@ _SKINNY_W6 = os.environ.get("PTD_LOWRANK_SKINNY_W6", "1") != "0"
 _SKINNY_W6_MAX_T = 96
 
 
-def _mx_skinny_operands(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
-    """The rule of the skinny MX entries on everything but the token count (the tile MX entries take the same operands)."""
-    ts = (x2d, Aq, ea, Bq, eb) if bias is None else (x2d, Aq, ea, Bq, eb, bias)
-    for t in ts:
-        if not isinstance(t, torch.Tensor) or type(t) not in (torch.Tensor, torch.nn.Parameter) or not t.is_cuda:
-            return False     # (CPU, meta, FakeTensor and other subclasses: no data pointer to look at)
-    if any(t.dim() != 2 for t in (x2d, Aq, ea, Bq, eb)) or any(t.dtype != torch.uint8 for t in (Aq, ea, Bq, eb)):
-        return False
-    if x2d.dtype not in (torch.bfloat16, torch.float16):
-        return False
-    (T, n_i), r, n_o = x2d.shape, Aq.shape[0], Bq.shape[0]
-    if T < 1 or n_o < 1 or r < 32 or n_i < 32 or n_i % 32 or r % 32:
-        return False
-    if n_i >= 1 << 30 or r >= 1 << 27 or n_o >= 1 << 30:
-        return False
-    if (tuple(Aq.shape) != (r, fmt.row_bytes(n_i)) or tuple(ea.shape) != (r, n_i // 32)
-            or tuple(Bq.shape) != (n_o, fmt.row_bytes(r)) or tuple(eb.shape) != (n_o, r // 32)):
-        return False
-    if bias is not None and (bias.dim() != 1 or bias.shape[0] != n_o or bias.dtype != x2d.dtype
-                             or (n_o > 1 and bias.stride(0) != 1)):
-        return False
-    for t, vec, align in ((x2d, 8, 16), (Aq, 8, 8), (Bq, 8, 8)):      # (a lane's piece is half a block: both formats)
-        if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % vec or t.data_ptr() % align:
-            return False
-    for e in (ea, eb):
-        if (e.shape[1] > 1 and e.stride(1) != 1) or e.stride(0) < e.shape[1]:
-            return False
-    return True
-
-
-def _mx_skinny_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
-    if not globals()[fmt.skinny_switch]:
-        return False
-    if not _mx_skinny_operands(fmt, x2d, Aq, ea, Bq, eb, bias):
-        return False
-    return _SKINNY_MIN_T <= x2d.shape[0] <= globals()[fmt.skinny_cap]
-
-
-def _mx_skinny(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> torch.Tensor:
-    _dev(x2d, Aq, ea, Bq, eb, bias)
-    x2d, Aq, ea, Bq, eb = _rows2d(x2d), _rows2d(Aq), _rows2d(ea), _rows2d(Bq), _rows2d(eb)
-    T, n_i = x2d.shape
-    r, n_o = Aq.shape[0], Bq.shape[0]
-    assert all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)) and n_i % 32 == 0 and r % 32 == 0
-    assert Aq.shape == (r, fmt.row_bytes(n_i)) and ea.shape == (r, n_i // 32)
-    assert Bq.shape == (n_o, fmt.row_bytes(r)) and eb.shape == (n_o, r // 32)
-    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
-    lib = _hip.load()
-    ws_bytes = getattr(lib, f"ptd_{fmt.skinny_entry}_workspace_bytes")(T, n_i, r, _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    if bias is not None:
-        bias = bias.to(x2d.dtype).contiguous()
-    with torch.cuda.device(x2d.device):
-        rc = getattr(lib, f"ptd_{fmt.skinny_entry}")(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0),
-                                                     ea.data_ptr(), ea.stride(0), r, Bq.data_ptr(), Bq.stride(0),
-                                                     eb.data_ptr(), eb.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o,
-                                                     ws.data_ptr(), ws_bytes, _code(x2d), fmt.code, _stream(x2d))
-    _hip.check(rc, f"ptd_{fmt.skinny_entry}")
-    return y
-
-
 def lowrank_skinny_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
                              bias: Optional[torch.Tensor]) -> bool:
     """Whether ``lowrank_skinny_w4`` takes these operands as they lie (the rule of ptd_lowrank_skinny_w4, without
@@ -937,7 +839,7 @@ def lowrank_skinny_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tens
     [n_o, r / 2] and eb [n_o, r / 32] uint8, _SKINNY_MIN_T <= T <= _SKINNY_W4_MAX_T, r >= 32, n_i and r multiples of 32,
     code row pitches multiples of 8 bytes, x2d's a multiple of 8 elements, unit inner strides, x2d 16-byte and the codes
     8-byte aligned (the scale rows need no alignment)."""
-    return _mx_skinny_serves(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+    return _q_serves(_MXFP4, "skinny", x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_skinny_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -946,7 +848,7 @@ def lowrank_skinny_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq:
     B^ the MXFP4 factors of ``lowrank_decode_w4``: ptd_lowrank_skinny_w4 (sums in f32, each rounded once to x2d's
     dtype).  Operands the entry does not serve (``lowrank_skinny_w4_serves``) raise; row t of the result depends on row
     t of x2d alone."""
-    return _mx_skinny(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+    return _q_call(_MXFP4, "skinny", x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_skinny_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -956,7 +858,7 @@ def lowrank_skinny_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tens
     [n_o, 3 r / 4] and eb [n_o, r / 32] uint8, _SKINNY_MIN_T <= T <= _SKINNY_W6_MAX_T, r >= 32, n_i and r multiples of
     32, code row pitches multiples of 8 bytes, x2d's a multiple of 8 elements, unit inner strides, x2d 16-byte and the
     codes 8-byte aligned (the scale rows need no alignment)."""
-    return _mx_skinny_serves(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+    return _q_serves(_MXFP6, "skinny", x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_skinny_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -965,7 +867,7 @@ def lowrank_skinny_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq:
     B^ the MXFP6 (e2m3) factors of ``lowrank_decode_w6``: ptd_lowrank_skinny_w6 (sums in f32, each rounded once to
     x2d's dtype).  Operands the entry does not serve (``lowrank_skinny_w6_serves``) raise; row t of the result depends
     on row t of x2d alone."""
-    return _mx_skinny(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+    return _q_call(_MXFP6, "skinny", x2d, Aq, ea, Bq, eb, bias)
 
 
 # The MX pairs at every other token count (17 <= T < _SKINNY_MIN_T and T above the format's skinny cap: prompt
@@ -987,7 +889,7 @@ _TILE_MX_MIN_T = _DECODE_MAX_T + 1
 _TILE_MX_SMALL_T_RATIO = {"MXFP4": 2, "MXFP6": 1}
 
 
-def _tile_mx_takes(fmt: _MxFormat, T: int, n_i: int, n_o: int) -> bool:
+def _tile_mx_takes(fmt: _QFormat, T: int, n_i: int, n_o: int) -> bool:
     """The (T, shape) cells the tile MX entries own: T above the format's skinny cap, and 17 <= T < _SKINNY_MIN_T where
     the layer's output is wide enough against its input for the entry to beat the expression (measured, above)."""
     if T > globals()[fmt.skinny_cap]:
@@ -995,38 +897,7 @@ def _tile_mx_takes(fmt: _MxFormat, T: int, n_i: int, n_o: int) -> bool:
     return _TILE_MX_MIN_T <= T < _SKINNY_MIN_T and n_o >= _TILE_MX_SMALL_T_RATIO[fmt.name] * n_i
 
 
-def _mx_tile_serves(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
-    if not globals()[fmt.tile_switch]:
-        return False
-    if not _mx_skinny_operands(fmt, x2d, Aq, ea, Bq, eb, bias):
-        return False
-    return _tile_mx_takes(fmt, x2d.shape[0], x2d.shape[1], Bq.shape[0])
-
-
-def _mx_tile(fmt: _MxFormat, x2d, Aq, ea, Bq, eb, bias) -> torch.Tensor:
-    _dev(x2d, Aq, ea, Bq, eb, bias)
-    x2d, Aq, ea, Bq, eb = _rows2d(x2d), _rows2d(Aq), _rows2d(ea), _rows2d(Bq), _rows2d(eb)
-    T, n_i = x2d.shape
-    r, n_o = Aq.shape[0], Bq.shape[0]
-    assert all(t.dtype == torch.uint8 for t in (Aq, ea, Bq, eb)) and n_i % 32 == 0 and r % 32 == 0
-    assert Aq.shape == (r, fmt.row_bytes(n_i)) and ea.shape == (r, n_i // 32)
-    assert Bq.shape == (n_o, fmt.row_bytes(r)) and eb.shape == (n_o, r // 32)
-    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
-    lib = _hip.load()
-    ws_bytes = getattr(lib, f"ptd_{fmt.tile_entry}_workspace_bytes")(T, n_i, r, n_o, _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    if bias is not None:
-        bias = bias.to(x2d.dtype).contiguous()
-    with torch.cuda.device(x2d.device):
-        rc = getattr(lib, f"ptd_{fmt.tile_entry}")(x2d.data_ptr(), x2d.stride(0), T, n_i, Aq.data_ptr(), Aq.stride(0),
-                                                   ea.data_ptr(), ea.stride(0), r, Bq.data_ptr(), Bq.stride(0),
-                                                   eb.data_ptr(), eb.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o,
-                                                   ws.data_ptr(), ws_bytes, _code(x2d), fmt.code, _stream(x2d))
-    _hip.check(rc, f"ptd_{fmt.tile_entry}")
-    return y
-
-
-def _mx_dequant(fmt: _MxFormat, q, e, dtype) -> torch.Tensor:
+def _mx_dequant(fmt: _QFormat, q, e, dtype) -> torch.Tensor:
     _dev(q, e)
     q, e = _rows2d(q), _rows2d(e)
     assert q.dtype == torch.uint8 and e.dtype == torch.uint8 and dtype in (torch.bfloat16, torch.float16)
@@ -1035,9 +906,9 @@ def _mx_dequant(fmt: _MxFormat, q, e, dtype) -> torch.Tensor:
     out = torch.empty((rows, cols), dtype=dtype, device=q.device)
     lib = _hip.load()
     with torch.cuda.device(q.device):
-        rc = getattr(lib, f"ptd_{fmt.dequant_entry}")(q.data_ptr(), q.stride(0), e.data_ptr(), e.stride(0), rows, cols,
+        rc = getattr(lib, f"ptd_lowrank_dequant_{fmt.tag}")(q.data_ptr(), q.stride(0), e.data_ptr(), e.stride(0), rows, cols,
                                                       out.data_ptr(), cols, _DT[dtype], fmt.code, _stream(q))
-    _hip.check(rc, f"ptd_{fmt.dequant_entry}")
+    _hip.check(rc, f"ptd_lowrank_dequant_{fmt.tag}")
     return out
 
 
@@ -1060,7 +931,7 @@ def lowrank_tile_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor
     """Whether ``lowrank_tile_w4`` takes these operands as they lie (without loading the library): the operands of
     ``lowrank_skinny_w4_serves`` at T > _SKINNY_W4_MAX_T, and at 17 <= T < _SKINNY_MIN_T where n_o >= 2 n_i (measured:
     ``_tile_mx_takes``) -- by T and the shapes alone, whatever the decode and skinny switches say."""
-    return _mx_tile_serves(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+    return _q_serves(_MXFP4, "tile", x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_tile_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -1069,7 +940,7 @@ def lowrank_tile_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: t
     factors of ``lowrank_decode_w4``: ptd_lowrank_tile_w4 -- one launch dequantises both factors into the workspace
     (exactly), the 16-bit tile pair runs on them.  The bits of ``lowrank_forward(x2d, A^, B^, bias)``.  Operands the C
     entry does not serve raise."""
-    return _mx_tile(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+    return _q_call(_MXFP4, "tile", x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_tile_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -1077,7 +948,7 @@ def lowrank_tile_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor
     """Whether ``lowrank_tile_w6`` takes these operands as they lie (without loading the library): the operands of
     ``lowrank_skinny_w6_serves`` at T > _SKINNY_W6_MAX_T, and at 17 <= T < _SKINNY_MIN_T where n_o >= n_i (measured:
     ``_tile_mx_takes``) -- by T and the shapes alone, whatever the decode and skinny switches say."""
-    return _mx_tile_serves(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+    return _q_serves(_MXFP6, "tile", x2d, Aq, ea, Bq, eb, bias)
 
 
 def lowrank_tile_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
@@ -1086,7 +957,7 @@ def lowrank_tile_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: t
     (e2m3) factors of ``lowrank_decode_w6``: ptd_lowrank_tile_w6 -- one launch dequantises both factors into the
     workspace (exactly), the 16-bit tile pair runs on them.  The bits of ``lowrank_forward(x2d, A^, B^, bias)``.
     Operands the C entry does not serve raise."""
-    return _mx_tile(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+    return _q_call(_MXFP6, "tile", x2d, Aq, ea, Bq, eb, bias)
 
 
 # The gated pair of an MLP at small batches, act(gate(x)) * up(x), runs on ptd_lowrank_skinny_gated: three launches (both
