@@ -52,7 +52,9 @@ extern "C" {
                              *    ptd_lowrank_skinny_w6_workspace_bytes, ptd_lowrank_skinny_w6,
                              *    ptd_lowrank_dequant_w4, ptd_lowrank_dequant_w6,
                              *    ptd_lowrank_tile_w4_workspace_bytes, ptd_lowrank_tile_w4,
-                             *    ptd_lowrank_tile_w6_workspace_bytes, ptd_lowrank_tile_w6) */
+                             *    ptd_lowrank_tile_w6_workspace_bytes, ptd_lowrank_tile_w6,
+                             *    ptd_lowrank_decode_group_q_workspace_bytes, ptd_lowrank_decode_group_q,
+                             *    ptd_lowrank_decode_gated_q_workspace_bytes, ptd_lowrank_decode_gated_q) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -520,6 +522,55 @@ int ptd_lowrank_decode_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                           const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
                           void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 
+/* 1 <= count <= PTD_LOWRANK_GROUP_MAX pairs with quantised factors of ONE format that read the same x at decode shapes
+ * (the q / k / v or gate / up projections of a quantised, decomposed transformer block) in two launches on the caller's
+ * stream instead of two per pair.  q_format: PTD_Q_FP8_E4M3 (operands and semantics of ptd_lowrank_decode_w8: sa[m] [r[m]]
+ * and sb[m] [n_o[m]] are f32 row scales, ldsa and ldsb are ignored and may be NULL), PTD_Q_MXFP4 (ptd_lowrank_decode_w4)
+ * or PTD_Q_MXFP6_E2M3 (ptd_lowrank_decode_w6): sa[m] [r[m], n_i / 32] and sb[m] [n_o[m], r[m] / 32] are e8m0 scale rows
+ * with the pitches ldsa[m] and ldsb[m]; lda and ldb are in bytes.  Member m has its own output y[m] [T, n_o[m]] with row
+ * pitch ldy[m] (the column blocks of one [T, sum n_o] tensor, or unrelated buffers); x, T, n_i and dtype are common.
+ * Every y[m] holds the bits the format's own decode entry gives for that member alone: each member runs with the K
+ * split, the grid and the kernel variant it would have there (ptd_lowrank_plan).  The argument arrays are read before
+ * the call returns and not after it (the call may be captured in a graph).  Served when every member is served by the
+ * format's decode entry with the common x, T, n_i and dtype; anything else, an unknown q_format and count outside
+ * 1 .. PTD_LOWRANK_GROUP_MAX included, returns PTD_ERR_UNSUPPORTED before a kernel is launched.  Null pointers (bias, or
+ * an entry of it, may be NULL), a leading dimension below its row length or a misaligned workspace PTD_ERR_INVALID; a
+ * short workspace PTD_ERR_WORKSPACE.  The workspace is the sum of the members' decode workspaces of that format. */
+#define PTD_Q_FP8_E4M3 1
+#define PTD_Q_MXFP4 2
+#define PTD_Q_MXFP6_E2M3 3
+size_t ptd_lowrank_decode_group_q_workspace_bytes(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r,
+                                                  int dtype);
+int ptd_lowrank_decode_group_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, int count,
+                               const void* const* Aq, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                               const int64_t* r,
+                               const void* const* Bq, const int64_t* ldb, const void* const* sb, const int64_t* ldsb,
+                               const int64_t* n_o,
+                               const void* const* bias /* entries may be NULL; the array may be NULL */,
+                               void* const* y, const int64_t* ldy,
+                               void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* The gated pair of a quantised, decomposed MLP at decode shapes, y = act(gate(x)) * up(x), gate and up pairs with
+ * factors of one q_format (operands per member as in ptd_lowrank_decode_group_q; for fp8 ldsa_* and ldsb_* are ignored)
+ * on the same x [T, n_i], in two launches on the caller's stream: both first products, then a kernel that forms both
+ * second products row tile by row tile and applies the activation and the product in the lane that holds both sums.
+ * With D the dtype: g = round_D(sb_g * acc_g + bias_g) (MX: no sb factor) and u likewise are the bits the format's decode
+ * entry stores for gate and up, and y = round_D(round_D(act(g)) * u) -- the rounding points of the unfused act(g) * u,
+ * act as in ptd_lowrank_decode_gated.  Served when both members are served by the format's decode entry with the common
+ * x, T, n_i, n_ff and dtype and act is one of PTD_ACT_*; anything else, an unknown q_format included, returns
+ * PTD_ERR_UNSUPPORTED before a kernel is launched.  Null pointers (either bias may be NULL), a leading dimension below
+ * its row length or a misaligned workspace PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  The workspace is the
+ * sum of the two members' decode workspaces of that format. */
+size_t ptd_lowrank_decode_gated_q_workspace_bytes(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u,
+                                                  int dtype);
+int ptd_lowrank_decode_gated_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                               const void* Aq_g, int64_t lda_g, const void* sa_g, int64_t ldsa_g, int64_t r_g,
+                               const void* Bq_g, int64_t ldb_g, const void* sb_g, int64_t ldsb_g, const void* bias_g,
+                               const void* Aq_u, int64_t lda_u, const void* sa_u, int64_t ldsa_u, int64_t r_u,
+                               const void* Bq_u, int64_t ldb_u, const void* sb_u, int64_t ldsb_u, const void* bias_u,
+                               int64_t n_ff, int act, void* y, int64_t ldy,
+                               void* ws, size_t ws_bytes, int dtype, void* stream);
+
 /* The pair with OCP MXFP6 (e2m3) factors (arguments, formats and semantics of ptd_lowrank_decode_w6, clamp to
  * [116, 140] included: h and y from f32 sums, each rounded ONCE; no per-row scales) for 32 <= T <=
  * PTD_LOWRANK_SKINNY_W6_MAX_T tokens, with the structure of ptd_lowrank_skinny_w4 -- the same kernel template: three
@@ -607,7 +658,9 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
  * dtype) with contiguous, aligned operands -- computed by the functions the launchers and kernels themselves call, so a
  * test can prove which branch combination a shape reaches.  family: PTD_PLAN_DECODE (ptd_lowrank_decode; every member
  * of ptd_lowrank_decode_group and both members of ptd_lowrank_decode_gated take the plan of that member alone),
- * PTD_PLAN_DECODE_W8, PTD_PLAN_DECODE_W4, PTD_PLAN_SKINNY (ptd_lowrank_skinny; both members of
+ * PTD_PLAN_DECODE_W8, PTD_PLAN_DECODE_W4 (every member of ptd_lowrank_decode_group_q and both members of
+ * ptd_lowrank_decode_gated_q take the plan of PTD_PLAN_DECODE_W8 / _W4 / _W6 for that member alone, the kernel variants
+ * xa_u and hb_u included), PTD_PLAN_SKINNY (ptd_lowrank_skinny; both members of
  * ptd_lowrank_skinny_gated take the plan of that member alone), PTD_PLAN_SKINNY_W8, PTD_PLAN_SKINNY_W4 (xa_u and hb_u:
  * the scale bytes of one load, 1 or 2; the tail fields: blocks of a row % that -- non-zero: the last block's scale byte
  * comes out of the clamped, shifted load), PTD_PLAN_DECODE_W6 (ptd_lowrank_decode_w6: every field with the meaning

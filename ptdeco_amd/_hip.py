@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libptdeco_hip.so")
 
 F32, F64, BF16, F16 = 0, 1, 2, 3
 ABI_VERSION = 6
+Q_FP8_E4M3, Q_MXFP4, Q_MXFP6_E2M3 = 1, 2, 3      # PTD_Q_*: q_format of the grouped and gated quantised decode entries
 
 # name -> (restype, argtypes); must list every symbol include/ptdeco_hip.h declares
 SIGNATURES = {
@@ -96,6 +97,18 @@ SIGNATURES = {
                                          c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
                                          c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
                                          c_int64, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]),
+    "ptd_lowrank_decode_group_q_workspace_bytes": (c_size_t, [c_int, c_int, c_int64, c_int64, c_void_p, c_int]),
+    "ptd_lowrank_decode_group_q": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ptd_lowrank_decode_gated_q_workspace_bytes": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64, c_int]),
+    "ptd_lowrank_decode_gated_q": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                           c_int64, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]),
     "ptd_lowrank_skinny_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
     "ptd_lowrank_skinny": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
                                    c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int,

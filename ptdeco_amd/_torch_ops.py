@@ -202,16 +202,21 @@ def lowrank_forward_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq
     return _route_q("w8", ("decode", "skinny"), lowrank_w8_expression, x2d, Aq, sa, Bq, sb, bias)
 
 
+def _w8_fake(op, x2d, Aq, sa, Bq, sb, bias):
+    """What the fake kernel of fp8 op ``op`` checks and returns."""
+    torch._check(x2d.dim() == 2 and Aq.dim() == 2 and Bq.dim() == 2, lambda: f"{op}: 2-D operands")
+    torch._check(Aq.shape[1] == x2d.shape[1] and Bq.shape[1] == Aq.shape[0], lambda: f"{op}: shape mismatch")
+    torch._check(tuple(sa.shape) == (Aq.shape[0],) and tuple(sb.shape) == (Bq.shape[0],),
+                 lambda: f"{op}: one scale per factor row")
+    torch._check(Aq.dtype == torch.float8_e4m3fn and Bq.dtype == torch.float8_e4m3fn,
+                 lambda: f"{op}: the factors must be float8_e4m3fn")
+    torch._check(bias is None or tuple(bias.shape) == (Bq.shape[0],), lambda: f"{op}: bias must be [n_o]")
+    return x2d.new_empty((x2d.shape[0], Bq.shape[0]))
+
+
 @lowrank_forward_w8.register_fake
 def _(x2d, Aq, sa, Bq, sb, bias):
-    torch._check(x2d.dim() == 2 and Aq.dim() == 2 and Bq.dim() == 2, lambda: "lowrank_forward_w8: 2-D operands")
-    torch._check(Aq.shape[1] == x2d.shape[1] and Bq.shape[1] == Aq.shape[0], lambda: "lowrank_forward_w8: shape mismatch")
-    torch._check(tuple(sa.shape) == (Aq.shape[0],) and tuple(sb.shape) == (Bq.shape[0],),
-                 lambda: "lowrank_forward_w8: one scale per factor row")
-    torch._check(Aq.dtype == torch.float8_e4m3fn and Bq.dtype == torch.float8_e4m3fn,
-                 lambda: "lowrank_forward_w8: the factors must be float8_e4m3fn")
-    torch._check(bias is None or tuple(bias.shape) == (Bq.shape[0],), lambda: "lowrank_forward_w8: bias must be [n_o]")
-    return x2d.new_empty((x2d.shape[0], Bq.shape[0]))
+    return _w8_fake("lowrank_forward_w8", x2d, Aq, sa, Bq, sb, bias)
 
 
 # e2m1: sign, two exponent bits, one mantissa bit -- the value of code c is (c & 8 ? -1 : 1) * _E2M1[c & 7]
@@ -350,6 +355,89 @@ def lowrank_forward_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq
 def _(x2d, Aq, ea, Bq, eb, bias):
     return _mx_fake("lowrank_forward_w6", lambda n: 3 * n // 4, "Aq [r, 3 n_i / 4], Bq [n_o, 3 r / 4]", x2d, Aq, ea, Bq, eb,
                     bias)
+
+
+# What the grouped and gated operators of quantised members need of a format (``fmt``: the names of ops._Q_FORMATS): the
+# tag, the regimes and the expression of the member's own operator, and its fake kernel's checks.
+_Q_MEMBER = {
+    "fp8": ("w8", ("decode", "skinny"), lowrank_w8_expression, _w8_fake),
+    "MXFP4": ("w4", ("decode", "skinny", "tile"), lowrank_w4_expression,
+              lambda op, *w: _mx_fake(op, lambda n: n // 2, "Aq [r, n_i / 2], Bq [n_o, r / 2]", *w)),
+    "MXFP6": ("w6", ("decode", "skinny", "tile"), lowrank_w6_expression,
+              lambda op, *w: _mx_fake(op, lambda n: 3 * n // 4, "Aq [r, 3 n_i / 4], Bq [n_o, 3 r / 4]", *w)),
+}
+
+
+def _q_member(fmt, x2d, *w):
+    """One quantised member as its own operator runs it: today's result for that member."""
+    tag, regimes, expression, _ = _Q_MEMBER[fmt]
+    return _route_q(tag, regimes, expression, x2d, *w)
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_group_q", mutates_args=())
+def lowrank_forward_group_q(x2d: torch.Tensor, Aqs: List[torch.Tensor], sas: List[torch.Tensor], Bqs: List[torch.Tensor],
+                            sbs: List[torch.Tensor], biases: List[Optional[torch.Tensor]], fmt: str) -> torch.Tensor:
+    """Quantised pairs of one format ``fmt`` ("fp8", "MXFP4", "MXFP6") that share x2d [T, n_i], side by side: y
+    [T, sum n_o] contiguous, member m = (Aqs[m], sas[m], Bqs[m], sbs[m], biases[m]) -- the operands of lowrank_forward_w8 /
+    _w4 / _w6 -- in columns [off_m, off_m + n_o_m).  At decode shapes two launches for the group
+    (ops.lowrank_decode_group_q_serves: ptd_lowrank_decode_group_q, every member's bits those of its own decode entry);
+    otherwise each member as its own operator runs it.  Inference only: no autograd formula."""
+    if fmt not in _Q_MEMBER:
+        raise ValueError(f"fmt must be one of {sorted(_Q_MEMBER)}, got {fmt!r}")
+    if ops.lowrank_decode_group_q_serves(fmt, x2d, Aqs, sas, Bqs, sbs, biases):
+        return ops.lowrank_decode_group_q(fmt, x2d, Aqs, sas, Bqs, sbs, biases)
+    y = x2d.new_empty((x2d.shape[0], sum(Bq.shape[0] for Bq in Bqs)))
+    off = 0
+    for w in zip(Aqs, sas, Bqs, sbs, biases):
+        n_o = w[2].shape[0]
+        y[:, off:off + n_o] = _q_member(fmt, x2d, *w)
+        off += n_o
+    return y
+
+
+@lowrank_forward_group_q.register_fake
+def _(x2d, Aqs, sas, Bqs, sbs, biases, fmt):
+    op = "lowrank_forward_group_q"
+    torch._check(fmt in _Q_MEMBER, lambda: f"{op}: fmt must be one of {sorted(_Q_MEMBER)}")
+    torch._check(len(Aqs) >= 1 and all(len(s) == len(Aqs) for s in (sas, Bqs, sbs, biases)),
+                 lambda: f"{op}: Aqs, sas, Bqs, sbs and biases must list the same members, at least one")
+    fake = _Q_MEMBER[fmt][3]
+    for w in zip(Aqs, sas, Bqs, sbs, biases):
+        fake(op, x2d, *w)
+    return x2d.new_empty((x2d.shape[0], sum(Bq.shape[0] for Bq in Bqs)))
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_gated_q", mutates_args=())
+def lowrank_forward_gated_q(x2d: torch.Tensor, Aq_g: torch.Tensor, s_a_g: torch.Tensor, Bq_g: torch.Tensor,
+                            s_b_g: torch.Tensor, bias_g: Optional[torch.Tensor], Aq_u: torch.Tensor, s_a_u: torch.Tensor,
+                            Bq_u: torch.Tensor, s_b_u: torch.Tensor, bias_u: Optional[torch.Tensor], act: str,
+                            fmt: str) -> torch.Tensor:
+    """act(g) * u for the quantised gate pair and the quantised up pair of one format ``fmt`` on x2d [T, n_i] (operands
+    per member as in lowrank_forward_group_q), act "silu", "gelu_tanh" or "relu": y [T, n_ff] contiguous.  At decode
+    shapes two launches (ops.lowrank_decode_gated_q_serves: ptd_lowrank_decode_gated_q; g and u are the members' own
+    bits, the activation is the kernel's); otherwise g and u as each member's own operator forms them and torch's own
+    activation and product.  Inference only: no autograd formula."""
+    if fmt not in _Q_MEMBER:
+        raise ValueError(f"fmt must be one of {sorted(_Q_MEMBER)}, got {fmt!r}")
+    if act not in GATE_ACTS:
+        raise ValueError(f"act must be one of {sorted(GATE_ACTS)}, got {act!r}")
+    gate, up = (Aq_g, s_a_g, Bq_g, s_b_g, bias_g), (Aq_u, s_a_u, Bq_u, s_b_u, bias_u)
+    if ops.lowrank_decode_gated_q_serves(fmt, x2d, *gate, *up, act):
+        return ops.lowrank_decode_gated_q(fmt, x2d, *gate, *up, act)
+    g, u = _q_member(fmt, x2d, *gate), _q_member(fmt, x2d, *up)
+    return (GATE_ACTS[act](g) * u).contiguous()
+
+
+@lowrank_forward_gated_q.register_fake
+def _(x2d, Aq_g, s_a_g, Bq_g, s_b_g, bias_g, Aq_u, s_a_u, Bq_u, s_b_u, bias_u, act, fmt):
+    op = "lowrank_forward_gated_q"
+    torch._check(fmt in _Q_MEMBER, lambda: f"{op}: fmt must be one of {sorted(_Q_MEMBER)}")
+    torch._check(act in GATE_ACTS, lambda: f"{op}: act must be one of {sorted(GATE_ACTS)}")
+    fake = _Q_MEMBER[fmt][3]
+    fake(op, x2d, Aq_g, s_a_g, Bq_g, s_b_g, bias_g)
+    fake(op, x2d, Aq_u, s_a_u, Bq_u, s_b_u, bias_u)
+    torch._check(Bq_g.shape[0] == Bq_u.shape[0], lambda: f"{op}: gate and up must have the same out_features")
+    return x2d.new_empty((x2d.shape[0], Bq_g.shape[0]))
 
 
 @torch.library.custom_op("ptdeco_amd::lowrank_forward_nchw", mutates_args=())

@@ -104,6 +104,55 @@ int lowrank_decode_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i, con
                          const void* Bu, int64_t ldb_u, const void* bias_u, int64_t n_o, int act, void* y, int64_t ldy,
                          void* ws, int dtype, hipStream_t st);
 
+// lowrank_group_q.hip: the rule, the workspace and nothing else of the decode entry of format q_format (PTD_Q_*) -- those
+// of lowrank_decode_w8 / _w4 / _w6; sa and sb are f32 row scales (fp8) or e8m0 scale rows (MX).  False / 0 for an
+// unknown format
+bool lowrank_decode_q_serves(int q_format, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, const void* x,
+                             int64_t ldx, const void* Aq, int64_t lda, const void* sa, const void* Bq, int64_t ldb,
+                             const void* sb, const void* bias);
+size_t lowrank_decode_q_workspace_bytes(int q_format, int64_t T, int64_t n_i, int64_t r, int dtype);
+
+// lowrank_group_q.hip: 1 .. PTD_LOWRANK_GROUP_MAX pairs with factors of one quantised format on one input at decode shapes
+// in two launches (ptd_lowrank_decode_group_q); every member's bits are those of its format's decode entry on that member
+// alone.  GroupQXa is what the first launch takes, which lowrank_gated_q.hip shares (ldsa: null for fp8)
+struct GroupQXa {
+  const void* x;
+  int64_t ldx, T, n_i;
+  int count;
+  const void* const* Aq;
+  const int64_t* lda;
+  const void* const* sa;
+  const int64_t* ldsa;
+  const int64_t* r;
+  void* ws;
+};
+bool lowrank_decode_group_q_serves(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r, const int64_t* n_o,
+                                   int dtype, const void* x, int64_t ldx, const void* const* Aq, const int64_t* lda,
+                                   const void* const* sa, const void* const* Bq, const int64_t* ldb, const void* const* sb,
+                                   const void* const* bias);
+size_t lowrank_decode_group_q_workspace_bytes(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r, int dtype);
+int lowrank_decode_group_q_xa(int q_format, const GroupQXa& a, int dtype, hipStream_t st);
+int lowrank_decode_group_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, int count,
+                           const void* const* Aq, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                           const int64_t* r, const void* const* Bq, const int64_t* ldb, const void* const* sb,
+                           const int64_t* ldsb, const int64_t* n_o, const void* const* bias, void* const* y,
+                           const int64_t* ldy, void* ws, int dtype, hipStream_t st);
+
+// lowrank_gated_q.hip: act(gate x) * up x for two pairs with factors of one quantised format at decode shapes in two
+// launches (ptd_lowrank_decode_gated_q); g and u are the bits of the format's decode entry, rounded where act(g) * u rounds
+bool lowrank_decode_gated_q_serves(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int64_t n_o, int act,
+                                   int dtype, const void* x, int64_t ldx, const void* Ag, int64_t lda_g, const void* sa_g,
+                                   const void* Bg, int64_t ldb_g, const void* sb_g, const void* bias_g, const void* Au,
+                                   int64_t lda_u, const void* sa_u, const void* Bu, int64_t ldb_u, const void* sb_u,
+                                   const void* bias_u);
+size_t lowrank_decode_gated_q_workspace_bytes(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype);
+int lowrank_decode_gated_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Ag, int64_t lda_g,
+                           const void* sa_g, int64_t ldsa_g, int64_t r_g, const void* Bg, int64_t ldb_g, const void* sb_g,
+                           int64_t ldsb_g, const void* bias_g, const void* Au, int64_t lda_u, const void* sa_u,
+                           int64_t ldsa_u, int64_t r_u, const void* Bu, int64_t ldb_u, const void* sb_u, int64_t ldsb_u,
+                           const void* bias_u, int64_t n_o, int act, void* y, int64_t ldy, void* ws, int dtype,
+                           hipStream_t st);
+
 // lowrank_skinny.hip: the pair at 32 <= T <= 96 tokens (bf16 / f16) as skinny products with a K split (ptd_lowrank_skinny)
 bool lowrank_skinny_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, const void* x, int64_t ldx,
                            const void* A, int64_t lda, const void* B, int64_t ldb);

@@ -122,8 +122,8 @@ __device__ __forceinline__ void decode_xa_body(const typename P::elem* __restric
 }
 
 // The image of h[:, chunk] in `himg` (16 rows of DEC_PITCH bytes) for a second product over r: the slabs added in slab
-// order, rounded once to the operand type.  The only copy: decode_hb_body, lowrank_gated.hip and lowrank_decode_mx.hip
-// call it (the fp8 kernels' staging also applies the row scale and is their own).
+// order, rounded once to the operand type.  The only copy: decode_hb_body, lowrank_gated.hip and the MX trait of
+// lowrank_decode_q.h call it (the fp8 trait's staging also applies the row scale and is its own).
 template <typename P>
 __device__ __forceinline__ void hb_stage(char* himg, const float* __restrict__ slabs, const int nslabs, const int r,
                                          const int T, const int chunk) {
@@ -308,6 +308,29 @@ inline int hb_grid(int64_t n_o) {
   const int64_t ntiles = ceil_div(n_o, 16);
   const int64_t per = ceil_div(ntiles, DEC_HB_MAX_GRID);
   return (int)ceil_div(ntiles, per);
+}
+
+// What the kernels of several pairs per launch share (lowrank_group.hip, lowrank_group_q.hip): the members' own grids are
+// laid end to end, first[p] the first workgroup of the member at position p (INT_MAX behind the last one, so that no
+// workgroup lands there).  Position of workgroup b among them (first[0] = 0); wave-uniform
+__device__ __forceinline__ int group_position(const int (&first)[PTD_LOWRANK_GROUP_MAX], const int b) {
+  int p = 0;
+#pragma unroll
+  for (int i = 1; i < PTD_LOWRANK_GROUP_MAX; ++i) p += b >= first[i];
+  return p;
+}
+
+// where a workgroup stands among those of its member's second product
+struct MemberGrid {
+  unsigned local, grid;
+  __device__ __forceinline__ unsigned tile0() const { return local; }
+  __device__ __forceinline__ unsigned stride() const { return grid; }
+};
+
+// members by descending weight (stable: equal members keep the caller's order)
+inline void by_descending(const int64_t* weight, int count, int (&order)[PTD_LOWRANK_GROUP_MAX]) {
+  for (int i = 0; i < count; ++i) order[i] = i;
+  std::stable_sort(order, order + count, [&](int a, int b) { return weight[a] > weight[b]; });
 }
 
 inline bool nontemporal_weights() {

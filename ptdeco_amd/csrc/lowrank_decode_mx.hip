@@ -34,18 +34,20 @@
 // of a row that exists and meets a zeroed token operand; its scale byte may be anything: the clamp makes the weight
 // finite), no floating-point atomics, one writer per output element, and row t of y is a function of row t of x alone,
 // bit for bit.
+//
+// The bodies of both kernels live in lowrank_decode_q.h (mx_xa_body; MxDec under q_hb_body), which lowrank_group_q.hip and
+// lowrank_gated_q.hip run too: the kernels here hand them blockIdx / gridDim.
 #include "common.h"
 #include "elem16.h"
 #include "kernels.h"
 #include "lowrank_decode.h"
+#include "lowrank_decode_q.h"
 #include "lowrank_w4.h"
 #include "lowrank_w6.h"
 
 namespace ptd {
 
 namespace {
-
-constexpr int MX_CHUNK_BLOCKS = MX_KC / MX_BLOCK;
 
 // slab_s[t, i] for the 16 rows i of blockIdx.x and the K range of blockIdx.y; U consecutive blocks per lane and step
 template <typename F, typename EL, bool NT, int U>
@@ -56,128 +58,17 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_mx_xa_kernel(const unsigne
                                                                    const int64_t ldsa, const int r,
                                                                    float* __restrict__ slabs, const int kchunk) {
   __shared__ f32x4 red[3][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 16 + (lane & 15), tok = lane & 15;
-  const bool row_ok = row < r, tok_ok = tok < T;
-  const int nblk = n_i / MX_BLOCK;
-  int wb, wend;      // the wave's range in blocks: a quarter of kchunk / MX_BLOCK, a multiple of four
-  xa_wave_range((int)blockIdx.y, kchunk / MX_BLOCK, wave, nblk, wb, wend);
-  // Every load is issued, none under a branch: a block outside the wave's range is fetched from the start of a row that
-  // exists, and the TOKEN operand is zeroed instead (its product adds nothing).
-  const unsigned char* wp = A + (int64_t)(row_ok ? row : 0) * lda;
-  const unsigned char* ep = ea + (int64_t)(row_ok ? row : 0) * ldsa;
-  const unsigned short* xp = x + (int64_t)(tok_ok ? tok : 0) * ldx;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  // a super-step is 4 U consecutive blocks of the row: lane group g takes blocks U g + 0 .. U - 1 of it, so the four
-  // groups of a load instruction read adjacent pieces of the row between them
-  for (int sb = wb; sb < wend; sb += 4 * U) {
-    const int b = sb + (lane >> 4) * U;
-    typename F::raw w[U];
-    s16x8 xv[U][4];
-    const unsigned int e = mx_row_scales<U>(ep, b, nblk);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int bo = b + u < wend ? b + u : 0;
-      w[u] = F::template load<NT>(wp + (int64_t)bo * F::BLOCK_BYTES);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) xv[u][q] = *reinterpret_cast<const s16x8*>(xp + (int64_t)bo * MX_BLOCK + 8 * q);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const bool ok = tok_ok && b + u < wend;
-      const typename F::template Cvt<EL> c(w[u], mx_scale<F>(e >> (8 * u)));
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc = EL::mfma16(c.operand(q), ok ? xv[u][q] : s16x8{}, acc);
-    }
-  }
-  if (wave > 0) red[wave - 1][lane] = acc;
-  __syncthreads();
-  if (wave > 0) return;
-  acc += red[0][lane];
-  acc += red[1][lane];
-  acc += red[2][lane];
-  // result layout: column (token) = lane & 15, rows 4 (lane >> 4) + 0..3 -- r is a multiple of 32: all four exist
-  const int row0 = blockIdx.x * 16 + 4 * (lane >> 4);
-  if (tok_ok && row0 < r)
-    *reinterpret_cast<f32x4*>(slabs + ((int64_t)blockIdx.y * T + tok) * r + row0) = acc;
+  mx_xa_body<F, EL, NT, U>(red, x, ldx, T, n_i, A, lda, ea, ldsa, r, slabs, kchunk, blockIdx.x, blockIdx.y);
 }
 
 // y[t, o] for 16 rows o of Bq at a time: tiles blockIdx.x, blockIdx.x + gridDim.x, ...; U blocks per lane and chunk
 // (2; 1 only where a row of B is a single block, r = 32)
 template <typename F, typename EL, bool NT, int U>
-__global__ __launch_bounds__(DEC_THREADS) void decode_mx_hb_kernel(const float* __restrict__ slabs, const int nslabs,
-                                                                   const int T, const int r,
-                                                                   const unsigned char* __restrict__ B, const int64_t ldb,
-                                                                   const unsigned char* __restrict__ eb,
-                                                                   const int64_t ldsb, const int n_o,
-                                                                   const unsigned short* __restrict__ bias,
+__global__ __launch_bounds__(DEC_THREADS) void decode_mx_hb_kernel(const int T, const MxSide m, const int n_o,
                                                                    unsigned short* __restrict__ y, const int64_t ldy) {
-  typedef Dec16<EL> P;
   __shared__ __attribute__((aligned(16))) char himg[16 * DEC_PITCH];
   __shared__ f32x4 red[2][3][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, tok = lane & 15;
-  const bool tok_ok = tok < T;
-  const int ntiles = (n_o + 15) >> 4, nchunks = hb_nchunks(r, MX_KC), nblk = r / MX_BLOCK;
-  // this lane's first block of a chunk: the lane groups of a wave 4 blocks (256 bytes of the image) apart
-  const int bc = 16 * (wave >> 1) + 4 * (lane >> 4) + 2 * (wave & 1);
-
-  // (no load under a branch: a block outside the row is fetched from the row's start and meets a zero token operand;
-  // rows >= n_o read row 0 and are never stored)
-  auto load_tile = [&](typename F::raw (&w)[U], unsigned int& e, int tile, int chunk) {
-    const int row = tile * 16 + (lane & 15), rr = row < n_o ? row : 0;
-    const int b = chunk * MX_CHUNK_BLOCKS + bc;
-    e = mx_row_scales<U>(eb + (int64_t)rr * ldsb, b, nblk);
-    const unsigned char* wp = B + (int64_t)rr * ldb;
-#pragma unroll
-    for (int u = 0; u < U; ++u) w[u] = F::template load<NT>(wp + (b + u < nblk ? b + u : 0) * F::BLOCK_BYTES);
-  };
-  int tile = blockIdx.x;
-  if (tile >= ntiles) return;
-  typename F::raw w[U];
-  unsigned int e;
-  load_tile(w, e, tile, 0);       // in flight while h is staged
-  bool loaded = true;
-  int parity = 0;
-  for (; tile < ntiles; tile += gridDim.x) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int chunk = 0; chunk < nchunks; ++chunk) {
-      if (nchunks > 1 || tile == (int)blockIdx.x) {
-        if (tile != (int)blockIdx.x || chunk > 0) __syncthreads();     // every wave is done with the previous image
-        hb_stage<P>(himg, slabs, nslabs, r, T, chunk);      // (P's chunk is MX_KC: 16-bit elements)
-        __syncthreads();
-      }
-      if (!loaded) load_tile(w, e, tile, chunk);
-      loaded = false;
-      const char* hp = himg + tok * DEC_PITCH;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bool ok = chunk * MX_CHUNK_BLOCKS + bc + u < nblk;
-        const char* hk = hp + (ok ? bc + u : 0) * (MX_BLOCK * 2);
-        const typename F::template Cvt<EL> c(w[u], mx_scale<F>(e >> (8 * u)));
-        s16x8 hv[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) hv[q] = *reinterpret_cast<const s16x8*>(hk + 16 * q);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = EL::mfma16(c.operand(q), ok && tok_ok ? hv[q] : s16x8{}, acc);
-      }
-    }
-    if (wave > 0) red[parity][wave - 1][lane] = acc;
-    __syncthreads();
-    if (wave == 0) {
-      acc += red[parity][0][lane];
-      acc += red[parity][1][lane];
-      acc += red[parity][2][lane];
-      const int row0 = tile * 16 + 4 * (lane >> 4);
-      if (tok_ok) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int row = row0 + j;
-          if (row < n_o) y[(int64_t)tok * ldy + row] = P::from_f32(acc[j] + (bias ? P::to_f32(bias[row]) : 0.f));
-        }
-      }
-    }
-    parity ^= 1;
-  }
+  q_hb_body<MxDec<F, EL, NT, U>>(himg, red, T, m, n_o, y, ldy, OwnGrid{});
 }
 
 template <typename F, typename EL, bool NT>
@@ -197,9 +88,9 @@ int launch_mx(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq
                      kchunk);
   PTD_CHECK_LAUNCH(F::XA_LAUNCH);
   auto hb = mx_hb_blocks(r) == 2 ? decode_mx_hb_kernel<F, EL, NT, 2> : decode_mx_hb_kernel<F, EL, NT, 1>;
-  hipLaunchKernelGGL(hb, g2, blk, 0, st, slabs, nslabs, (int)T, (int)r, static_cast<const unsigned char*>(Bq), ldb,
-                     static_cast<const unsigned char*>(eb), ldsb, (int)n_o, static_cast<const unsigned short*>(bias),
-                     static_cast<unsigned short*>(y), ldy);
+  const MxSide side = {slabs, static_cast<const unsigned char*>(Bq), static_cast<const unsigned char*>(eb),
+                       static_cast<const unsigned short*>(bias), ldb, ldsb, nslabs, (int)r};
+  hipLaunchKernelGGL(hb, g2, blk, 0, st, (int)T, side, (int)n_o, static_cast<unsigned short*>(y), ldy);
   PTD_CHECK_LAUNCH(F::HB_LAUNCH);
   return PTD_OK;
 }

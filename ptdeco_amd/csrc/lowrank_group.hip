@@ -57,14 +57,6 @@ struct HbTable {
   int first[PTD_LOWRANK_GROUP_MAX];
 };
 
-// position of workgroup b among the members' grids (first[0] = 0)
-__device__ __forceinline__ int group_position(const int (&first)[PTD_LOWRANK_GROUP_MAX], const int b) {
-  int p = 0;
-#pragma unroll
-  for (int i = 1; i < PTD_LOWRANK_GROUP_MAX; ++i) p += b >= first[i];
-  return p;
-}
-
 template <typename P, bool NT>
 __global__ __launch_bounds__(DEC_THREADS) void group_xa_kernel(const typename P::elem* __restrict__ x, const int64_t ldx,
                                                                const int T, const int n_i, const XaTable tab) {
@@ -76,12 +68,6 @@ __global__ __launch_bounds__(DEC_THREADS) void group_xa_kernel(const typename P:
   decode_xa_body<P, NT>(x, ldx, T, n_i, static_cast<const elem*>(g.A), g.lda, g.r, g.slabs, g.kchunk, bx, by);
 }
 
-struct MemberGrid {
-  unsigned local, grid;
-  __device__ __forceinline__ unsigned tile0() const { return local; }
-  __device__ __forceinline__ unsigned stride() const { return grid; }
-};
-
 template <typename P, bool NT>
 __global__ __launch_bounds__(DEC_THREADS) void group_hb_kernel(const int T, const HbTable tab) {
   typedef typename P::elem elem;
@@ -90,12 +76,6 @@ __global__ __launch_bounds__(DEC_THREADS) void group_hb_kernel(const int T, cons
   const MemberGrid where = {(unsigned)(b - tab.first[p]), (unsigned)g.grid};
   decode_hb_body<P, NT>(g.slabs, g.nslabs, T, g.r, static_cast<const elem*>(g.B), g.ldb, g.n_o,
                         static_cast<const elem*>(g.bias), static_cast<elem*>(g.y), g.ldy, where);
-}
-
-// members by descending weight (stable: equal members keep the caller's order)
-void by_descending(const int64_t* weight, int count, int (&order)[PTD_LOWRANK_GROUP_MAX]) {
-  for (int i = 0; i < count; ++i) order[i] = i;
-  std::stable_sort(order, order + count, [&](int a, int b) { return weight[a] > weight[b]; });
 }
 
 template <typename P>

@@ -28,6 +28,8 @@ _lowrank_forward_gated = torch.ops.ptdeco_amd.lowrank_forward_gated.default
 _lowrank_forward_w8 = torch.ops.ptdeco_amd.lowrank_forward_w8.default
 _lowrank_forward_w4 = torch.ops.ptdeco_amd.lowrank_forward_w4.default
 _lowrank_forward_w6 = torch.ops.ptdeco_amd.lowrank_forward_w6.default
+_lowrank_forward_group_q = torch.ops.ptdeco_amd.lowrank_forward_group_q.default
+_lowrank_forward_gated_q = torch.ops.ptdeco_amd.lowrank_forward_gated_q.default
 
 logger = logging.getLogger(__name__)
 
@@ -148,6 +150,8 @@ class LowRankLinearW8(_QuantizedPair):
                 self._buffers[name] = old.to(new.device)
         return self
 
+    _q_fmt = "fp8"      # (the ``fmt`` of the grouped and gated operators)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         operands = (self.weight_a_q, self.scale_a, self.weight_b_q, self.scale_b, self.bias)
         wants_grad = torch.is_grad_enabled() and x.requires_grad
@@ -242,7 +246,7 @@ class LowRankLinearW4(_LowRankLinearMX):
     cast (``.half()``, ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the packed buffers
     as they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place``, or empty for ``load_state_dict``."""
 
-    _mx_name = "MXFP4"
+    _mx_name = _q_fmt = "MXFP4"
     _forward_op = staticmethod(_lowrank_forward_w4)
     _expression = staticmethod(_torch_ops.lowrank_w4_expression)
 
@@ -283,7 +287,7 @@ class LowRankLinearW6(_LowRankLinearMX):
     (``.half()``, ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the packed buffers as
     they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place`` with ``"mxfp6_e2m3"``, or empty for ``load_state_dict``."""
 
-    _mx_name = "MXFP6"
+    _mx_name = _q_fmt = "MXFP6"
     _forward_op = staticmethod(_lowrank_forward_w6)
     _expression = staticmethod(_torch_ops.lowrank_w6_expression)
 
@@ -460,15 +464,53 @@ def quantize_pairs_in_place(model: torch.nn.Module, fmt: str = "fp8_e4m3", names
     return done
 
 
-def lowrank_group(x: torch.Tensor, pairs) -> torch.Tensor:
+_QUANTIZED_MODES = ("members", "fused")
+
+
+def _fused_format(x: torch.Tensor, pairs, quantized: str):
+    """The ``fmt`` of the grouped / gated quantised operators when ``quantized="fused"`` applies to these members, else
+    None: all of ONE quantised class, equal in_features and activation dtype, x a ROCm tensor of that dtype, no
+    gradient wanted.  Any mode but "members" and "fused" raises."""
+    if quantized not in _QUANTIZED_MODES:
+        raise ValueError(f"quantized must be one of {_QUANTIZED_MODES}, got {quantized!r}")
+    if quantized != "fused" or not pairs:
+        return None
+    first = pairs[0]
+    if type(first) not in (LowRankLinearW8, LowRankLinearW4, LowRankLinearW6):
+        return None
+    if any(type(p) is not type(first) or p.in_features != first.in_features or p.dtype != first.dtype for p in pairs):
+        return None
+    if not x.is_cuda or x.dtype != first.dtype or (torch.is_grad_enabled() and x.requires_grad):
+        return None
+    return first._q_fmt
+
+
+def _q_operands(p):
+    return p.weight_a_q, p.scale_a, p.weight_b_q, p.scale_b, p.bias
+
+
+def lowrank_group(x: torch.Tensor, pairs, *, quantized: str = "members") -> torch.Tensor:
     """The outputs of installed ``LowRankLinear`` modules that read the same x, side by side: [..., sum out_features],
     member m in the columns after those of the members before it (``y.split([p[1].out_features for p in pairs], -1)``
     are the members' outputs).  For the q / k / v and gate / up projections of a decomposed transformer block: at decode
     shapes (1 to 16 tokens, up to four members) the group runs in two kernel launches instead of two per member, and
     every member's output is bit for bit what the member returns alone.  Inference only: when a gradient is wanted, or
     a member is not a ``LowRankLinear`` on the HIP kernels' tensors, this is ``torch.cat([p(x) for p in pairs], -1)``.
-    It keeps no state: the modules, their ``state_dict`` and the decompose config are untouched."""
+    It keeps no state: the modules, their ``state_dict`` and the decompose config are untouched.
+
+    ``quantized`` says what happens to quantised members (``LowRankLinearW8`` / ``W4`` / ``W6``).  "members", the
+    default: each runs as it does alone and the outputs are concatenated.  "fused": when all members are of ONE
+    quantised class with equal in_features and activation dtype, x is a ROCm tensor of that dtype and no gradient is
+    wanted, the group runs on ``torch.ops.ptdeco_amd.lowrank_forward_group_q`` -- at 1 to 16 tokens two launches for
+    the group, every member's columns bit for bit what the member returns alone; at other token counts each member as
+    it runs alone.  A mix of formats, or a quantised member beside a 16-bit one, is the "members" path.  16-bit members
+    ignore the keyword; any other value raises ``ValueError``."""
     pairs = list(pairs)
+    fmt = _fused_format(x, pairs, quantized)
+    if fmt is not None:
+        x2d = x.reshape(-1, pairs[0].in_features)
+        y = _lowrank_forward_group_q(x2d, *(list(t) for t in zip(*(_q_operands(p) for p in pairs))), fmt)
+        return y.reshape(*x.shape[:-1], y.shape[1])
     fused = len(pairs) > 0 and all(isinstance(p, LowRankLinear) and p[0].in_features == pairs[0][0].in_features
                                    for p in pairs)
     fused = fused and all(_use_hip(x, p[0].weight, "LowRankLinear") for p in pairs)
@@ -482,15 +524,29 @@ def lowrank_group(x: torch.Tensor, pairs) -> torch.Tensor:
     return y.reshape(*x.shape[:-1], y.shape[1])
 
 
-def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu") -> torch.Tensor:
+def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu", *, quantized: str = "members") -> torch.Tensor:
     """``act(gate(x)) * up(x)`` for the gate and up projections of a decomposed gated MLP (SwiGLU: "silu", GeGLU:
     "gelu_tanh", ReGLU: "relu"): [..., out_features].  For installed ``LowRankLinear`` modules with equal in_features and
     out_features at decode shapes (1 to 16 tokens) the whole expression runs in two kernel launches, at small batches
     (32 to 96 tokens, bf16) in three -- no [T, 2 n_ff] intermediate, no elementwise launch --, gate's and up's values
     bit for bit what the modules return alone, rounded where the expression rounds.  Inference only: when a gradient is wanted, or a member is not a ``LowRankLinear`` on
-    the HIP kernels' tensors, this is the expression itself.  It keeps no state."""
+    the HIP kernels' tensors, this is the expression itself.  It keeps no state.
+
+    ``quantized`` says what happens to quantised members (``LowRankLinearW8`` / ``W4`` / ``W6``).  "members", the
+    default: the expression itself on the modules' outputs.  "fused": when gate and up are of ONE quantised class with
+    equal in_features, out_features and activation dtype, x is a ROCm tensor of that dtype and no gradient is wanted,
+    ``torch.ops.ptdeco_amd.lowrank_forward_gated_q`` -- at 1 to 16 tokens two launches, the activation evaluated by the
+    kernel on gate's own bits: with "relu" the result is the expression's bit for bit, with "silu" and "gelu_tanh" it is
+    within the gated bound of it (the kernel's f32 activation against torch's, each rounded once), not its bits.  At
+    other token counts the members run as they do alone and torch applies the activation.  Anything else is the
+    "members" path; 16-bit members ignore the keyword; any other value raises ``ValueError``."""
     if act not in _torch_ops.GATE_ACTS:
         raise ValueError(f"act must be one of {sorted(_torch_ops.GATE_ACTS)}, got {act!r}")
+    fmt = _fused_format(x, [gate, up], quantized)
+    if fmt is not None and gate.out_features == up.out_features:
+        x2d = x.reshape(-1, gate.in_features)
+        y = _lowrank_forward_gated_q(x2d, *_q_operands(gate), *_q_operands(up), act, fmt)
+        return y.reshape(*x.shape[:-1], y.shape[1])
     fused = all(isinstance(p, LowRankLinear) for p in (gate, up))
     fused = fused and gate[0].in_features == up[0].in_features and gate[1].out_features == up[1].out_features
     fused = fused and all(_use_hip(x, p[0].weight, "LowRankLinear") for p in (gate, up))
@@ -504,10 +560,13 @@ def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu") -> torch.Tensor:
     return y.reshape(*x.shape[:-1], y.shape[1])
 
 
-def lowrank_mlp(x: torch.Tensor, gate, up, down, act: str = "silu") -> torch.Tensor:
+def lowrank_mlp(x: torch.Tensor, gate, up, down, act: str = "silu", *, quantized: str = "members") -> torch.Tensor:
     """``down(act(gate(x)) * up(x))``, the MLP of a decomposed Llama / Mistral / Qwen block: ``lowrank_gated`` and then
-    ``down`` as it is called alone -- at decode shapes four kernel launches in all, at 32 to 96 tokens six."""
-    return down(lowrank_gated(x, gate, up, act))
+    ``down`` as it is called alone -- at decode shapes four kernel launches in all, at 32 to 96 tokens six.
+    ``quantized`` is passed to ``lowrank_gated`` (with "fused", quantised gate and up of one format run in two
+    launches at decode shapes: bit for bit the module expression with "relu", within the gated bound of it with "silu"
+    and "gelu_tanh"); ``down`` runs as it does alone."""
+    return down(lowrank_gated(x, gate, up, act, quantized=quantized))
 
 
 def _is_plain_1x1(m: torch.nn.Module) -> bool:
