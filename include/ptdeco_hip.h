@@ -54,7 +54,9 @@ extern "C" {
                              *    ptd_lowrank_tile_w4_workspace_bytes, ptd_lowrank_tile_w4,
                              *    ptd_lowrank_tile_w6_workspace_bytes, ptd_lowrank_tile_w6,
                              *    ptd_lowrank_decode_group_q_workspace_bytes, ptd_lowrank_decode_group_q,
-                             *    ptd_lowrank_decode_gated_q_workspace_bytes, ptd_lowrank_decode_gated_q) */
+                             *    ptd_lowrank_decode_gated_q_workspace_bytes, ptd_lowrank_decode_gated_q,
+                             *    ptd_lowrank_skinny_group_q_workspace_bytes, ptd_lowrank_skinny_group_q,
+                             *    ptd_lowrank_skinny_gated_q_workspace_bytes, ptd_lowrank_skinny_gated_q) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -654,6 +656,54 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                              int64_t n_ff, int act, void* y, int64_t ldy,
                              void* ws, size_t ws_bytes, int dtype, void* stream);
 
+/* 1 <= count <= PTD_LOWRANK_GROUP_MAX pairs with quantised factors of ONE format that read the same x at small batches,
+ * 32 <= T <= the format's PTD_LOWRANK_SKINNY_W8_MAX_T / _W4_MAX_T / _W6_MAX_T (arguments of ptd_lowrank_decode_group_q;
+ * operands and semantics per member those of ptd_lowrank_skinny_w8 / _w4 / _w6), in THREE launches on the caller's stream
+ * instead of three per pair: every member's first product into its own f32 slabs (the members' grids laid end to end,
+ * the token tile in the grid's z), every member's slab sum into its own 16-bit h (fp8: with sa), every member's second
+ * product into its own y[m] with row pitch ldy[m].  Each member keeps the K split, the slab order, the wave quarters, the
+ * step order, the scale-byte variant and the rounding points of its format's skinny entry, so every y[m] holds the bits
+ * that entry gives for the member alone and row t of y depends on row t of x alone.  No floating-point atomics; one
+ * writer per output element.  The argument arrays are read before the call returns and not after it (the call may be
+ * captured in a graph).  Served when every member is served by the format's skinny entry with the common x, T, n_i and
+ * dtype (bf16 / f16); anything else, an unknown q_format and count outside 1 .. PTD_LOWRANK_GROUP_MAX included, returns
+ * PTD_ERR_UNSUPPORTED before a kernel is launched.  Null pointers (bias, or an entry of it, may be NULL), a leading
+ * dimension below its row length or a misaligned workspace PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  The
+ * workspace is the sum of the members' skinny workspaces of that format (each a multiple of 256 bytes: member m's region
+ * starts where member m - 1's ends).  No reference counterpart. */
+size_t ptd_lowrank_skinny_group_q_workspace_bytes(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r,
+                                                  int dtype);
+int ptd_lowrank_skinny_group_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, int count,
+                               const void* const* Aq, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                               const int64_t* r,
+                               const void* const* Bq, const int64_t* ldb, const void* const* sb, const int64_t* ldsb,
+                               const int64_t* n_o,
+                               const void* const* bias /* entries may be NULL; the array may be NULL */,
+                               void* const* y, const int64_t* ldy,
+                               void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* The gated pair of a quantised, decomposed MLP at the same token counts, y = act(gate(x)) * up(x) (arguments of
+ * ptd_lowrank_decode_gated_q), in THREE launches on the caller's stream: the first two launches of
+ * ptd_lowrank_skinny_group_q on (gate, up), then a kernel in which a workgroup forms both second products for the same
+ * 32 rows and 64 tokens -- gate's loop and its wave sums, then up's -- and applies the activation and the product in the
+ * lanes that hold both sums: no [T, 2 n_ff] intermediate and no elementwise launch.  With D the dtype:
+ * g = round_D(sb_g * acc_g + bias_g) (MX: no sb factor) and u likewise are the bits the format's skinny entry stores for
+ * gate and up, and y = round_D(round_D(act(g)) * u), act as in ptd_lowrank_decode_gated.  Served when both members are
+ * served by the format's skinny entry with the common x, T, n_i, n_ff and dtype and act is one of PTD_ACT_*; anything
+ * else, an unknown q_format included, returns PTD_ERR_UNSUPPORTED before a kernel is launched.  Null pointers (either
+ * bias may be NULL), a leading dimension below its row length or a misaligned workspace PTD_ERR_INVALID; a short
+ * workspace PTD_ERR_WORKSPACE.  The workspace is the sum of the two members' skinny workspaces of that format.  No
+ * reference counterpart. */
+size_t ptd_lowrank_skinny_gated_q_workspace_bytes(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u,
+                                                  int dtype);
+int ptd_lowrank_skinny_gated_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                               const void* Aq_g, int64_t lda_g, const void* sa_g, int64_t ldsa_g, int64_t r_g,
+                               const void* Bq_g, int64_t ldb_g, const void* sb_g, int64_t ldsb_g, const void* bias_g,
+                               const void* Aq_u, int64_t lda_u, const void* sa_u, int64_t ldsa_u, int64_t r_u,
+                               const void* Bq_u, int64_t ldb_u, const void* sb_u, int64_t ldsb_u, const void* bias_u,
+                               int64_t n_ff, int act, void* y, int64_t ldy,
+                               void* ws, size_t ws_bytes, int dtype, void* stream);
+
 /* Host query for tests and tools: the numbers a launch of one serving family of the pair would use for (T, n_i, r, n_o,
  * dtype) with contiguous, aligned operands -- computed by the functions the launchers and kernels themselves call, so a
  * test can prove which branch combination a shape reaches.  family: PTD_PLAN_DECODE (ptd_lowrank_decode; every member
@@ -665,7 +715,9 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
  * the scale bytes of one load, 1 or 2; the tail fields: blocks of a row % that -- non-zero: the last block's scale byte
  * comes out of the clamped, shifted load), PTD_PLAN_DECODE_W6 (ptd_lowrank_decode_w6: every field with the meaning
  * PTD_PLAN_DECODE_W4 gives it, "MXFP4" below read as "MXFP4 and MXFP6"), PTD_PLAN_SKINNY_W6 (ptd_lowrank_skinny_w6: every
- * field with the meaning PTD_PLAN_SKINNY_W4 gives it -- the two share one kernel template).  Writes out[PTD_PLAN_*] for the
+ * field with the meaning PTD_PLAN_SKINNY_W4 gives it -- the two share one kernel template; every member of
+ * ptd_lowrank_skinny_group_q and both members of ptd_lowrank_skinny_gated_q take the plan of PTD_PLAN_SKINNY_W8 / _W4 /
+ * _W6 for that member alone, xa_u and hb_u included).  Writes out[PTD_PLAN_*] for the
  * PTD_PLAN_LEN indices below and returns PTD_PLAN_LEN; PTD_ERR_UNSUPPORTED where the family does not serve the shape or
  * the family is unknown, PTD_ERR_INVALID for a null `out` or cap < PTD_PLAN_LEN.  "First product" is x A^T into K slabs,
  * "second" h B^T.  A wave's "load step" is the k its 64 lanes cover with one 16-byte load each (32 for bf16 / f16, 16 for

@@ -109,6 +109,18 @@ SIGNATURES = {
                                            c_void_p, c_int64, c_void_p, c_int64, c_int64,
                                            c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                            c_int64, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]),
+    "ptd_lowrank_skinny_group_q_workspace_bytes": (c_size_t, [c_int, c_int, c_int64, c_int64, c_void_p, c_int]),
+    "ptd_lowrank_skinny_group_q": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ptd_lowrank_skinny_gated_q_workspace_bytes": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64, c_int]),
+    "ptd_lowrank_skinny_gated_q": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                           c_int64, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]),
     "ptd_lowrank_skinny_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
     "ptd_lowrank_skinny": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
                                    c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int,

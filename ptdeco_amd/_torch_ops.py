@@ -380,12 +380,15 @@ def lowrank_forward_group_q(x2d: torch.Tensor, Aqs: List[torch.Tensor], sas: Lis
     """Quantised pairs of one format ``fmt`` ("fp8", "MXFP4", "MXFP6") that share x2d [T, n_i], side by side: y
     [T, sum n_o] contiguous, member m = (Aqs[m], sas[m], Bqs[m], sbs[m], biases[m]) -- the operands of lowrank_forward_w8 /
     _w4 / _w6 -- in columns [off_m, off_m + n_o_m).  At decode shapes two launches for the group
-    (ops.lowrank_decode_group_q_serves: ptd_lowrank_decode_group_q, every member's bits those of its own decode entry);
-    otherwise each member as its own operator runs it.  Inference only: no autograd formula."""
+    (ops.lowrank_decode_group_q_serves: ptd_lowrank_decode_group_q, every member's bits those of its own decode entry),
+    at 32 to 96 tokens three (ops.lowrank_skinny_group_q_serves: ptd_lowrank_skinny_group_q, the bits of its own skinny
+    entry); otherwise each member as its own operator runs it.  Inference only: no autograd formula."""
     if fmt not in _Q_MEMBER:
         raise ValueError(f"fmt must be one of {sorted(_Q_MEMBER)}, got {fmt!r}")
     if ops.lowrank_decode_group_q_serves(fmt, x2d, Aqs, sas, Bqs, sbs, biases):
         return ops.lowrank_decode_group_q(fmt, x2d, Aqs, sas, Bqs, sbs, biases)
+    if ops.lowrank_skinny_group_q_serves(fmt, x2d, Aqs, sas, Bqs, sbs, biases):
+        return ops.lowrank_skinny_group_q(fmt, x2d, Aqs, sas, Bqs, sbs, biases)
     y = x2d.new_empty((x2d.shape[0], sum(Bq.shape[0] for Bq in Bqs)))
     off = 0
     for w in zip(Aqs, sas, Bqs, sbs, biases):
@@ -415,7 +418,8 @@ def lowrank_forward_gated_q(x2d: torch.Tensor, Aq_g: torch.Tensor, s_a_g: torch.
     """act(g) * u for the quantised gate pair and the quantised up pair of one format ``fmt`` on x2d [T, n_i] (operands
     per member as in lowrank_forward_group_q), act "silu", "gelu_tanh" or "relu": y [T, n_ff] contiguous.  At decode
     shapes two launches (ops.lowrank_decode_gated_q_serves: ptd_lowrank_decode_gated_q; g and u are the members' own
-    bits, the activation is the kernel's); otherwise g and u as each member's own operator forms them and torch's own
+    bits, the activation is the kernel's), at 32 to 96 tokens three (ops.lowrank_skinny_gated_q_serves:
+    ptd_lowrank_skinny_gated_q, likewise); otherwise g and u as each member's own operator forms them and torch's own
     activation and product.  Inference only: no autograd formula."""
     if fmt not in _Q_MEMBER:
         raise ValueError(f"fmt must be one of {sorted(_Q_MEMBER)}, got {fmt!r}")
@@ -424,6 +428,8 @@ def lowrank_forward_gated_q(x2d: torch.Tensor, Aq_g: torch.Tensor, s_a_g: torch.
     gate, up = (Aq_g, s_a_g, Bq_g, s_b_g, bias_g), (Aq_u, s_a_u, Bq_u, s_b_u, bias_u)
     if ops.lowrank_decode_gated_q_serves(fmt, x2d, *gate, *up, act):
         return ops.lowrank_decode_gated_q(fmt, x2d, *gate, *up, act)
+    if ops.lowrank_skinny_gated_q_serves(fmt, x2d, *gate, *up, act):
+        return ops.lowrank_skinny_gated_q(fmt, x2d, *gate, *up, act)
     g, u = _q_member(fmt, x2d, *gate), _q_member(fmt, x2d, *up)
     return (GATE_ACTS[act](g) * u).contiguous()
 

@@ -682,6 +682,86 @@ static bool q_member_pitches(int q_format, int64_t n_i, int64_t r, int64_t n_o, 
   return q_format == PTD_Q_FP8_E4M3 || (ldsa >= n_i / 32 && ldsb >= r / 32);
 }
 
+// What precedes the launches of a quantised group entry `name` (ptd_lowrank_<regime>_group_q), in the order it is
+// reported: null pointers, the format and the member count, leading dimensions, the workspace's alignment, what the
+// kernels serve (`serves`: the entry's *_serves) and the workspace's size (`workspace`: the entry's *_workspace_bytes)
+typedef bool (*q_group_serves_fn)(int, int, int64_t, int64_t, const int64_t*, const int64_t*, int, const void*, int64_t,
+                                  const void* const*, const int64_t*, const void* const*, const void* const*,
+                                  const int64_t*, const void* const*, const void* const*);
+typedef size_t (*q_group_workspace_fn)(int, int, int64_t, int64_t, const int64_t*, int);
+static int q_group_entry_checks(const char* name, const char* regime, q_group_serves_fn serves,
+                                q_group_workspace_fn workspace, int q_format, const void* x, int64_t ldx, int64_t T,
+                                int64_t n_i, int count, const void* const* Aq, const int64_t* lda, const void* const* sa,
+                                const int64_t* ldsa, const int64_t* r, const void* const* Bq, const int64_t* ldb,
+                                const void* const* sb, const int64_t* ldsb, const int64_t* n_o, const void* const* bias,
+                                void* const* y, const int64_t* ldy, const void* ws, size_t ws_bytes, int dtype) {
+  PTD_REQUIRE(x && Aq && lda && sa && r && Bq && ldb && sb && n_o && y && ldy && ws, "%s: null pointer", name);
+  if (q_code_bytes(q_format, 0) < 0 || count < 1 || count > PTD_LOWRANK_GROUP_MAX) {
+    set_error("%s: not served (q_format=%d count=%d: PTD_Q_FP8_E4M3, PTD_Q_MXFP4 or PTD_Q_MXFP6_E2M3, 1 <= count <= %d)",
+              name, q_format, count, PTD_LOWRANK_GROUP_MAX);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  const bool mx = q_format != PTD_Q_FP8_E4M3;
+  PTD_REQUIRE(!mx || (ldsa && ldsb), "%s: null pointer", name);
+  PTD_REQUIRE(ldx >= n_i, "%s: bad leading dimension", name);
+  for (int m = 0; m < count; ++m) {
+    PTD_REQUIRE(Aq[m] && sa[m] && Bq[m] && sb[m] && y[m], "%s: null pointer (member %d)", name, m);
+    PTD_REQUIRE(q_member_pitches(q_format, n_i, r[m], n_o[m], lda[m], mx ? ldsa[m] : 0, ldb[m], mx ? ldsb[m] : 0, ldy[m]),
+                "%s: bad leading dimension (member %d)", name, m);
+  }
+  PTD_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", name);
+  // (nothing is launched for a group the kernels do not serve: the caller runs the members one by one)
+  if (!serves(q_format, count, T, n_i, r, n_o, dtype, x, ldx, Aq, lda, sa, Bq, ldb, sb, bias)) {
+    set_error("%s: not served (q_format=%d count=%d T=%lld n_i=%lld dtype=%d: every member as the format's %s entry "
+              "serves it)", name, q_format, count, (long long)T, (long long)n_i, dtype, regime);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  const size_t need = workspace(q_format, count, T, n_i, r, dtype);
+  if (ws_bytes < need) {
+    set_error("%s: workspace %zu < required %zu bytes", name, ws_bytes, need);
+    return PTD_ERR_WORKSPACE;
+  }
+  return PTD_OK;
+}
+
+// The same for a quantised gated entry `name` (ptd_lowrank_<regime>_gated_q)
+typedef bool (*q_gated_serves_fn)(int, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, const void*, int64_t,
+                                  const void*, int64_t, const void*, const void*, int64_t, const void*, const void*,
+                                  const void*, int64_t, const void*, const void*, int64_t, const void*, const void*);
+typedef size_t (*q_gated_workspace_fn)(int, int64_t, int64_t, int64_t, int64_t, int);
+static int q_gated_entry_checks(const char* name, const char* regime, q_gated_serves_fn serves,
+                                q_gated_workspace_fn workspace, int q_format, const void* x, int64_t ldx, int64_t T,
+                                int64_t n_i, const void* Aq_g, int64_t lda_g, const void* sa_g, int64_t ldsa_g, int64_t r_g,
+                                const void* Bq_g, int64_t ldb_g, const void* sb_g, int64_t ldsb_g, const void* bias_g,
+                                const void* Aq_u, int64_t lda_u, const void* sa_u, int64_t ldsa_u, int64_t r_u,
+                                const void* Bq_u, int64_t ldb_u, const void* sb_u, int64_t ldsb_u, const void* bias_u,
+                                int64_t n_ff, int act, const void* y, int64_t ldy, const void* ws, size_t ws_bytes,
+                                int dtype) {
+  PTD_REQUIRE(x && Aq_g && sa_g && Bq_g && sb_g && Aq_u && sa_u && Bq_u && sb_u && y && ws, "%s: null pointer", name);
+  if (q_code_bytes(q_format, 0) < 0) {
+    set_error("%s: not served (q_format=%d: PTD_Q_FP8_E4M3, PTD_Q_MXFP4 or PTD_Q_MXFP6_E2M3)", name, q_format);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  PTD_REQUIRE(ldx >= n_i && q_member_pitches(q_format, n_i, r_g, n_ff, lda_g, ldsa_g, ldb_g, ldsb_g, ldy) &&
+                  q_member_pitches(q_format, n_i, r_u, n_ff, lda_u, ldsa_u, ldb_u, ldsb_u, ldy),
+              "%s: bad leading dimension", name);
+  PTD_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", name);
+  // (nothing is launched for what the kernels do not serve: the caller forms g and u and applies the activation itself)
+  if (!serves(q_format, T, n_i, r_g, r_u, n_ff, act, dtype, x, ldx, Aq_g, lda_g, sa_g, Bq_g, ldb_g, sb_g, bias_g, Aq_u,
+              lda_u, sa_u, Bq_u, ldb_u, sb_u, bias_u)) {
+    set_error("%s: not served (q_format=%d T=%lld n_i=%lld r_g=%lld r_u=%lld n_ff=%lld act=%d dtype=%d: both members as "
+              "the format's %s entry serves them, act 0 (silu), 1 (gelu_tanh) or 2 (relu))", name, q_format, (long long)T,
+              (long long)n_i, (long long)r_g, (long long)r_u, (long long)n_ff, act, dtype, regime);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  const size_t need = workspace(q_format, T, n_i, r_g, r_u, dtype);
+  if (ws_bytes < need) {
+    set_error("%s: workspace %zu < required %zu bytes", name, ws_bytes, need);
+    return PTD_ERR_WORKSPACE;
+  }
+  return PTD_OK;
+}
+
 size_t ptd_lowrank_decode_group_q_workspace_bytes(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r,
                                                   int dtype) {
   if (!r || count < 1 || count > PTD_LOWRANK_GROUP_MAX) return 0;
@@ -693,33 +773,11 @@ int ptd_lowrank_decode_group_q(int q_format, const void* x, int64_t ldx, int64_t
                                const int64_t* r, const void* const* Bq, const int64_t* ldb, const void* const* sb,
                                const int64_t* ldsb, const int64_t* n_o, const void* const* bias, void* const* y,
                                const int64_t* ldy, void* ws, size_t ws_bytes, int dtype, void* stream) {
-  PTD_REQUIRE(x && Aq && lda && sa && r && Bq && ldb && sb && n_o && y && ldy && ws,
-              "ptd_lowrank_decode_group_q: null pointer");
-  if (q_code_bytes(q_format, 0) < 0 || count < 1 || count > PTD_LOWRANK_GROUP_MAX) {
-    set_error("ptd_lowrank_decode_group_q: not served (q_format=%d count=%d: PTD_Q_FP8_E4M3, PTD_Q_MXFP4 or "
-              "PTD_Q_MXFP6_E2M3, 1 <= count <= %d)", q_format, count, PTD_LOWRANK_GROUP_MAX);
-    return PTD_ERR_UNSUPPORTED;
-  }
+  const int rc = q_group_entry_checks("ptd_lowrank_decode_group_q", "decode", lowrank_decode_group_q_serves,
+                                      lowrank_decode_group_q_workspace_bytes, q_format, x, ldx, T, n_i, count, Aq, lda, sa,
+                                      ldsa, r, Bq, ldb, sb, ldsb, n_o, bias, y, ldy, ws, ws_bytes, dtype);
+  if (rc != PTD_OK) return rc;
   const bool mx = q_format != PTD_Q_FP8_E4M3;
-  PTD_REQUIRE(!mx || (ldsa && ldsb), "ptd_lowrank_decode_group_q: null pointer");
-  PTD_REQUIRE(ldx >= n_i, "ptd_lowrank_decode_group_q: bad leading dimension");
-  for (int m = 0; m < count; ++m) {
-    PTD_REQUIRE(Aq[m] && sa[m] && Bq[m] && sb[m] && y[m], "ptd_lowrank_decode_group_q: null pointer (member %d)", m);
-    PTD_REQUIRE(q_member_pitches(q_format, n_i, r[m], n_o[m], lda[m], mx ? ldsa[m] : 0, ldb[m], mx ? ldsb[m] : 0, ldy[m]),
-                "ptd_lowrank_decode_group_q: bad leading dimension (member %d)", m);
-  }
-  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_decode_group_q: the workspace must be 16-byte aligned");
-  // (nothing is launched for a group the kernels do not serve: the caller runs the members one by one)
-  if (!lowrank_decode_group_q_serves(q_format, count, T, n_i, r, n_o, dtype, x, ldx, Aq, lda, sa, Bq, ldb, sb, bias)) {
-    set_error("ptd_lowrank_decode_group_q: not served (q_format=%d count=%d T=%lld n_i=%lld dtype=%d: every member as "
-              "the format's decode entry serves it)", q_format, count, (long long)T, (long long)n_i, dtype);
-    return PTD_ERR_UNSUPPORTED;
-  }
-  const size_t need = lowrank_decode_group_q_workspace_bytes(q_format, count, T, n_i, r, dtype);
-  if (ws_bytes < need) {
-    set_error("ptd_lowrank_decode_group_q: workspace %zu < required %zu bytes", ws_bytes, need);
-    return PTD_ERR_WORKSPACE;
-  }
   return lowrank_decode_group_q(q_format, x, ldx, T, n_i, count, Aq, lda, sa, mx ? ldsa : nullptr, r, Bq, ldb, sb,
                                 mx ? ldsb : nullptr, n_o, bias, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
 }
@@ -735,31 +793,53 @@ int ptd_lowrank_decode_gated_q(int q_format, const void* x, int64_t ldx, int64_t
                                int64_t lda_u, const void* sa_u, int64_t ldsa_u, int64_t r_u, const void* Bq_u,
                                int64_t ldb_u, const void* sb_u, int64_t ldsb_u, const void* bias_u, int64_t n_ff, int act,
                                void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, void* stream) {
-  PTD_REQUIRE(x && Aq_g && sa_g && Bq_g && sb_g && Aq_u && sa_u && Bq_u && sb_u && y && ws,
-              "ptd_lowrank_decode_gated_q: null pointer");
-  if (q_code_bytes(q_format, 0) < 0) {
-    set_error("ptd_lowrank_decode_gated_q: not served (q_format=%d: PTD_Q_FP8_E4M3, PTD_Q_MXFP4 or PTD_Q_MXFP6_E2M3)",
-              q_format);
-    return PTD_ERR_UNSUPPORTED;
-  }
-  PTD_REQUIRE(ldx >= n_i && q_member_pitches(q_format, n_i, r_g, n_ff, lda_g, ldsa_g, ldb_g, ldsb_g, ldy) &&
-                  q_member_pitches(q_format, n_i, r_u, n_ff, lda_u, ldsa_u, ldb_u, ldsb_u, ldy),
-              "ptd_lowrank_decode_gated_q: bad leading dimension");
-  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_decode_gated_q: the workspace must be 16-byte aligned");
-  // (nothing is launched for what the kernels do not serve: the caller forms g and u and applies the activation itself)
-  if (!lowrank_decode_gated_q_serves(q_format, T, n_i, r_g, r_u, n_ff, act, dtype, x, ldx, Aq_g, lda_g, sa_g, Bq_g, ldb_g,
-                                     sb_g, bias_g, Aq_u, lda_u, sa_u, Bq_u, ldb_u, sb_u, bias_u)) {
-    set_error("ptd_lowrank_decode_gated_q: not served (q_format=%d T=%lld n_i=%lld r_g=%lld r_u=%lld n_ff=%lld act=%d "
-              "dtype=%d: both members as the format's decode entry serves them, act 0 (silu), 1 (gelu_tanh) or 2 (relu))",
-              q_format, (long long)T, (long long)n_i, (long long)r_g, (long long)r_u, (long long)n_ff, act, dtype);
-    return PTD_ERR_UNSUPPORTED;
-  }
-  const size_t need = lowrank_decode_gated_q_workspace_bytes(q_format, T, n_i, r_g, r_u, dtype);
-  if (ws_bytes < need) {
-    set_error("ptd_lowrank_decode_gated_q: workspace %zu < required %zu bytes", ws_bytes, need);
-    return PTD_ERR_WORKSPACE;
-  }
+  const int rc = q_gated_entry_checks("ptd_lowrank_decode_gated_q", "decode", lowrank_decode_gated_q_serves,
+                                      lowrank_decode_gated_q_workspace_bytes, q_format, x, ldx, T, n_i, Aq_g, lda_g, sa_g,
+                                      ldsa_g, r_g, Bq_g, ldb_g, sb_g, ldsb_g, bias_g, Aq_u, lda_u, sa_u, ldsa_u, r_u, Bq_u,
+                                      ldb_u, sb_u, ldsb_u, bias_u, n_ff, act, y, ldy, ws, ws_bytes, dtype);
+  if (rc != PTD_OK) return rc;
   return lowrank_decode_gated_q(q_format, x, ldx, T, n_i, Aq_g, lda_g, sa_g, ldsa_g, r_g, Bq_g, ldb_g, sb_g, ldsb_g, bias_g,
+                                Aq_u, lda_u, sa_u, ldsa_u, r_u, Bq_u, ldb_u, sb_u, ldsb_u, bias_u, n_ff, act, y, ldy, ws,
+                                dtype, static_cast<hipStream_t>(stream));
+}
+
+size_t ptd_lowrank_skinny_group_q_workspace_bytes(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r,
+                                                  int dtype) {
+  if (!r || count < 1 || count > PTD_LOWRANK_GROUP_MAX) return 0;
+  return lowrank_skinny_group_q_workspace_bytes(q_format, count, T, n_i, r, dtype);
+}
+
+int ptd_lowrank_skinny_group_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, int count,
+                               const void* const* Aq, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                               const int64_t* r, const void* const* Bq, const int64_t* ldb, const void* const* sb,
+                               const int64_t* ldsb, const int64_t* n_o, const void* const* bias, void* const* y,
+                               const int64_t* ldy, void* ws, size_t ws_bytes, int dtype, void* stream) {
+  const int rc = q_group_entry_checks("ptd_lowrank_skinny_group_q", "skinny", lowrank_skinny_group_q_serves,
+                                      lowrank_skinny_group_q_workspace_bytes, q_format, x, ldx, T, n_i, count, Aq, lda, sa,
+                                      ldsa, r, Bq, ldb, sb, ldsb, n_o, bias, y, ldy, ws, ws_bytes, dtype);
+  if (rc != PTD_OK) return rc;
+  const bool mx = q_format != PTD_Q_FP8_E4M3;
+  return lowrank_skinny_group_q(q_format, x, ldx, T, n_i, count, Aq, lda, sa, mx ? ldsa : nullptr, r, Bq, ldb, sb,
+                                mx ? ldsb : nullptr, n_o, bias, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
+}
+
+size_t ptd_lowrank_skinny_gated_q_workspace_bytes(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u,
+                                                  int dtype) {
+  return lowrank_skinny_gated_q_workspace_bytes(q_format, T, n_i, r_g, r_u, dtype);
+}
+
+int ptd_lowrank_skinny_gated_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq_g,
+                               int64_t lda_g, const void* sa_g, int64_t ldsa_g, int64_t r_g, const void* Bq_g,
+                               int64_t ldb_g, const void* sb_g, int64_t ldsb_g, const void* bias_g, const void* Aq_u,
+                               int64_t lda_u, const void* sa_u, int64_t ldsa_u, int64_t r_u, const void* Bq_u,
+                               int64_t ldb_u, const void* sb_u, int64_t ldsb_u, const void* bias_u, int64_t n_ff, int act,
+                               void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, void* stream) {
+  const int rc = q_gated_entry_checks("ptd_lowrank_skinny_gated_q", "skinny", lowrank_skinny_gated_q_serves,
+                                      lowrank_skinny_gated_q_workspace_bytes, q_format, x, ldx, T, n_i, Aq_g, lda_g, sa_g,
+                                      ldsa_g, r_g, Bq_g, ldb_g, sb_g, ldsb_g, bias_g, Aq_u, lda_u, sa_u, ldsa_u, r_u, Bq_u,
+                                      ldb_u, sb_u, ldsb_u, bias_u, n_ff, act, y, ldy, ws, ws_bytes, dtype);
+  if (rc != PTD_OK) return rc;
+  return lowrank_skinny_gated_q(q_format, x, ldx, T, n_i, Aq_g, lda_g, sa_g, ldsa_g, r_g, Bq_g, ldb_g, sb_g, ldsb_g, bias_g,
                                 Aq_u, lda_u, sa_u, ldsa_u, r_u, Bq_u, ldb_u, sb_u, ldsb_u, bias_u, n_ff, act, y, ldy, ws,
                                 dtype, static_cast<hipStream_t>(stream));
 }

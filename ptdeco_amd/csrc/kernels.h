@@ -201,6 +201,47 @@ int lowrank_skinny_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const 
                       int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
                       const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_skinny_group_q.hip: the rule, the workspace and nothing else of the skinny entry of format q_format (PTD_Q_*) --
+// those of lowrank_skinny_w8 / _w4 / _w6; sa and sb are f32 row scales (fp8) or e8m0 scale rows (MX).  False / 0 for an
+// unknown format
+bool lowrank_skinny_q_serves(int q_format, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, const void* x,
+                             int64_t ldx, const void* Aq, int64_t lda, const void* sa, const void* Bq, int64_t ldb,
+                             const void* sb, const void* bias);
+size_t lowrank_skinny_q_workspace_bytes(int q_format, int64_t T, int64_t n_i, int64_t r, int dtype);
+
+// lowrank_skinny_group_q.hip: 1 .. PTD_LOWRANK_GROUP_MAX pairs with factors of one quantised format on one input at
+// 32 <= T <= the format's skinny cap in three launches (ptd_lowrank_skinny_group_q); every member's bits are those of its
+// format's skinny entry on that member alone.  lowrank_skinny_group_q_first: the first two launches (first products, slab
+// sums) under the caller's labels (string literals), which lowrank_skinny_gated_q.hip shares (GroupQXa: ldsa null for fp8)
+bool lowrank_skinny_group_q_serves(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r, const int64_t* n_o,
+                                   int dtype, const void* x, int64_t ldx, const void* const* Aq, const int64_t* lda,
+                                   const void* const* sa, const void* const* Bq, const int64_t* ldb, const void* const* sb,
+                                   const void* const* bias);
+size_t lowrank_skinny_group_q_workspace_bytes(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r, int dtype);
+int lowrank_skinny_group_q_first(int q_format, const GroupQXa& a, int dtype, const char* xa_label, const char* sum_label,
+                                 hipStream_t st);
+int lowrank_skinny_group_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, int count,
+                           const void* const* Aq, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                           const int64_t* r, const void* const* Bq, const int64_t* ldb, const void* const* sb,
+                           const int64_t* ldsb, const int64_t* n_o, const void* const* bias, void* const* y,
+                           const int64_t* ldy, void* ws, int dtype, hipStream_t st);
+
+// lowrank_skinny_gated_q.hip: act(gate x) * up x for two pairs with factors of one quantised format at 32 <= T <= the
+// format's skinny cap in three launches (ptd_lowrank_skinny_gated_q); g and u are the bits of the format's skinny entry,
+// rounded where act(g) * u rounds
+bool lowrank_skinny_gated_q_serves(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int64_t n_o, int act,
+                                   int dtype, const void* x, int64_t ldx, const void* Ag, int64_t lda_g, const void* sa_g,
+                                   const void* Bg, int64_t ldb_g, const void* sb_g, const void* bias_g, const void* Au,
+                                   int64_t lda_u, const void* sa_u, const void* Bu, int64_t ldb_u, const void* sb_u,
+                                   const void* bias_u);
+size_t lowrank_skinny_gated_q_workspace_bytes(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype);
+int lowrank_skinny_gated_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Ag, int64_t lda_g,
+                           const void* sa_g, int64_t ldsa_g, int64_t r_g, const void* Bg, int64_t ldb_g, const void* sb_g,
+                           int64_t ldsb_g, const void* bias_g, const void* Au, int64_t lda_u, const void* sa_u,
+                           int64_t ldsa_u, int64_t r_u, const void* Bu, int64_t ldb_u, const void* sb_u, int64_t ldsb_u,
+                           const void* bias_u, int64_t n_o, int act, void* y, int64_t ldy, void* ws, int dtype,
+                           hipStream_t st);
+
 // lowrank_dequant_mx.hip: an MX factor (MXFP4 / MXFP6 codes and e8m0 block scales) written out as its exact 16-bit
 // values, one block per lane (ptd_lowrank_dequant_w4 / _w6), and both factors of a pair in one launch into the workspace
 // of ptd_lowrank_tile_w4 / _w6: A^ [r, n_i] at ws, B^ [n_o, r] lowrank_tile_mx_factor_bytes(r, n_i) behind it, both

@@ -3,12 +3,13 @@
 // per factor row; the semantics of lowrank_decode_w8.hip) and the two OCP MX formats of lowrank_decode_mx.hip, MXFP4
 // (packed e2m1 codes) and MXFP6 (e2m3, packed six-bit codes), one e8m0 scale byte per 32 consecutive weights of a row.
 // ONE kernel body over a skinny format trait (the bytes of a lane's piece, its load and its conversion to the two MFMA
-// operands, the odd lane groups' swap included, where its scales live and what its entry serves: SkFp8 in
-// lowrank_skinny_w8.hip, SkMxFp4 in lowrank_skinny_w4.hip, SkMxFp6 in lowrank_skinny_w6.hip); the slab sum, the
-// launcher, the serving rule and the workspace rule are shared.  The formats stay separate translation units, so a
-// format's device code can be compiled and inspected on its own and its kernels carry the format in their names: the
-// including file names the two kernel templates before it includes this one (SKINNY_Q_PRODUCT_KERNEL,
-// SKINNY_Q_COMBINE_KERNEL) and supplies the trait and the C++ entry after it.
+// operands, the odd lane groups' swap included, where its scales live and what its entry serves: SkFp8, SkMxFp4 and
+// SkMxFp6 of lowrank_skinny_q_body.h, which holds the body as __device__ functions of explicit block coordinates -- the
+// kernels here are callers of it, and so are the grouped and gated kernels of lowrank_skinny_group_q.hip and
+// lowrank_skinny_gated_q.hip); the slab sum, the launcher, the serving rule and the workspace rule are shared.  The
+// formats stay separate translation units, so a format's device code can be compiled and inspected on its own and its
+// kernels carry the format in their names: the including file names the two kernel templates before it includes this
+// one (SKINNY_Q_PRODUCT_KERNEL, SKINNY_Q_COMBINE_KERNEL) and supplies the C++ entry after it.
 //
 //   MX:  W^[i, k]                  = val(code(W, i, k)) * 2^(clamp(e[i, k >> 5], F::E_MIN, 140) - 127);   s = 1
 //   fp8: W^[i, k]                  = val(code(W, i, k));                                                   s = the row scales
@@ -66,45 +67,18 @@
 #error "name the kernels (SKINNY_Q_PRODUCT_KERNEL, SKINNY_Q_COMBINE_KERNEL) before including lowrank_skinny_q.h"
 #endif
 
-#include "common.h"
-#include "elem16.h"
-#include "kernels.h"
-#include "lowrank_mx.h"
-#include "lowrank_skinny.h"
+#include "lowrank_skinny_q_body.h"
 
 namespace ptd {
 
 namespace {
 
-static_assert(SK_KW == 2 * MX_BLOCK, "a wave's step is two MX blocks: a lane's piece is half a block");
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-
-// What the two MX formats share as skinny formats: block scales in a byte matrix of their own, no row scales, rows of
-// whole blocks on 8-byte aligned code rows
-struct SkMx {
-  static constexpr bool BLOCK_SCALES = true, ROW_SCALES = false;
-  static constexpr int K_QUANTUM = MX_BLOCK;      // the minimum and the multiple of n_i and r
-  static constexpr int CODE_ALIGN = 8;            // of a factor's first code row and of its row pitch
-  static constexpr int SCALE_ALIGN = 1;           // of a scale array
-  static int scale_bytes(int64_t k_total) { return mx_sk_scale_bytes(k_total); }
-  static __device__ __forceinline__ float row_scale(const unsigned char*, int64_t, int) { return 1.f; }
-};
-
-// the scale operand of F's conversion for the step's scale bits e (1.0 where the format has no block scales)
-template <typename F>
-__device__ __forceinline__ float sk_block_scale(unsigned e) {
-  if constexpr (F::BLOCK_SCALES) return mx_scale<F>(e);
-  return 1.f;
-}
-
-// out[t, i] over the K range of blockIdx.y for rows 32 blockIdx.x + 0..31 and tokens 64 blockIdx.z + 0..63; W [R, K]
-// code bytes of format F with row pitch ldw; E the format's scales: [R, K / 32] scale bytes with row pitch ldse, U
-// scale bytes per load (F::scale_bytes), or what F::row_scale reads row i's scale from.  SLAB: f32 sums to
-// out_f32[(blockIdx.y T + t) R + i]; otherwise round(sum scale[i] + bias[i]) to y[t ldy + i].
+// out[t, i] over the K range of blockIdx.y for rows 32 blockIdx.x + 0..31 and tokens 64 blockIdx.z + 0..63: skq_product
+// of lowrank_skinny_q_body.h with the launch's own coordinates
+// (compiled for F::WAVES waves per SIMD: left to itself the register allocator keeps copies in AGPRs and MXFP4 falls from
+// three waves to two)
 template <typename F, typename EL, bool SLAB, int U>
-__global__ __launch_bounds__(SK_THREADS) void SKINNY_Q_PRODUCT_KERNEL(const elem* __restrict__ X, const int64_t ldx,
+__global__ __launch_bounds__(SK_THREADS) __attribute__((amdgpu_waves_per_eu(F::WAVES, F::WAVES))) void SKINNY_Q_PRODUCT_KERNEL(const elem* __restrict__ X, const int64_t ldx,
                                                                       const int T, const int K,
                                                                       const unsigned char* __restrict__ W,
                                                                       const int64_t ldw,
@@ -113,181 +87,18 @@ __global__ __launch_bounds__(SK_THREADS) void SKINNY_Q_PRODUCT_KERNEL(const elem
                                                                       float* __restrict__ out_f32,
                                                                       const elem* __restrict__ bias,
                                                                       elem* __restrict__ y, const int64_t ldy) {
-  static_assert(F::BLOCK_SCALES || U == 1, "a format without block scales has one instance");
   __shared__ __attribute__((aligned(16))) char lds[SK_LDS_BYTES];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int kw = kchunk >> 2;                         // a multiple of SK_KW
-  const int nsteps = kw / SK_KW;
-  const int kbase = blockIdx.y * kchunk;
-  const int kend = min(kbase + kchunk, K);            // (K, kchunk multiples of 16: a lane's 16 k are inside or outside)
-  const int tok0 = blockIdx.z * SK_TOK;
-  const int nblk = K / MX_BLOCK;                      // (>= U: F::scale_bytes)
-
-  // weights: this wave's k range, rows f * 16 + (lane & 15), 16 codes (one piece) per lane and step
-  int wk0, wkend;
-  xa_wave_range((int)blockIdx.y, kchunk, wave, K, wk0, wkend);
-  const int kl = 16 * (lane >> 4);
-  const bool swap = (lane >> 4) & 1;
-  const auto sw = F::swap_arg(swap);                  // (what the format's conversion makes of it)
-  const int eb = (lane >> 5) & (U - 1);               // which of the step's two blocks this lane group is in
-  const unsigned char* wp[2];
-  const unsigned char* ep[2];
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    const int row = blockIdx.x * SK_ROWS + f * 16 + (lane & 15);
-    wp[f] = W + (int64_t)(row < R ? row : 0) * ldw;
-    ep[f] = E + (int64_t)(row < R ? row : 0) * ldse;
-  }
-  // token pieces: piece p = threadIdx.x + 256 q is token p >> 5 (= 8 q + threadIdx.x >> 5), wave range (p >> 3) & 3 and
-  // 16-byte piece p & 7 (both the same for every q)
-  const int xwr = (threadIdx.x >> 3) & 3;
-  const int xk0 = kbase + xwr * kw + 8 * (threadIdx.x & 7), xkend = min(kbase + (xwr + 1) * kw, kend);
-  const elem* xp[SK_PIECES];
-  bool xtok[SK_PIECES];
-#pragma unroll
-  for (int q = 0; q < SK_PIECES; ++q) {
-    const int t = tok0 + 8 * q + (int)(threadIdx.x >> 5);
-    xtok[q] = t < T;
-    xp[q] = X + (int64_t)(xtok[q] ? t : 0) * ldx;
-  }
-
-  typename F::piece wn[2];
-  unsigned int en[2] = {0u, 0u};
-  s16x8 xn[SK_PIECES];
-  auto issue = [&](int step) {          // every load is issued; what lies outside is fetched from k = 0 and zeroed
-    const int ks = wk0 + step * SK_KW;
-    // the step's U scale bytes in one load that stays inside the row (blocks ks / 32 + 0 .. U - 1; where the row's
-    // block count is odd its last block is the second byte of the load one block back: shifted down)
-    const int b = ks / MX_BLOCK, bl = min(b, nblk - U);
-    const int sh = 8 * (min(b - bl, U - 1) + eb);
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const int k = ks + kl;
-      const bool ok = k < wkend;
-      const typename F::piece v = F::load(wp[f], ok ? k : 0);
-      wn[f] = ok ? v : typename F::piece{};          // (code 0 is +0 in every format, under every clamped scale)
-      if constexpr (F::BLOCK_SCALES) en[f] = mx_load_scales<U>(ep[f] + bl) >> sh;
-    }
-#pragma unroll
-    for (int q = 0; q < SK_PIECES; ++q) {
-      const int k = xk0 + step * SK_KW;
-      const bool ok = k < xkend;
-      const s16x8 v = *reinterpret_cast<const s16x8*>(xp[q] + (ok ? k : 0));
-      xn[q] = ok && xtok[q] ? v : s16x8{};
-    }
-  };
-
-  f32x4 acc[2][4];
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) acc[f][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // this lane's 32 bytes of a token's line as 8-byte pieces, read i at xo[i].  The four offsets are made opaque to the
-  // compiler one by one: knowing that two of them differ by 16 it fuses the pair into ds_read2_b64, which is banked
-  // modulo 32 dwords and costs four times the cycles of the ds_read_b64 the argument above is made for.
-  int xo[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    xo[i] = (lane & 15) * SK_PITCH + wave * (SK_KW * 2) + 2 * kl + 8 * (i ^ (int)swap);
-    asm volatile("" : "+v"(xo[i]));
-  }
-
-  issue(0);
-  for (int step = 0; step < nsteps; ++step) {
-    s16x8 w[2][2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) F::template operands<EL>(wn[f], sk_block_scale<F>(en[f]), sw, w[f]);
-#pragma unroll
-    for (int q = 0; q < SK_PIECES; ++q) {
-      const int p = (int)threadIdx.x + SK_THREADS * q;
-      *reinterpret_cast<s16x8*>(lds + (p >> 5) * SK_PITCH + (p & 31) * 16) = xn[q];
-    }
-    __syncthreads();
-    issue(step + 1 < nsteps ? step + 1 : step);      // (the last step fetches itself again: no load under a branch)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      const int off = tt * 16 * SK_PITCH;
-      u32x2 p[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) p[i] = *reinterpret_cast<const u32x2*>(lds + xo[i] + off);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const u32x4 xv = {p[2 * j][0], p[2 * j][1], p[2 * j + 1][0], p[2 * j + 1][1]};
-#pragma unroll
-        for (int f = 0; f < 2; ++f) acc[f][tt] = EL::mfma16(w[f][j], __builtin_bit_cast(s16x8, xv), acc[f][tt]);
-      }
-    }
-    __syncthreads();
-  }
-
-  // the four waves' sums, added in wave order: wave w finishes accumulators 2 w and 2 w + 1 (a = 4 f + tt)
-  f32x4* red = reinterpret_cast<f32x4*>(lds);
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) red[(wave * 8 + f * 4 + tt) * 64 + lane] = acc[f][tt];
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int a = 2 * wave + i, f = a >> 2, tt = a & 3;
-    f32x4 sum = red[a * 64 + lane];
-    sum += red[(8 + a) * 64 + lane];
-    sum += red[(16 + a) * 64 + lane];
-    sum += red[(24 + a) * 64 + lane];
-    // result layout: column (token) = lane & 15, rows 4 (lane >> 4) + 0..3 -- R is a multiple of 16 for the slabs
-    const int t = tok0 + tt * 16 + (lane & 15);
-    const int row0 = blockIdx.x * SK_ROWS + f * 16 + 4 * (lane >> 4);
-    if (SLAB) {
-      if (t < T && row0 < R) *reinterpret_cast<f32x4*>(out_f32 + ((int64_t)blockIdx.y * T + t) * R + row0) = sum;
-    } else {
-      float sc[4], bv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {                   // (rows beyond R read the last row's scale and bias; never stored)
-        const int row = min(row0 + j, R - 1);
-        sc[j] = F::row_scale(E, ldse, row);
-        bv[j] = bias ? EL::to_f32(bias[row]) : 0.f;
-      }
-      if (t < T) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (row0 + j < R)
-            y[(int64_t)t * ldy + row0 + j] = EL::from_f32(F::ROW_SCALES ? sum[j] * sc[j] + bv[j] : sum[j] + bv[j]);
-      }
-    }
-  }
+  skq_product<F, EL, SLAB, U>(lds, X, ldx, T, K, W, ldw, E, ldse, R, kchunk, out_f32, bias, y, ldy, blockIdx.x, blockIdx.y,
+                              (int)blockIdx.z * SK_TOK);
 }
 
-// h = round(sa (slab_0 + slab_1 + ...)), four elements per thread (r is a multiple of 4: the four share a token).  E,
-// ldse and r4 = r / 4 are read only where the format has row scales.
+// h = round(sa (slab_0 + slab_1 + ...)), four elements per thread: skq_combine
 template <typename F, typename EL>
 __global__ __launch_bounds__(SK_THREADS) void SKINNY_Q_COMBINE_KERNEL(const float* __restrict__ slabs, const int nslabs,
                                                                       const int64_t items, elem* __restrict__ h,
                                                                       const unsigned char* __restrict__ E,
                                                                       const int64_t ldse, const int r4) {
-  const int64_t i = (int64_t)blockIdx.x * SK_THREADS + threadIdx.x;
-  const int64_t ic = min(i, items - 1);
-  f32x4 v[SK_MAX_SLABS];
-#pragma unroll
-  for (int s = 0; s < SK_MAX_SLABS; ++s)      // (all in flight together; a slab that does not exist: the last one again)
-    v[s] = *reinterpret_cast<const f32x4*>(slabs + ((int64_t)min(s, nslabs - 1) * items + ic) * 4);
-  f32x4 sc;
-  if constexpr (F::ROW_SCALES) {
-    const int col = (int)(ic % r4) * 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sc[j] = F::row_scale(E, ldse, col + j);      // (the scales are only 4-byte aligned)
-  }
-  f32x4 sum = v[0];
-#pragma unroll
-  for (int s = 1; s < SK_MAX_SLABS; ++s)
-    if (s < nslabs) sum += v[s];
-  if constexpr (F::ROW_SCALES) sum *= sc;
-  if (i < items) {
-    uint2 p;
-    p.x = EL::pack2(sum[0], sum[1]);
-    p.y = EL::pack2(sum[2], sum[3]);
-    *reinterpret_cast<uint2*>(h + i * 4) = p;
-  }
+  skq_combine<F, EL>(slabs, nslabs, items, h, E, ldse, r4, (int64_t)blockIdx.x * SK_THREADS + threadIdx.x);
 }
 
 // the product instance for rows of k_total weights: by the scale bytes of a load where the format has block scales
@@ -328,30 +139,6 @@ int launch_skinny_q(const void* x, int64_t ldx, int64_t T, int64_t n_i, const vo
                      static_cast<elem*>(y), ldy);
   PTD_CHECK_LAUNCH(F::HB_LAUNCH);
   return PTD_OK;
-}
-
-// what format F's entry takes, at 32 <= T <= F::MAX_T: n_i and r multiples of F::K_QUANTUM, code rows on
-// F::CODE_ALIGN bytes, scale arrays on F::SCALE_ALIGN (ea, eb: null where the format does not look at them)
-template <typename F>
-bool skinny_q_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x, int64_t ldx,
-                     const void* Aq, int64_t lda, const void* ea, const void* Bq, int64_t ldb, const void* eb,
-                     const void* bias) {
-  if (dtype != PTD_BF16 && dtype != PTD_F16) return false;
-  if (w_format != F::FORMAT) return false;
-  if (T < SK_MIN_T || T > F::MAX_T || n_o < 1 || r < F::K_QUANTUM || n_i < F::K_QUANTUM) return false;
-  if (n_i % F::K_QUANTUM || r % F::K_QUANTUM || ldx % 8 || lda % F::CODE_ALIGN || ldb % F::CODE_ALIGN) return false;
-  if (n_i >= (1ll << 30) || r >= (1ll << 27) || n_o >= (1ll << 30)) return false;      // (lowrank_skinny_serves' limits)
-  const uintptr_t scale_bits = F::SCALE_ALIGN - 1, code_bits = F::CODE_ALIGN - 1;
-  if ((reinterpret_cast<uintptr_t>(ea) & scale_bits) || (reinterpret_cast<uintptr_t>(eb) & scale_bits)) return false;
-  if (reinterpret_cast<uintptr_t>(bias) & 1) return false;
-  if ((reinterpret_cast<uintptr_t>(Aq) & code_bits) || (reinterpret_cast<uintptr_t>(Bq) & code_bits)) return false;
-  return aligned16(x);
-}
-
-size_t skinny_q_workspace_bytes(int64_t T, int64_t r) {
-  if (T < 1 || r < 1) return 0;
-  // (the 16-bit entry's formula -- the bound over every split, then the 16-bit h: monotone in T and r)
-  return slab_bytes(T, r) + align_up((size_t)T * (size_t)r * 2, 256);
 }
 
 template <typename F>

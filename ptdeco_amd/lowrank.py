@@ -502,8 +502,8 @@ def lowrank_group(x: torch.Tensor, pairs, *, quantized: str = "members") -> torc
     default: each runs as it does alone and the outputs are concatenated.  "fused": when all members are of ONE
     quantised class with equal in_features and activation dtype, x is a ROCm tensor of that dtype and no gradient is
     wanted, the group runs on ``torch.ops.ptdeco_amd.lowrank_forward_group_q`` -- at 1 to 16 tokens two launches for
-    the group, every member's columns bit for bit what the member returns alone; at other token counts each member as
-    it runs alone.  A mix of formats, or a quantised member beside a 16-bit one, is the "members" path.  16-bit members
+    the group, at 32 to 96 tokens three, every member's columns bit for bit what the member returns alone; at other
+    token counts each member as it runs alone.  A mix of formats, or a quantised member beside a 16-bit one, is the "members" path.  16-bit members
     ignore the keyword; any other value raises ``ValueError``."""
     pairs = list(pairs)
     fmt = _fused_format(x, pairs, quantized)
@@ -535,8 +535,8 @@ def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu", *, quantized: st
     ``quantized`` says what happens to quantised members (``LowRankLinearW8`` / ``W4`` / ``W6``).  "members", the
     default: the expression itself on the modules' outputs.  "fused": when gate and up are of ONE quantised class with
     equal in_features, out_features and activation dtype, x is a ROCm tensor of that dtype and no gradient is wanted,
-    ``torch.ops.ptdeco_amd.lowrank_forward_gated_q`` -- at 1 to 16 tokens two launches, the activation evaluated by the
-    kernel on gate's own bits: with "relu" the result is the expression's bit for bit, with "silu" and "gelu_tanh" it is
+    ``torch.ops.ptdeco_amd.lowrank_forward_gated_q`` -- at 1 to 16 tokens two launches, at 32 to 96 tokens three, the
+    activation evaluated by the kernel on gate's own bits: with "relu" the result is the expression's bit for bit, with "silu" and "gelu_tanh" it is
     within the gated bound of it (the kernel's f32 activation against torch's, each rounded once), not its bits.  At
     other token counts the members run as they do alone and torch applies the activation.  Anything else is the
     "members" path; 16-bit members ignore the keyword; any other value raises ``ValueError``."""

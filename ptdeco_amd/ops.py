@@ -1027,6 +1027,144 @@ def lowrank_skinny_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq:
     return _q_call(_MXFP6, "skinny", x2d, Aq, ea, Bq, eb, bias)
 
 
+# Quantised pairs of ONE format that read one input at small batches (32 <= T <= the format's skinny cap) run on
+# ptd_lowrank_skinny_group_q (q / k / v, gate / up: three launches for the group) and ptd_lowrank_skinny_gated_q
+# (act(gate(x)) * up(x): three launches); every member's bits are those of the format's own skinny entry.  No switch of
+# their own: PTD_LOWRANK_GROUP_Q=0 turns both off, and so does the format's PTD_LOWRANK_SKINNY_W8 / _W4 / _W6=0 for that
+# format.  The C entries serve every group their members' entries serve; which groups these functions TAKE is measured
+# (profiles/pair_skinny_group_q.json; `_q_skinny_group_takes`).
+
+
+def _q_skinny_group_takes(fmt: _QFormat, T: int, n_i: int, ranks: Sequence[int], widths: Sequence[int]) -> bool:
+    """The measured rule on shapes: the classes of cells of profiles/pair_skinny_group_q.json in which every fused round
+    is below every round of the members run one by one.  Every measured class is won (both ranks, 32 / 64 / 96 tokens,
+    the three formats, the q / k / v group and the gated pair): nothing is excluded."""
+    return True
+
+
+def _q_skinny_group_rule(fmt: _QFormat, x: _Facts, members: Sequence[Sequence[Optional[_Facts]]]) -> bool:
+    """The rule of ptd_lowrank_skinny_group_q on plain facts: 1 to 4 members (Aq, sa, Bq, sb, bias), each served by the
+    format's skinny entry on the common x (which makes every member's n_i that of x)."""
+    if not 1 <= len(members) <= _GROUP_MAX:
+        return False
+    return all(_q_rule(fmt, "skinny", x, *m) for m in members)
+
+
+def _q_skinny_group_facts(fmt: _QFormat, x2d, Aqs, sas, Bqs, sbs, biases):
+    """``_q_group_facts`` under the switches of the skinny routes."""
+    count = len(Aqs)
+    if not (_GROUP_Q and globals()[fmt.switch("skinny")]) or any(len(s) != count for s in (sas, Bqs, sbs, biases)):
+        return None
+    f = _facts(x2d, *Aqs, *sas, *Bqs, *sbs, *biases)
+    if f is None:
+        return None
+    cols = [f[1 + i * count:1 + (i + 1) * count] for i in range(5)]
+    return f[0], list(zip(*cols))
+
+
+def lowrank_skinny_group_q_serves(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], sas: Sequence[torch.Tensor],
+                                  Bqs: Sequence[torch.Tensor], sbs: Sequence[torch.Tensor],
+                                  biases: Sequence[Optional[torch.Tensor]]) -> bool:
+    """Whether ``lowrank_skinny_group_q`` takes these operands as they lie (the rule of ptd_lowrank_skinny_group_q,
+    without loading the library): 1 to 4 members of the format ``fmt`` ("fp8", "MXFP4" or "MXFP6"), each served by
+    ``lowrank_skinny_w8`` / ``_w4`` / ``_w6`` on the common x2d, in a measured class of shapes."""
+    fmt = _q_format(fmt)
+    f = _q_skinny_group_facts(fmt, x2d, Aqs, sas, Bqs, sbs, biases)
+    if f is None or not _q_skinny_group_rule(fmt, *f):
+        return False
+    return _q_skinny_group_takes(fmt, x2d.shape[0], x2d.shape[1], [A.shape[0] for A in Aqs], [B.shape[0] for B in Bqs])
+
+
+def lowrank_skinny_group_q(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], sas: Sequence[torch.Tensor],
+                           Bqs: Sequence[torch.Tensor], sbs: Sequence[torch.Tensor],
+                           biases: Sequence[Optional[torch.Tensor]]) -> torch.Tensor:
+    """[the skinny pair of member m on x2d for m] side by side: y [T, sum n_o] contiguous, member m in columns
+    [off_m, off_m + n_o_m), for 32 <= T <= the format's cap rows of x2d and 1 to 4 members of the format ``fmt`` ("fp8":
+    operands of ``lowrank_skinny_w8``; "MXFP4": of ``lowrank_skinny_w4``; "MXFP6": of ``lowrank_skinny_w6``):
+    ptd_lowrank_skinny_group_q, three launches.  Every member's columns hold the bits its own entry gives.  A group the
+    entry does not serve raises."""
+    fmt = _q_format(fmt)
+    count = len(Aqs)
+    assert 1 <= count and all(len(s) == count for s in (sas, Bqs, sbs, biases))
+    _dev(x2d, *Aqs, *sas, *Bqs, *sbs, *biases)
+    x2d = _rows2d(x2d)
+    T, n_i = x2d.shape
+    ms = [_q_member(fmt, x2d, *m) for m in zip(Aqs, sas, Bqs, sbs, biases)]
+    widths = [m[2].shape[0] for m in ms]
+    total = sum(widths)
+    y = torch.empty((T, total), dtype=x2d.dtype, device=x2d.device)
+    offs = [sum(widths[:m]) * y.element_size() for m in range(count)]
+    ptrs, i64s = ctypes.c_void_p * count, ctypes.c_int64 * count
+    r = i64s(*[m[0].shape[0] for m in ms])
+    lib = _hip.load()
+    code = _Q_CODES[fmt.name]
+    ws_bytes = lib.ptd_lowrank_skinny_group_q_workspace_bytes(code, count, T, n_i, r, _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+    with torch.cuda.device(x2d.device):
+        rc = lib.ptd_lowrank_skinny_group_q(
+            code, x2d.data_ptr(), x2d.stride(0), T, n_i, count,
+            ptrs(*[m[0].data_ptr() for m in ms]), i64s(*[m[0].stride(0) for m in ms]),
+            ptrs(*[m[1].data_ptr() for m in ms]), i64s(*[_scale_pitch(fmt, m[1]) for m in ms]), r,
+            ptrs(*[m[2].data_ptr() for m in ms]), i64s(*[m[2].stride(0) for m in ms]),
+            ptrs(*[m[3].data_ptr() for m in ms]), i64s(*[_scale_pitch(fmt, m[3]) for m in ms]), i64s(*widths),
+            ptrs(*[_ptr(m[4]) for m in ms]), ptrs(*[y.data_ptr() + off for off in offs]), i64s(*[total] * count),
+            ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
+    _hip.check(rc, "ptd_lowrank_skinny_group_q")
+    return y
+
+
+def lowrank_skinny_gated_q_serves(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: torch.Tensor, Bq_g: torch.Tensor,
+                                  sb_g: torch.Tensor, bias_g: Optional[torch.Tensor], Aq_u: torch.Tensor,
+                                  sa_u: torch.Tensor, Bq_u: torch.Tensor, sb_u: torch.Tensor,
+                                  bias_u: Optional[torch.Tensor], act: str) -> bool:
+    """Whether ``lowrank_skinny_gated_q`` takes these operands as they lie (the rule of ptd_lowrank_skinny_gated_q,
+    without loading the library): a known activation, gate and up of the format ``fmt`` each served by its skinny entry
+    on the common x2d, and the same number of output rows."""
+    if act not in GATED_ACTS:
+        return False
+    if not lowrank_skinny_group_q_serves(fmt, x2d, (Aq_g, Aq_u), (sa_g, sa_u), (Bq_g, Bq_u), (sb_g, sb_u),
+                                         (bias_g, bias_u)):
+        return False
+    return Bq_g.shape[0] == Bq_u.shape[0]
+
+
+def lowrank_skinny_gated_q(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: torch.Tensor, Bq_g: torch.Tensor,
+                           sb_g: torch.Tensor, bias_g: Optional[torch.Tensor], Aq_u: torch.Tensor, sa_u: torch.Tensor,
+                           Bq_u: torch.Tensor, sb_u: torch.Tensor, bias_u: Optional[torch.Tensor],
+                           act: str) -> torch.Tensor:
+    """round(round(act(g)) * u) with g and u the skinny pairs of gate and up (format ``fmt``, operands per member as in
+    ``lowrank_skinny_group_q``) on 32 <= T <= the format's cap rows of x2d, act one of ``GATED_ACTS``:
+    ptd_lowrank_skinny_gated_q, three launches, y [T, n_ff] contiguous.  g and u are the bits the members' own entries
+    give.  Operands the entry does not serve raise."""
+    fmt = _q_format(fmt)
+    if act not in GATED_ACTS:
+        raise ValueError(f"act must be one of {sorted(GATED_ACTS)}, got {act!r}")
+    _dev(x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g, Aq_u, sa_u, Bq_u, sb_u, bias_u)
+    x2d = _rows2d(x2d)
+    T, n_i = x2d.shape
+    g = _q_member(fmt, x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g)
+    u = _q_member(fmt, x2d, Aq_u, sa_u, Bq_u, sb_u, bias_u)
+    n_ff = g[2].shape[0]
+    assert u[2].shape[0] == n_ff
+    y = torch.empty((T, n_ff), dtype=x2d.dtype, device=x2d.device)
+    lib = _hip.load()
+    code = _Q_CODES[fmt.name]
+    ws_bytes = lib.ptd_lowrank_skinny_gated_q_workspace_bytes(code, T, n_i, g[0].shape[0], u[0].shape[0], _code(x2d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
+
+    def side(m):
+        Aq, ea, Bq, eb, bias = m
+        return (Aq.data_ptr(), Aq.stride(0), ea.data_ptr(), _scale_pitch(fmt, ea), Aq.shape[0],
+                Bq.data_ptr(), Bq.stride(0), eb.data_ptr(), _scale_pitch(fmt, eb), _ptr(bias))
+
+    with torch.cuda.device(x2d.device):
+        rc = lib.ptd_lowrank_skinny_gated_q(code, x2d.data_ptr(), x2d.stride(0), T, n_i, *side(g), *side(u), n_ff,
+                                            GATED_ACTS[act], y.data_ptr(), n_ff, ws.data_ptr(), ws_bytes, _code(x2d),
+                                            _stream(x2d))
+    _hip.check(rc, "ptd_lowrank_skinny_gated_q")
+    return y
+
+
 # The MX pairs at every other token count (17 <= T < _SKINNY_MIN_T and T above the format's skinny cap: prompt
 # processing) run on ptd_lowrank_tile_w4 / ptd_lowrank_tile_w6: one HIP launch writes both factors out as their exact
 # 16-bit values into the call's workspace, then the 16-bit tile pair (ptd_lowrank_forward) runs on them -- the bits of
