@@ -17,6 +17,35 @@ F32, F64, BF16, F16 = 0, 1, 2, 3
 ABI_VERSION = 6
 Q_FP8_E4M3, Q_MXFP4, Q_MXFP6_E2M3 = 1, 2, 3      # PTD_Q_*: q_format of the grouped and gated quantised decode entries
 
+# The argument lists the entries of the low-rank pair share, each named once (restype, argtypes): the regimes of a family
+# (forward / decode / skinny / tile) differ in their kernels, not in their C parameters.
+_PAIR_WS = (c_size_t, [c_int64, c_int64, c_int64, c_int])                       # (T, n_i, r, dtype)
+_TILE_WS = (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int])              # (T, n_i, r, n_o, dtype)
+_GATED_WS = (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int])             # (T, n_i, r_g, r_u, dtype)
+_GROUP_Q_WS = (c_size_t, [c_int, c_int, c_int64, c_int64, c_void_p, c_int])     # (q_format, count, T, n_i, r[], dtype)
+_GATED_Q_WS = (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64, c_int])    # (q_format, T, n_i, r_g, r_u, dtype)
+_X = [c_void_p, c_int64, c_int64, c_int64]                                      # x, ldx, T, n_i
+_Y_WS = [c_void_p, c_int64, c_void_p, c_size_t]                                 # y, ldy, ws, ws_bytes
+# the 16-bit pair: A, lda, r, B, ldb, n_o, bias
+_PAIR16 = (c_int, _X + [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p] + _Y_WS + [c_int, c_void_p])
+# the fp8 pair: Aq, lda, scale_a, r, Bq, ldb, scale_b, n_o, bias; then dtype, w_format, stream
+_PAIR_FP8 = (c_int, _X + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
+             + _Y_WS + [c_int, c_int, c_void_p])
+# the MX pair: Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias; then dtype, w_format, stream
+_PAIR_MX = (c_int, _X + [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                         c_void_p] + _Y_WS + [c_int, c_int, c_void_p])
+# codes, ldq, scales, lds, rows, cols, out, ldo, dtype, w_format, stream
+_MX_DEQUANT = (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p])
+# the 16-bit gated pair: per side A, lda, r, B, ldb, bias; then n_ff, act
+_SIDE16 = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]
+_GATED16 = (c_int, _X + _SIDE16 + _SIDE16 + [c_int64, c_int] + _Y_WS + [c_int, c_void_p])
+# the quantised group: q_format, x, ldx, T, n_i, count, then 13 arrays (Aq, lda, sa, ldsa, r, Bq, ldb, sb, ldsb, n_o, bias,
+# y, ldy), ws, ws_bytes, dtype, stream
+_GROUP_Q = (c_int, [c_int] + _X + [c_int] + [c_void_p] * 13 + [c_void_p, c_size_t, c_int, c_void_p])
+# the quantised gated pair: q_format, x ..., per side Aq, lda, sa, ldsa, r, Bq, ldb, sb, ldsb, bias; then n_ff, act
+_SIDE_Q = [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
+_GATED_Q = (c_int, [c_int] + _X + _SIDE_Q + _SIDE_Q + [c_int64, c_int] + _Y_WS + [c_int, c_void_p])
+
 # name -> (restype, argtypes); must list every symbol include/ptdeco_hip.h declares
 SIGNATURES = {
     "ptd_version": (c_int, []),
@@ -68,92 +97,46 @@ SIGNATURES = {
     "ptd_gemm_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int]),
     "ptd_gemm_ws": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                             c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ptd_lowrank_forward_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_forward": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
-                                    c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int,
-                                    c_void_p]),
-    "ptd_lowrank_decode_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_decode": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
-                                   c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int,
-                                   c_void_p]),
-    "ptd_lowrank_decode_w8_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_decode_w8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                      c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
-                                      c_size_t, c_int, c_int, c_void_p]),
-    "ptd_lowrank_decode_w4_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_decode_w4": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                      c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
-                                      c_size_t, c_int, c_int, c_void_p]),
-    "ptd_lowrank_decode_w6_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_decode_w6": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                      c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
-                                      c_size_t, c_int, c_int, c_void_p]),
+    "ptd_lowrank_forward_workspace_bytes": _PAIR_WS,
+    "ptd_lowrank_forward": _PAIR16,
+    "ptd_lowrank_decode_workspace_bytes": _PAIR_WS,
+    "ptd_lowrank_decode": _PAIR16,
+    "ptd_lowrank_decode_w8_workspace_bytes": _PAIR_WS,
+    "ptd_lowrank_decode_w8": _PAIR_FP8,
+    "ptd_lowrank_decode_w4_workspace_bytes": _PAIR_WS,
+    "ptd_lowrank_decode_w4": _PAIR_MX,
+    "ptd_lowrank_decode_w6_workspace_bytes": _PAIR_WS,
+    "ptd_lowrank_decode_w6": _PAIR_MX,
     "ptd_lowrank_decode_group_workspace_bytes": (c_size_t, [c_int, c_int64, c_int64, c_void_p, c_int]),
     "ptd_lowrank_decode_group": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                          c_int, c_void_p]),
-    "ptd_lowrank_decode_gated_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_decode_gated": (c_int, [c_void_p, c_int64, c_int64, c_int64,
-                                         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
-                                         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
-                                         c_int64, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]),
-    "ptd_lowrank_decode_group_q_workspace_bytes": (c_size_t, [c_int, c_int, c_int64, c_int64, c_void_p, c_int]),
-    "ptd_lowrank_decode_group_q": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
-    "ptd_lowrank_decode_gated_q_workspace_bytes": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_decode_gated_q": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64,
-                                           c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                           c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                           c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                           c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                           c_int64, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]),
-    "ptd_lowrank_skinny_group_q_workspace_bytes": (c_size_t, [c_int, c_int, c_int64, c_int64, c_void_p, c_int]),
-    "ptd_lowrank_skinny_group_q": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
-    "ptd_lowrank_skinny_gated_q_workspace_bytes": (c_size_t, [c_int, c_int64, c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_skinny_gated_q": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64,
-                                           c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                           c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                           c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                           c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                           c_int64, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]),
-    "ptd_lowrank_skinny_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_skinny": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
-                                   c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int,
-                                   c_void_p]),
-    "ptd_lowrank_skinny_w8_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_skinny_w8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                      c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
-                                      c_size_t, c_int, c_int, c_void_p]),
-    "ptd_lowrank_skinny_w4_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_skinny_w4": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                      c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
-                                      c_size_t, c_int, c_int, c_void_p]),
-    "ptd_lowrank_skinny_w6_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_skinny_w6": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                      c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
-                                      c_size_t, c_int, c_int, c_void_p]),
-    "ptd_lowrank_dequant_w4": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
-                                       c_int, c_void_p]),
-    "ptd_lowrank_dequant_w6": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
-                                       c_int, c_void_p]),
-    "ptd_lowrank_tile_w4_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_tile_w4": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                    c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
-                                    c_size_t, c_int, c_int, c_void_p]),
-    "ptd_lowrank_tile_w6_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_tile_w6": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                    c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
-                                    c_size_t, c_int, c_int, c_void_p]),
-    "ptd_lowrank_skinny_gated_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
-    "ptd_lowrank_skinny_gated": (c_int, [c_void_p, c_int64, c_int64, c_int64,
-                                         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
-                                         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
-                                         c_int64, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]),
+    "ptd_lowrank_decode_gated_workspace_bytes": _GATED_WS,
+    "ptd_lowrank_decode_gated": _GATED16,
+    "ptd_lowrank_decode_group_q_workspace_bytes": _GROUP_Q_WS,
+    "ptd_lowrank_decode_group_q": _GROUP_Q,
+    "ptd_lowrank_decode_gated_q_workspace_bytes": _GATED_Q_WS,
+    "ptd_lowrank_decode_gated_q": _GATED_Q,
+    "ptd_lowrank_skinny_group_q_workspace_bytes": _GROUP_Q_WS,
+    "ptd_lowrank_skinny_group_q": _GROUP_Q,
+    "ptd_lowrank_skinny_gated_q_workspace_bytes": _GATED_Q_WS,
+    "ptd_lowrank_skinny_gated_q": _GATED_Q,
+    "ptd_lowrank_skinny_workspace_bytes": _PAIR_WS,
+    "ptd_lowrank_skinny": _PAIR16,
+    "ptd_lowrank_skinny_w8_workspace_bytes": _PAIR_WS,
+    "ptd_lowrank_skinny_w8": _PAIR_FP8,
+    "ptd_lowrank_skinny_w4_workspace_bytes": _PAIR_WS,
+    "ptd_lowrank_skinny_w4": _PAIR_MX,
+    "ptd_lowrank_skinny_w6_workspace_bytes": _PAIR_WS,
+    "ptd_lowrank_skinny_w6": _PAIR_MX,
+    "ptd_lowrank_dequant_w4": _MX_DEQUANT,
+    "ptd_lowrank_dequant_w6": _MX_DEQUANT,
+    "ptd_lowrank_tile_w4_workspace_bytes": _TILE_WS,
+    "ptd_lowrank_tile_w4": _PAIR_MX,
+    "ptd_lowrank_tile_w6_workspace_bytes": _TILE_WS,
+    "ptd_lowrank_tile_w6": _PAIR_MX,
+    "ptd_lowrank_skinny_gated_workspace_bytes": _GATED_WS,
+    "ptd_lowrank_skinny_gated": _GATED16,
     "ptd_lowrank_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),
     "ptd_lowrank_forward_nchw_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
     "ptd_lowrank_forward_nchw": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,

@@ -56,16 +56,21 @@ import torch
 from . import ops
 
 
-@torch.library.custom_op("ptdeco_amd::lowrank_forward", mutates_args=())
-def lowrank_forward(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """(x2d @ A^T) @ B^T + bias with x2d [T, n_i], A [r, n_i], B [n_o, r]; y [T, n_o] contiguous.  At decode shapes
-    (1 <= T <= 16, aligned operands: ops.lowrank_decode_serves) on the weight-streaming kernels of ptd_lowrank_decode,
-    at small batches (32 <= T <= 96, bf16 / f16: ops.lowrank_skinny_serves) on the skinny products of ptd_lowrank_skinny."""
+def _member(x2d, A, B, bias):
+    """One 16-bit pair on the entry that serves it: decode, else skinny, else the tile pair."""
     if ops.lowrank_decode_serves(x2d, A, B, bias):
         return ops.lowrank_decode(x2d, A, B, bias)
     if ops.lowrank_skinny_serves(x2d, A, B, bias):
         return ops.lowrank_skinny(x2d, A, B, bias)
     return ops.lowrank_forward(x2d, A, B, bias)
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward", mutates_args=())
+def lowrank_forward(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """(x2d @ A^T) @ B^T + bias with x2d [T, n_i], A [r, n_i], B [n_o, r]; y [T, n_o] contiguous.  At decode shapes
+    (1 <= T <= 16, aligned operands: ops.lowrank_decode_serves) on the weight-streaming kernels of ptd_lowrank_decode,
+    at small batches (32 <= T <= 96, bf16 / f16: ops.lowrank_skinny_serves) on the skinny products of ptd_lowrank_skinny."""
+    return _member(x2d, A, B, bias)
 
 
 @lowrank_forward.register_fake
@@ -89,13 +94,7 @@ def lowrank_forward_group(x2d: torch.Tensor, As: List[torch.Tensor], Bs: List[to
     y = x2d.new_empty((x2d.shape[0], sum(B.shape[0] for B in Bs)))
     off = 0
     for A, B, bias in zip(As, Bs, biases):
-        if ops.lowrank_decode_serves(x2d, A, B, bias):
-            ym = ops.lowrank_decode(x2d, A, B, bias)
-        elif ops.lowrank_skinny_serves(x2d, A, B, bias):
-            ym = ops.lowrank_skinny(x2d, A, B, bias)
-        else:
-            ym = ops.lowrank_forward(x2d, A, B, bias)
-        y[:, off:off + B.shape[0]] = ym
+        y[:, off:off + B.shape[0]] = _member(x2d, A, B, bias)
         off += B.shape[0]
     return y
 
@@ -141,14 +140,6 @@ def lowrank_forward_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor,
     else:
         g, u = (_member(x2d, A, B, bias) for A, B, bias in zip(As, Bs, biases))
     return (GATE_ACTS[act](g) * u).contiguous()
-
-
-def _member(x2d, A, B, bias):
-    if ops.lowrank_decode_serves(x2d, A, B, bias):
-        return ops.lowrank_decode(x2d, A, B, bias)
-    if ops.lowrank_skinny_serves(x2d, A, B, bias):
-        return ops.lowrank_skinny(x2d, A, B, bias)
-    return ops.lowrank_forward(x2d, A, B, bias)
 
 
 @lowrank_forward_gated.register_fake
@@ -368,6 +359,16 @@ _Q_MEMBER = {
 }
 
 
+def _route_fused_q(kind, fmt, *operands):
+    """The fused entry of quantised members that serves them: ops.lowrank_<regime>_<kind>_serves, then
+    ops.lowrank_<regime>_<kind> (``kind`` "group_q" or "gated_q"; both looked up when the body runs), decode before
+    skinny; None where neither takes the operands as they lie."""
+    for regime in ("decode", "skinny"):
+        if getattr(ops, f"lowrank_{regime}_{kind}_serves")(fmt, *operands):
+            return getattr(ops, f"lowrank_{regime}_{kind}")(fmt, *operands)
+    return None
+
+
 def _q_member(fmt, x2d, *w):
     """One quantised member as its own operator runs it: today's result for that member."""
     tag, regimes, expression, _ = _Q_MEMBER[fmt]
@@ -385,10 +386,9 @@ def lowrank_forward_group_q(x2d: torch.Tensor, Aqs: List[torch.Tensor], sas: Lis
     entry); otherwise each member as its own operator runs it.  Inference only: no autograd formula."""
     if fmt not in _Q_MEMBER:
         raise ValueError(f"fmt must be one of {sorted(_Q_MEMBER)}, got {fmt!r}")
-    if ops.lowrank_decode_group_q_serves(fmt, x2d, Aqs, sas, Bqs, sbs, biases):
-        return ops.lowrank_decode_group_q(fmt, x2d, Aqs, sas, Bqs, sbs, biases)
-    if ops.lowrank_skinny_group_q_serves(fmt, x2d, Aqs, sas, Bqs, sbs, biases):
-        return ops.lowrank_skinny_group_q(fmt, x2d, Aqs, sas, Bqs, sbs, biases)
+    y = _route_fused_q("group_q", fmt, x2d, Aqs, sas, Bqs, sbs, biases)
+    if y is not None:
+        return y
     y = x2d.new_empty((x2d.shape[0], sum(Bq.shape[0] for Bq in Bqs)))
     off = 0
     for w in zip(Aqs, sas, Bqs, sbs, biases):
@@ -426,10 +426,9 @@ def lowrank_forward_gated_q(x2d: torch.Tensor, Aq_g: torch.Tensor, s_a_g: torch.
     if act not in GATE_ACTS:
         raise ValueError(f"act must be one of {sorted(GATE_ACTS)}, got {act!r}")
     gate, up = (Aq_g, s_a_g, Bq_g, s_b_g, bias_g), (Aq_u, s_a_u, Bq_u, s_b_u, bias_u)
-    if ops.lowrank_decode_gated_q_serves(fmt, x2d, *gate, *up, act):
-        return ops.lowrank_decode_gated_q(fmt, x2d, *gate, *up, act)
-    if ops.lowrank_skinny_gated_q_serves(fmt, x2d, *gate, *up, act):
-        return ops.lowrank_skinny_gated_q(fmt, x2d, *gate, *up, act)
+    y = _route_fused_q("gated_q", fmt, x2d, *gate, *up, act)
+    if y is not None:
+        return y
     g, u = _q_member(fmt, x2d, *gate), _q_member(fmt, x2d, *up)
     return (GATE_ACTS[act](g) * u).contiguous()
 

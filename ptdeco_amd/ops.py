@@ -429,19 +429,16 @@ def _pair16_rule(regime: str, x: _Facts, A: _Facts, B: _Facts, bias: Optional[_F
     return True
 
 
-def lowrank_decode_serves(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> bool:
-    """Whether ``lowrank_decode`` takes these operands as they lie (the rule of ptd_lowrank_decode, without loading the
-    library): real tensors on a ROCm device, f32 / bf16 / f16, 1 <= T <= 16, r >= 8, n_i, r and the row pitches
-    multiples of 8 (f32: 4) elements, unit inner strides, 16-byte aligned data."""
-    if not _DECODE:
+def _pair16_serves(regime: str, x2d, A, B, bias) -> bool:
+    """The rule of ptd_lowrank_<regime> under its switch (_DECODE / _SKINNY); loads no library."""
+    if not globals()[f"_{regime.upper()}"]:
         return False
     f = _facts(x2d, A, B, bias)
-    return f is not None and _pair16_rule("decode", *f)
+    return f is not None and _pair16_rule(regime, *f)
 
 
-def lowrank_decode(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """(x2d @ A^T) @ B^T + bias for 1 <= T <= 16 rows of x2d, A [r, n_i], B [n_o, r]: ptd_lowrank_decode.  A shape the
-    entry does not serve (``lowrank_decode_serves``) raises; row t of the result depends on row t of x2d alone."""
+def _pair16_call(regime: str, x2d, A, B, bias) -> torch.Tensor:
+    """ptd_lowrank_<regime> on these operands: the workspace, the bias in x2d's dtype, the argument list."""
     _dev(x2d, A, B, bias)
     x2d, A, B = _rows2d(x2d), _rows2d(A), _rows2d(B)
     T, n_i = x2d.shape
@@ -449,16 +446,30 @@ def lowrank_decode(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Op
     assert A.shape[1] == n_i and B.shape[1] == r and x2d.dtype == A.dtype == B.dtype
     y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
     lib = _hip.load()
-    ws_bytes = lib.ptd_lowrank_decode_workspace_bytes(T, n_i, r, _code(x2d))
+    entry = f"ptd_lowrank_{regime}"
+    ws_bytes = getattr(lib, entry + "_workspace_bytes")(T, n_i, r, _code(x2d))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
     if bias is not None:
         bias = bias.to(x2d.dtype).contiguous()
     with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_decode(x2d.data_ptr(), x2d.stride(0), T, n_i, A.data_ptr(), A.stride(0), r,
-                                    B.data_ptr(), B.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o,
-                                    ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_decode")
+        rc = getattr(lib, entry)(x2d.data_ptr(), x2d.stride(0), T, n_i, A.data_ptr(), A.stride(0), r,
+                                 B.data_ptr(), B.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o,
+                                 ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
+    _hip.check(rc, entry)
     return y
+
+
+def lowrank_decode_serves(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``lowrank_decode`` takes these operands as they lie (the rule of ptd_lowrank_decode, without loading the
+    library): real tensors on a ROCm device, f32 / bf16 / f16, 1 <= T <= 16, r >= 8, n_i, r and the row pitches
+    multiples of 8 (f32: 4) elements, unit inner strides, 16-byte aligned data."""
+    return _pair16_serves("decode", x2d, A, B, bias)
+
+
+def lowrank_decode(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """(x2d @ A^T) @ B^T + bias for 1 <= T <= 16 rows of x2d, A [r, n_i], B [n_o, r]: ptd_lowrank_decode.  A shape the
+    entry does not serve (``lowrank_decode_serves``) raises; row t of the result depends on row t of x2d alone."""
+    return _pair16_call("decode", x2d, A, B, bias)
 
 
 # The pair with fp8 (e4m3fn) factors and one f32 scale per factor row at decode shapes runs on ptd_lowrank_decode_w8:
@@ -571,25 +582,33 @@ def _q_serves(fmt: _QFormat, regime: str, x2d, Aq, ea, Bq, eb, bias) -> bool:
     return f is not None and _q_rule(fmt, regime, *f)
 
 
-def _q_call(fmt: _QFormat, regime: str, x2d, Aq, ea, Bq, eb, bias) -> torch.Tensor:
-    """ptd_lowrank_<regime>_<tag> on these operands: the workspace, the bias in x2d's dtype, the argument list."""
-    _dev(x2d, Aq, ea, Bq, eb, bias)
-    x2d, Aq, Bq = _rows2d(x2d), _rows2d(Aq), _rows2d(Bq)
+def _q_member(fmt: _QFormat, x2d, Aq, ea, Bq, eb, bias):
+    """One pair's operands as the entries take them, on an x2d that ``_rows2d`` has seen: row-major views, the bias in
+    x2d's dtype.  The one copy of the asserts, for the single pair, the members of a group and both sides of a gate."""
+    Aq, Bq = _rows2d(Aq), _rows2d(Bq)
     ea, eb = (ea.contiguous(), eb.contiguous()) if fmt.scale_rank == 1 else (_rows2d(ea), _rows2d(eb))
-    T, n_i = x2d.shape
-    r, n_o = Aq.shape[0], Bq.shape[0]
+    n_i, r, n_o = x2d.shape[1], Aq.shape[0], Bq.shape[0]
     assert Aq.dtype == Bq.dtype == fmt.code_dtype and ea.dtype == eb.dtype == fmt.scale_dtype
     assert fmt.scale_rank == 1 or (n_i % 32 == 0 and r % 32 == 0)
     assert Aq.shape == (r, fmt.row_bytes(n_i)) and ea.shape == fmt.scale_shape(r, n_i)
     assert Bq.shape == (n_o, fmt.row_bytes(r)) and eb.shape == fmt.scale_shape(n_o, r)
+    bias = None if bias is None else bias.to(x2d.dtype).contiguous()
+    return Aq, ea, Bq, eb, bias
+
+
+def _q_call(fmt: _QFormat, regime: str, x2d, Aq, ea, Bq, eb, bias) -> torch.Tensor:
+    """ptd_lowrank_<regime>_<tag> on these operands: the workspace, the bias in x2d's dtype, the argument list."""
+    _dev(x2d, Aq, ea, Bq, eb, bias)
+    x2d = _rows2d(x2d)
+    Aq, ea, Bq, eb, bias = _q_member(fmt, x2d, Aq, ea, Bq, eb, bias)
+    T, n_i = x2d.shape
+    r, n_o = Aq.shape[0], Bq.shape[0]
     y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
     lib = _hip.load()
     entry = f"ptd_lowrank_{regime}_{fmt.tag}"
     shape = (T, n_i, r, n_o) if regime == "tile" else (T, n_i, r)      # (the tile entry holds both factors too)
     ws_bytes = getattr(lib, entry + "_workspace_bytes")(*shape, _code(x2d))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    if bias is not None:
-        bias = bias.to(x2d.dtype).contiguous()
     a = (Aq.data_ptr(), Aq.stride(0), ea.data_ptr()) + ((ea.stride(0),) if fmt.scale_rank == 2 else ())
     b = (Bq.data_ptr(), Bq.stride(0), eb.data_ptr()) + ((eb.stride(0),) if fmt.scale_rank == 2 else ())
     with torch.cuda.device(x2d.device):
@@ -708,23 +727,19 @@ def lowrank_decode_group(x2d: torch.Tensor, As: Sequence[torch.Tensor], Bs: Sequ
 GATED_ACTS = {"silu": 0, "gelu_tanh": 1, "relu": 2}      # PTD_ACT_*
 
 
-def lowrank_decode_gated_serves(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
-                                Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> bool:
-    """Whether ``lowrank_decode_gated`` takes these operands as they lie (the rule of ptd_lowrank_decode_gated, without
-    loading the library): a known activation, gate and up each served by ``lowrank_decode`` on the common x2d, and the
-    same number of output rows."""
+def _gated16_serves(regime: str, x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act) -> bool:
+    """The rule of ptd_lowrank_<regime>_gated: a known activation, both members served by ``lowrank_<regime>``, equal
+    n_ff; loads no library."""
     if act not in GATED_ACTS:
         return False
-    if not (lowrank_decode_serves(x2d, Ag, Bg, bias_g) and lowrank_decode_serves(x2d, Au, Bu, bias_u)):
+    member = globals()[f"lowrank_{regime}_serves"]      # (the module attribute, at call time; gate is asked first)
+    if not (member(x2d, Ag, Bg, bias_g) and member(x2d, Au, Bu, bias_u)):
         return False
     return Bg.shape[0] == Bu.shape[0]
 
 
-def lowrank_decode_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
-                         Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> torch.Tensor:
-    """act((x2d @ Ag^T) @ Bg^T + bias_g) * ((x2d @ Au^T) @ Bu^T + bias_u) for 1 <= T <= 16 rows of x2d, Ag [r_g, n_i],
-    Bg [n_ff, r_g], Au [r_u, n_i], Bu [n_ff, r_u], act one of ``GATED_ACTS``: ptd_lowrank_decode_gated, y [T, n_ff]
-    contiguous.  Operands the entry does not serve (``lowrank_decode_gated_serves``) raise."""
+def _gated16_call(regime: str, x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act) -> torch.Tensor:
+    """ptd_lowrank_<regime>_gated on these operands: the workspace, the biases in x2d's dtype, the argument list."""
     if act not in GATED_ACTS:
         raise ValueError(f"act must be one of {sorted(GATED_ACTS)}, got {act!r}")
     _dev(x2d, Ag, Bg, bias_g, Au, Bu, bias_u)
@@ -735,17 +750,34 @@ def lowrank_decode_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, 
     assert x2d.dtype == Ag.dtype == Bg.dtype == Au.dtype == Bu.dtype
     y = torch.empty((T, n_ff), dtype=x2d.dtype, device=x2d.device)
     lib = _hip.load()
-    ws_bytes = lib.ptd_lowrank_decode_gated_workspace_bytes(T, n_i, r_g, r_u, _code(x2d))
+    entry = f"ptd_lowrank_{regime}_gated"
+    ws_bytes = getattr(lib, entry + "_workspace_bytes")(T, n_i, r_g, r_u, _code(x2d))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
     bias_g = None if bias_g is None else bias_g.to(x2d.dtype).contiguous()
     bias_u = None if bias_u is None else bias_u.to(x2d.dtype).contiguous()
     with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_decode_gated(
+        rc = getattr(lib, entry)(
             x2d.data_ptr(), x2d.stride(0), T, n_i, Ag.data_ptr(), Ag.stride(0), r_g, Bg.data_ptr(), Bg.stride(0),
             _ptr(bias_g), Au.data_ptr(), Au.stride(0), r_u, Bu.data_ptr(), Bu.stride(0), _ptr(bias_u), n_ff,
             GATED_ACTS[act], y.data_ptr(), n_ff, ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_decode_gated")
+    _hip.check(rc, entry)
     return y
+
+
+def lowrank_decode_gated_serves(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
+                                Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> bool:
+    """Whether ``lowrank_decode_gated`` takes these operands as they lie (the rule of ptd_lowrank_decode_gated, without
+    loading the library): a known activation, gate and up each served by ``lowrank_decode`` on the common x2d, and the
+    same number of output rows."""
+    return _gated16_serves("decode", x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
+
+
+def lowrank_decode_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
+                         Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> torch.Tensor:
+    """act((x2d @ Ag^T) @ Bg^T + bias_g) * ((x2d @ Au^T) @ Bu^T + bias_u) for 1 <= T <= 16 rows of x2d, Ag [r_g, n_i],
+    Bg [n_ff, r_g], Au [r_u, n_i], Bu [n_ff, r_u], act one of ``GATED_ACTS``: ptd_lowrank_decode_gated, y [T, n_ff]
+    contiguous.  Operands the entry does not serve (``lowrank_decode_gated_serves``) raise."""
+    return _gated16_call("decode", x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
 
 
 # Quantised pairs of ONE format that read one input at decode shapes run on ptd_lowrank_decode_group_q (q / k / v, gate /
@@ -767,18 +799,18 @@ def _q_format(fmt) -> _QFormat:
         raise ValueError(f"fmt must be one of {sorted(_Q_FORMATS)}, got {fmt!r}") from None
 
 
-def _q_group_rule(fmt: _QFormat, x: _Facts, members: Sequence[Sequence[Optional[_Facts]]]) -> bool:
-    """The rule of ptd_lowrank_decode_group_q on plain facts: 1 to 4 members (Aq, sa, Bq, sb, bias), each served by the
-    format's decode entry on the common x (which makes every member's n_i that of x)."""
+def _q_group_rule(fmt: _QFormat, regime: str, x: _Facts, members: Sequence[Sequence[Optional[_Facts]]]) -> bool:
+    """The rule of ptd_lowrank_<regime>_group_q on plain facts: 1 to 4 members (Aq, sa, Bq, sb, bias), each served by the
+    format's entry of that regime on the common x (which makes every member's n_i that of x)."""
     if not 1 <= len(members) <= _GROUP_MAX:
         return False
-    return all(_q_rule(fmt, "decode", x, *m) for m in members)
+    return all(_q_rule(fmt, regime, x, *m) for m in members)
 
 
-def _q_group_facts(fmt: _QFormat, x2d, Aqs, sas, Bqs, sbs, biases):
+def _q_group_facts(fmt: _QFormat, regime: str, x2d, Aqs, sas, Bqs, sbs, biases):
     """(facts of x2d, facts of the members) of a group the switches allow and whose lists agree in length, else None."""
     count = len(Aqs)
-    if not (_GROUP_Q and globals()[fmt.switch("decode")]) or any(len(s) != count for s in (sas, Bqs, sbs, biases)):
+    if not (_GROUP_Q and globals()[fmt.switch(regime)]) or any(len(s) != count for s in (sas, Bqs, sbs, biases)):
         return None
     f = _facts(x2d, *Aqs, *sas, *Bqs, *sbs, *biases)
     if f is None:
@@ -787,42 +819,20 @@ def _q_group_facts(fmt: _QFormat, x2d, Aqs, sas, Bqs, sbs, biases):
     return f[0], list(zip(*cols))
 
 
-def lowrank_decode_group_q_serves(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], sas: Sequence[torch.Tensor],
-                                  Bqs: Sequence[torch.Tensor], sbs: Sequence[torch.Tensor],
-                                  biases: Sequence[Optional[torch.Tensor]]) -> bool:
-    """Whether ``lowrank_decode_group_q`` takes these operands as they lie (the rule of ptd_lowrank_decode_group_q,
-    without loading the library): 1 to 4 members of the format ``fmt`` ("fp8", "MXFP4" or "MXFP6"), each served by
-    ``lowrank_decode_w8`` / ``_w4`` / ``_w6`` on the common x2d."""
+def _q_group_serves(fmt, regime: str, x2d, Aqs, sas, Bqs, sbs, biases) -> bool:
+    """The rule of ptd_lowrank_<regime>_group_q under its switches (``_q_group_facts``); loads no library."""
     fmt = _q_format(fmt)
-    f = _q_group_facts(fmt, x2d, Aqs, sas, Bqs, sbs, biases)
-    return f is not None and _q_group_rule(fmt, *f)
-
-
-def _q_member(fmt: _QFormat, x2d, Aq, ea, Bq, eb, bias):
-    """One member's operands as the entries take them (``_q_call``): row-major views, the bias in x2d's dtype."""
-    Aq, Bq = _rows2d(Aq), _rows2d(Bq)
-    ea, eb = (ea.contiguous(), eb.contiguous()) if fmt.scale_rank == 1 else (_rows2d(ea), _rows2d(eb))
-    n_i, r, n_o = x2d.shape[1], Aq.shape[0], Bq.shape[0]
-    assert Aq.dtype == Bq.dtype == fmt.code_dtype and ea.dtype == eb.dtype == fmt.scale_dtype
-    assert fmt.scale_rank == 1 or (n_i % 32 == 0 and r % 32 == 0)
-    assert Aq.shape == (r, fmt.row_bytes(n_i)) and ea.shape == fmt.scale_shape(r, n_i)
-    assert Bq.shape == (n_o, fmt.row_bytes(r)) and eb.shape == fmt.scale_shape(n_o, r)
-    bias = None if bias is None else bias.to(x2d.dtype).contiguous()
-    return Aq, ea, Bq, eb, bias
+    f = _q_group_facts(fmt, regime, x2d, Aqs, sas, Bqs, sbs, biases)
+    return f is not None and _q_group_rule(fmt, regime, *f)
 
 
 def _scale_pitch(fmt: _QFormat, e: torch.Tensor) -> int:
     return e.stride(0) if fmt.scale_rank == 2 else 0
 
 
-def lowrank_decode_group_q(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], sas: Sequence[torch.Tensor],
-                           Bqs: Sequence[torch.Tensor], sbs: Sequence[torch.Tensor],
-                           biases: Sequence[Optional[torch.Tensor]]) -> torch.Tensor:
-    """[the decode pair of member m on x2d for m] side by side: y [T, sum n_o] contiguous, member m in columns
-    [off_m, off_m + n_o_m), for 1 <= T <= 16 rows of x2d and 1 to 4 members of the format ``fmt`` ("fp8": operands of
-    ``lowrank_decode_w8``; "MXFP4": of ``lowrank_decode_w4``; "MXFP6": of ``lowrank_decode_w6``):
-    ptd_lowrank_decode_group_q, two launches.  Every member's columns hold the bits its own entry gives.  A group the
-    entry does not serve (``lowrank_decode_group_q_serves``) raises."""
+def _q_group_call(fmt, regime: str, x2d, Aqs, sas, Bqs, sbs, biases) -> torch.Tensor:
+    """ptd_lowrank_<regime>_group_q on these members: the workspace, the members' operands (``_q_member``) as arrays,
+    every member's columns of one y."""
     fmt = _q_format(fmt)
     count = len(Aqs)
     assert 1 <= count and all(len(s) == count for s in (sas, Bqs, sbs, biases))
@@ -837,11 +847,12 @@ def lowrank_decode_group_q(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], 
     ptrs, i64s = ctypes.c_void_p * count, ctypes.c_int64 * count
     r = i64s(*[m[0].shape[0] for m in ms])
     lib = _hip.load()
+    entry = f"ptd_lowrank_{regime}_group_q"
     code = _Q_CODES[fmt.name]
-    ws_bytes = lib.ptd_lowrank_decode_group_q_workspace_bytes(code, count, T, n_i, r, _code(x2d))
+    ws_bytes = getattr(lib, entry + "_workspace_bytes")(code, count, T, n_i, r, _code(x2d))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
     with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_decode_group_q(
+        rc = getattr(lib, entry)(
             code, x2d.data_ptr(), x2d.stride(0), T, n_i, count,
             ptrs(*[m[0].data_ptr() for m in ms]), i64s(*[m[0].stride(0) for m in ms]),
             ptrs(*[m[1].data_ptr() for m in ms]), i64s(*[_scale_pitch(fmt, m[1]) for m in ms]), r,
@@ -849,33 +860,24 @@ def lowrank_decode_group_q(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], 
             ptrs(*[m[3].data_ptr() for m in ms]), i64s(*[_scale_pitch(fmt, m[3]) for m in ms]), i64s(*widths),
             ptrs(*[_ptr(m[4]) for m in ms]), ptrs(*[y.data_ptr() + off for off in offs]), i64s(*[total] * count),
             ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_decode_group_q")
+    _hip.check(rc, entry)
     return y
 
 
-def lowrank_decode_gated_q_serves(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: torch.Tensor, Bq_g: torch.Tensor,
-                                  sb_g: torch.Tensor, bias_g: Optional[torch.Tensor], Aq_u: torch.Tensor,
-                                  sa_u: torch.Tensor, Bq_u: torch.Tensor, sb_u: torch.Tensor,
-                                  bias_u: Optional[torch.Tensor], act: str) -> bool:
-    """Whether ``lowrank_decode_gated_q`` takes these operands as they lie (the rule of ptd_lowrank_decode_gated_q,
-    without loading the library): a known activation, gate and up of the format ``fmt`` each served by its decode entry
-    on the common x2d, and the same number of output rows."""
+def _q_gated_serves(fmt, regime: str, x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g, Aq_u, sa_u, Bq_u, sb_u, bias_u, act) -> bool:
+    """The rule of ptd_lowrank_<regime>_gated_q: a known activation, (gate, up) a group ``_q_group_serves`` takes, equal
+    n_ff; loads no library."""
     if act not in GATED_ACTS:
         return False
-    if not lowrank_decode_group_q_serves(fmt, x2d, (Aq_g, Aq_u), (sa_g, sa_u), (Bq_g, Bq_u), (sb_g, sb_u),
-                                         (bias_g, bias_u)):
+    if not _q_group_serves(fmt, regime, x2d, (Aq_g, Aq_u), (sa_g, sa_u), (Bq_g, Bq_u), (sb_g, sb_u), (bias_g, bias_u)):
         return False
     return Bq_g.shape[0] == Bq_u.shape[0]
 
 
-def lowrank_decode_gated_q(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: torch.Tensor, Bq_g: torch.Tensor,
-                           sb_g: torch.Tensor, bias_g: Optional[torch.Tensor], Aq_u: torch.Tensor, sa_u: torch.Tensor,
-                           Bq_u: torch.Tensor, sb_u: torch.Tensor, bias_u: Optional[torch.Tensor],
-                           act: str) -> torch.Tensor:
-    """round(round(act(g)) * u) with g and u the decode pairs of gate and up (format ``fmt``, operands per member as in
-    ``lowrank_decode_group_q``) on 1 <= T <= 16 rows of x2d, act one of ``GATED_ACTS``: ptd_lowrank_decode_gated_q, two
-    launches, y [T, n_ff] contiguous.  g and u are the bits the members' own entries give.  Operands the entry does not
-    serve (``lowrank_decode_gated_q_serves``) raise."""
+def _q_gated_call(fmt, regime: str, x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g, Aq_u, sa_u, Bq_u, sb_u, bias_u,
+                  act) -> torch.Tensor:
+    """ptd_lowrank_<regime>_gated_q on gate and up: the workspace, each side's operands (``_q_member``) in the entry's
+    order, the activation's code."""
     fmt = _q_format(fmt)
     if act not in GATED_ACTS:
         raise ValueError(f"act must be one of {sorted(GATED_ACTS)}, got {act!r}")
@@ -888,8 +890,9 @@ def lowrank_decode_gated_q(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: tor
     assert u[2].shape[0] == n_ff
     y = torch.empty((T, n_ff), dtype=x2d.dtype, device=x2d.device)
     lib = _hip.load()
+    entry = f"ptd_lowrank_{regime}_gated_q"
     code = _Q_CODES[fmt.name]
-    ws_bytes = lib.ptd_lowrank_decode_gated_q_workspace_bytes(code, T, n_i, g[0].shape[0], u[0].shape[0], _code(x2d))
+    ws_bytes = getattr(lib, entry + "_workspace_bytes")(code, T, n_i, g[0].shape[0], u[0].shape[0], _code(x2d))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
 
     def side(m):
@@ -898,11 +901,51 @@ def lowrank_decode_gated_q(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: tor
                 Bq.data_ptr(), Bq.stride(0), eb.data_ptr(), _scale_pitch(fmt, eb), _ptr(bias))
 
     with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_decode_gated_q(code, x2d.data_ptr(), x2d.stride(0), T, n_i, *side(g), *side(u), n_ff,
-                                            GATED_ACTS[act], y.data_ptr(), n_ff, ws.data_ptr(), ws_bytes, _code(x2d),
-                                            _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_decode_gated_q")
+        rc = getattr(lib, entry)(code, x2d.data_ptr(), x2d.stride(0), T, n_i, *side(g), *side(u), n_ff, GATED_ACTS[act],
+                                 y.data_ptr(), n_ff, ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
+    _hip.check(rc, entry)
     return y
+
+
+def lowrank_decode_group_q_serves(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], sas: Sequence[torch.Tensor],
+                                  Bqs: Sequence[torch.Tensor], sbs: Sequence[torch.Tensor],
+                                  biases: Sequence[Optional[torch.Tensor]]) -> bool:
+    """Whether ``lowrank_decode_group_q`` takes these operands as they lie (the rule of ptd_lowrank_decode_group_q,
+    without loading the library): 1 to 4 members of the format ``fmt`` ("fp8", "MXFP4" or "MXFP6"), each served by
+    ``lowrank_decode_w8`` / ``_w4`` / ``_w6`` on the common x2d."""
+    return _q_group_serves(fmt, "decode", x2d, Aqs, sas, Bqs, sbs, biases)
+
+
+def lowrank_decode_group_q(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], sas: Sequence[torch.Tensor],
+                           Bqs: Sequence[torch.Tensor], sbs: Sequence[torch.Tensor],
+                           biases: Sequence[Optional[torch.Tensor]]) -> torch.Tensor:
+    """[the decode pair of member m on x2d for m] side by side: y [T, sum n_o] contiguous, member m in columns
+    [off_m, off_m + n_o_m), for 1 <= T <= 16 rows of x2d and 1 to 4 members of the format ``fmt`` ("fp8": operands of
+    ``lowrank_decode_w8``; "MXFP4": of ``lowrank_decode_w4``; "MXFP6": of ``lowrank_decode_w6``):
+    ptd_lowrank_decode_group_q, two launches.  Every member's columns hold the bits its own entry gives.  A group the
+    entry does not serve (``lowrank_decode_group_q_serves``) raises."""
+    return _q_group_call(fmt, "decode", x2d, Aqs, sas, Bqs, sbs, biases)
+
+
+def lowrank_decode_gated_q_serves(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: torch.Tensor, Bq_g: torch.Tensor,
+                                  sb_g: torch.Tensor, bias_g: Optional[torch.Tensor], Aq_u: torch.Tensor,
+                                  sa_u: torch.Tensor, Bq_u: torch.Tensor, sb_u: torch.Tensor,
+                                  bias_u: Optional[torch.Tensor], act: str) -> bool:
+    """Whether ``lowrank_decode_gated_q`` takes these operands as they lie (the rule of ptd_lowrank_decode_gated_q,
+    without loading the library): a known activation, gate and up of the format ``fmt`` each served by its decode entry
+    on the common x2d, and the same number of output rows."""
+    return _q_gated_serves(fmt, "decode", x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g, Aq_u, sa_u, Bq_u, sb_u, bias_u, act)
+
+
+def lowrank_decode_gated_q(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: torch.Tensor, Bq_g: torch.Tensor,
+                           sb_g: torch.Tensor, bias_g: Optional[torch.Tensor], Aq_u: torch.Tensor, sa_u: torch.Tensor,
+                           Bq_u: torch.Tensor, sb_u: torch.Tensor, bias_u: Optional[torch.Tensor],
+                           act: str) -> torch.Tensor:
+    """round(round(act(g)) * u) with g and u the decode pairs of gate and up (format ``fmt``, operands per member as in
+    ``lowrank_decode_group_q``) on 1 <= T <= 16 rows of x2d, act one of ``GATED_ACTS``: ptd_lowrank_decode_gated_q, two
+    launches, y [T, n_ff] contiguous.  g and u are the bits the members' own entries give.  Operands the entry does not
+    serve (``lowrank_decode_gated_q_serves``) raise."""
+    return _q_gated_call(fmt, "decode", x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g, Aq_u, sa_u, Bq_u, sb_u, bias_u, act)
 
 
 # The pair at small batches (32 <= T <= _SKINNY_MAX_T tokens, bf16 / f16) runs on ptd_lowrank_skinny: skinny products
@@ -919,33 +962,14 @@ def lowrank_skinny_serves(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, b
     """Whether ``lowrank_skinny`` takes these operands as they lie (the rule of ptd_lowrank_skinny, without loading the
     library): real tensors on a ROCm device, bf16 / f16, _SKINNY_MIN_T <= T <= _SKINNY_MAX_T, r >= 8, n_i, r and the row
     pitches multiples of 8 elements, unit inner strides, 16-byte aligned data."""
-    if not _SKINNY:
-        return False
-    f = _facts(x2d, A, B, bias)
-    return f is not None and _pair16_rule("skinny", *f)
+    return _pair16_serves("skinny", x2d, A, B, bias)
 
 
 def lowrank_skinny(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
     """(x2d @ A^T) @ B^T + bias for 32 <= T <= _SKINNY_MAX_T rows of x2d, A [r, n_i], B [n_o, r], bf16 / f16:
     ptd_lowrank_skinny.  A shape the entry does not serve (``lowrank_skinny_serves``) raises; row t of the result
     depends on row t of x2d alone."""
-    _dev(x2d, A, B, bias)
-    x2d, A, B = _rows2d(x2d), _rows2d(A), _rows2d(B)
-    T, n_i = x2d.shape
-    r, n_o = A.shape[0], B.shape[0]
-    assert A.shape[1] == n_i and B.shape[1] == r and x2d.dtype == A.dtype == B.dtype
-    y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
-    lib = _hip.load()
-    ws_bytes = lib.ptd_lowrank_skinny_workspace_bytes(T, n_i, r, _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    if bias is not None:
-        bias = bias.to(x2d.dtype).contiguous()
-    with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_skinny(x2d.data_ptr(), x2d.stride(0), T, n_i, A.data_ptr(), A.stride(0), r,
-                                    B.data_ptr(), B.stride(0), n_o, _ptr(bias), y.data_ptr(), n_o,
-                                    ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_skinny")
-    return y
+    return _pair16_call("skinny", x2d, A, B, bias)
 
 
 # The fp8 pair of lowrank_decode_w8 at small batches (32 <= T <= _SKINNY_W8_MAX_T tokens) runs on ptd_lowrank_skinny_w8:
@@ -1031,35 +1055,11 @@ def lowrank_skinny_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq:
 # ptd_lowrank_skinny_group_q (q / k / v, gate / up: three launches for the group) and ptd_lowrank_skinny_gated_q
 # (act(gate(x)) * up(x): three launches); every member's bits are those of the format's own skinny entry.  No switch of
 # their own: PTD_LOWRANK_GROUP_Q=0 turns both off, and so does the format's PTD_LOWRANK_SKINNY_W8 / _W4 / _W6=0 for that
-# format.  The C entries serve every group their members' entries serve; which groups these functions TAKE is measured
-# (profiles/pair_skinny_group_q.json; `_q_skinny_group_takes`).
-
-
-def _q_skinny_group_takes(fmt: _QFormat, T: int, n_i: int, ranks: Sequence[int], widths: Sequence[int]) -> bool:
-    """The measured rule on shapes: the classes of cells of profiles/pair_skinny_group_q.json in which every fused round
-    is below every round of the members run one by one.  Every measured class is won (both ranks, 32 / 64 / 96 tokens,
-    the three formats, the q / k / v group and the gated pair): nothing is excluded."""
-    return True
-
-
-def _q_skinny_group_rule(fmt: _QFormat, x: _Facts, members: Sequence[Sequence[Optional[_Facts]]]) -> bool:
-    """The rule of ptd_lowrank_skinny_group_q on plain facts: 1 to 4 members (Aq, sa, Bq, sb, bias), each served by the
-    format's skinny entry on the common x (which makes every member's n_i that of x)."""
-    if not 1 <= len(members) <= _GROUP_MAX:
-        return False
-    return all(_q_rule(fmt, "skinny", x, *m) for m in members)
-
-
-def _q_skinny_group_facts(fmt: _QFormat, x2d, Aqs, sas, Bqs, sbs, biases):
-    """``_q_group_facts`` under the switches of the skinny routes."""
-    count = len(Aqs)
-    if not (_GROUP_Q and globals()[fmt.switch("skinny")]) or any(len(s) != count for s in (sas, Bqs, sbs, biases)):
-        return None
-    f = _facts(x2d, *Aqs, *sas, *Bqs, *sbs, *biases)
-    if f is None:
-        return None
-    cols = [f[1 + i * count:1 + (i + 1) * count] for i in range(5)]
-    return f[0], list(zip(*cols))
+# format.  The C entries serve every group their members' entries serve, and these functions take them all: measured
+# (profiles/pair_skinny_group_q.json), every fused round is below every round of the members run one by one in every
+# class of cells (both ranks, 32 / 64 / 96 tokens, the three formats, the q / k / v group and the gated pair), so every
+# measured class is won and nothing is excluded.  (A later measured exclusion adds its predicate on shapes then, as
+# ``_tile_mx_takes`` did.)
 
 
 def lowrank_skinny_group_q_serves(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], sas: Sequence[torch.Tensor],
@@ -1068,11 +1068,7 @@ def lowrank_skinny_group_q_serves(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Te
     """Whether ``lowrank_skinny_group_q`` takes these operands as they lie (the rule of ptd_lowrank_skinny_group_q,
     without loading the library): 1 to 4 members of the format ``fmt`` ("fp8", "MXFP4" or "MXFP6"), each served by
     ``lowrank_skinny_w8`` / ``_w4`` / ``_w6`` on the common x2d, in a measured class of shapes."""
-    fmt = _q_format(fmt)
-    f = _q_skinny_group_facts(fmt, x2d, Aqs, sas, Bqs, sbs, biases)
-    if f is None or not _q_skinny_group_rule(fmt, *f):
-        return False
-    return _q_skinny_group_takes(fmt, x2d.shape[0], x2d.shape[1], [A.shape[0] for A in Aqs], [B.shape[0] for B in Bqs])
+    return _q_group_serves(fmt, "skinny", x2d, Aqs, sas, Bqs, sbs, biases)
 
 
 def lowrank_skinny_group_q(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], sas: Sequence[torch.Tensor],
@@ -1083,34 +1079,7 @@ def lowrank_skinny_group_q(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], 
     operands of ``lowrank_skinny_w8``; "MXFP4": of ``lowrank_skinny_w4``; "MXFP6": of ``lowrank_skinny_w6``):
     ptd_lowrank_skinny_group_q, three launches.  Every member's columns hold the bits its own entry gives.  A group the
     entry does not serve raises."""
-    fmt = _q_format(fmt)
-    count = len(Aqs)
-    assert 1 <= count and all(len(s) == count for s in (sas, Bqs, sbs, biases))
-    _dev(x2d, *Aqs, *sas, *Bqs, *sbs, *biases)
-    x2d = _rows2d(x2d)
-    T, n_i = x2d.shape
-    ms = [_q_member(fmt, x2d, *m) for m in zip(Aqs, sas, Bqs, sbs, biases)]
-    widths = [m[2].shape[0] for m in ms]
-    total = sum(widths)
-    y = torch.empty((T, total), dtype=x2d.dtype, device=x2d.device)
-    offs = [sum(widths[:m]) * y.element_size() for m in range(count)]
-    ptrs, i64s = ctypes.c_void_p * count, ctypes.c_int64 * count
-    r = i64s(*[m[0].shape[0] for m in ms])
-    lib = _hip.load()
-    code = _Q_CODES[fmt.name]
-    ws_bytes = lib.ptd_lowrank_skinny_group_q_workspace_bytes(code, count, T, n_i, r, _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_skinny_group_q(
-            code, x2d.data_ptr(), x2d.stride(0), T, n_i, count,
-            ptrs(*[m[0].data_ptr() for m in ms]), i64s(*[m[0].stride(0) for m in ms]),
-            ptrs(*[m[1].data_ptr() for m in ms]), i64s(*[_scale_pitch(fmt, m[1]) for m in ms]), r,
-            ptrs(*[m[2].data_ptr() for m in ms]), i64s(*[m[2].stride(0) for m in ms]),
-            ptrs(*[m[3].data_ptr() for m in ms]), i64s(*[_scale_pitch(fmt, m[3]) for m in ms]), i64s(*widths),
-            ptrs(*[_ptr(m[4]) for m in ms]), ptrs(*[y.data_ptr() + off for off in offs]), i64s(*[total] * count),
-            ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_skinny_group_q")
-    return y
+    return _q_group_call(fmt, "skinny", x2d, Aqs, sas, Bqs, sbs, biases)
 
 
 def lowrank_skinny_gated_q_serves(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: torch.Tensor, Bq_g: torch.Tensor,
@@ -1120,12 +1089,7 @@ def lowrank_skinny_gated_q_serves(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa
     """Whether ``lowrank_skinny_gated_q`` takes these operands as they lie (the rule of ptd_lowrank_skinny_gated_q,
     without loading the library): a known activation, gate and up of the format ``fmt`` each served by its skinny entry
     on the common x2d, and the same number of output rows."""
-    if act not in GATED_ACTS:
-        return False
-    if not lowrank_skinny_group_q_serves(fmt, x2d, (Aq_g, Aq_u), (sa_g, sa_u), (Bq_g, Bq_u), (sb_g, sb_u),
-                                         (bias_g, bias_u)):
-        return False
-    return Bq_g.shape[0] == Bq_u.shape[0]
+    return _q_gated_serves(fmt, "skinny", x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g, Aq_u, sa_u, Bq_u, sb_u, bias_u, act)
 
 
 def lowrank_skinny_gated_q(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: torch.Tensor, Bq_g: torch.Tensor,
@@ -1136,33 +1100,7 @@ def lowrank_skinny_gated_q(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: tor
     ``lowrank_skinny_group_q``) on 32 <= T <= the format's cap rows of x2d, act one of ``GATED_ACTS``:
     ptd_lowrank_skinny_gated_q, three launches, y [T, n_ff] contiguous.  g and u are the bits the members' own entries
     give.  Operands the entry does not serve raise."""
-    fmt = _q_format(fmt)
-    if act not in GATED_ACTS:
-        raise ValueError(f"act must be one of {sorted(GATED_ACTS)}, got {act!r}")
-    _dev(x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g, Aq_u, sa_u, Bq_u, sb_u, bias_u)
-    x2d = _rows2d(x2d)
-    T, n_i = x2d.shape
-    g = _q_member(fmt, x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g)
-    u = _q_member(fmt, x2d, Aq_u, sa_u, Bq_u, sb_u, bias_u)
-    n_ff = g[2].shape[0]
-    assert u[2].shape[0] == n_ff
-    y = torch.empty((T, n_ff), dtype=x2d.dtype, device=x2d.device)
-    lib = _hip.load()
-    code = _Q_CODES[fmt.name]
-    ws_bytes = lib.ptd_lowrank_skinny_gated_q_workspace_bytes(code, T, n_i, g[0].shape[0], u[0].shape[0], _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-
-    def side(m):
-        Aq, ea, Bq, eb, bias = m
-        return (Aq.data_ptr(), Aq.stride(0), ea.data_ptr(), _scale_pitch(fmt, ea), Aq.shape[0],
-                Bq.data_ptr(), Bq.stride(0), eb.data_ptr(), _scale_pitch(fmt, eb), _ptr(bias))
-
-    with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_skinny_gated_q(code, x2d.data_ptr(), x2d.stride(0), T, n_i, *side(g), *side(u), n_ff,
-                                            GATED_ACTS[act], y.data_ptr(), n_ff, ws.data_ptr(), ws_bytes, _code(x2d),
-                                            _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_skinny_gated_q")
-    return y
+    return _q_gated_call(fmt, "skinny", x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g, Aq_u, sa_u, Bq_u, sb_u, bias_u, act)
 
 
 # The MX pairs at every other token count (17 <= T < _SKINNY_MIN_T and T above the format's skinny cap: prompt
@@ -1265,11 +1203,7 @@ def lowrank_skinny_gated_serves(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.T
     """Whether ``lowrank_skinny_gated`` takes these operands as they lie (the rule of ptd_lowrank_skinny_gated, without
     loading the library): a known activation, gate and up each served by ``lowrank_skinny`` on the common x2d, and the
     same number of output rows."""
-    if act not in GATED_ACTS:
-        return False
-    if not (lowrank_skinny_serves(x2d, Ag, Bg, bias_g) and lowrank_skinny_serves(x2d, Au, Bu, bias_u)):
-        return False
-    return Bg.shape[0] == Bu.shape[0]
+    return _gated16_serves("skinny", x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
 
 
 def lowrank_skinny_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
@@ -1278,27 +1212,7 @@ def lowrank_skinny_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, 
     Ag [r_g, n_i], Bg [n_ff, r_g], Au [r_u, n_i], Bu [n_ff, r_u], bf16 / f16, act one of ``GATED_ACTS``:
     ptd_lowrank_skinny_gated, y [T, n_ff] contiguous.  Operands the entry does not serve
     (``lowrank_skinny_gated_serves``) raise; row t of the result depends on row t of x2d alone."""
-    if act not in GATED_ACTS:
-        raise ValueError(f"act must be one of {sorted(GATED_ACTS)}, got {act!r}")
-    _dev(x2d, Ag, Bg, bias_g, Au, Bu, bias_u)
-    x2d, Ag, Bg, Au, Bu = (_rows2d(t) for t in (x2d, Ag, Bg, Au, Bu))
-    T, n_i = x2d.shape
-    r_g, r_u, n_ff = Ag.shape[0], Au.shape[0], Bg.shape[0]
-    assert Ag.shape[1] == n_i and Au.shape[1] == n_i and Bg.shape[1] == r_g and Bu.shape == (n_ff, r_u)
-    assert x2d.dtype == Ag.dtype == Bg.dtype == Au.dtype == Bu.dtype
-    y = torch.empty((T, n_ff), dtype=x2d.dtype, device=x2d.device)
-    lib = _hip.load()
-    ws_bytes = lib.ptd_lowrank_skinny_gated_workspace_bytes(T, n_i, r_g, r_u, _code(x2d))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
-    bias_g = None if bias_g is None else bias_g.to(x2d.dtype).contiguous()
-    bias_u = None if bias_u is None else bias_u.to(x2d.dtype).contiguous()
-    with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_skinny_gated(
-            x2d.data_ptr(), x2d.stride(0), T, n_i, Ag.data_ptr(), Ag.stride(0), r_g, Bg.data_ptr(), Bg.stride(0),
-            _ptr(bias_g), Au.data_ptr(), Au.stride(0), r_u, Bu.data_ptr(), Bu.stride(0), _ptr(bias_u), n_ff,
-            GATED_ACTS[act], y.data_ptr(), n_ff, ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_skinny_gated")
-    return y
+    return _gated16_call("skinny", x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
 
 
 def lowrank_forward_nchw(x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:

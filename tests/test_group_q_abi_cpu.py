@@ -204,17 +204,18 @@ def test_the_group_rule_on_facts(fmt):
     from ptdeco_amd import ops
 
     f, x, ms = _facts(fmt)
-    assert ops._q_group_rule(f, x, ms) and ops._q_group_rule(f, x, ms[:1]) and ops._q_group_rule(f, x, ms * 2)
-    assert not ops._q_group_rule(f, x, [])                                   # count 0
-    assert not ops._q_group_rule(f, x, ms * 2 + ms[:1])                      # count 5
+    assert (ops._q_group_rule(f, "decode", x, ms) and ops._q_group_rule(f, "decode", x, ms[:1])
+            and ops._q_group_rule(f, "decode", x, ms * 2))
+    assert not ops._q_group_rule(f, "decode", x, [])                                   # count 0
+    assert not ops._q_group_rule(f, "decode", x, ms * 2 + ms[:1])                      # count 5
     _, _, other = _facts(fmt, n_i=128)
-    assert not ops._q_group_rule(f, x, [ms[0], other[1]])                    # a member with another n_i
+    assert not ops._q_group_rule(f, "decode", x, [ms[0], other[1]])                    # a member with another n_i
     bad = ms[1][0]._replace(ptr=ms[1][0].ptr + 4)
-    assert not ops._q_group_rule(f, x, [ms[0], (bad,) + ms[1][1:]])          # a misaligned member
+    assert not ops._q_group_rule(f, "decode", x, [ms[0], (bad,) + ms[1][1:]])          # a misaligned member
     _, x17, ms17 = _facts(fmt, T=17)
-    assert not ops._q_group_rule(f, x17, ms17)                               # T = 17
+    assert not ops._q_group_rule(f, "decode", x17, ms17)                               # T = 17
     _, x16, ms16 = _facts(fmt, T=16)
-    assert ops._q_group_rule(f, x16, ms16)
+    assert ops._q_group_rule(f, "decode", x16, ms16)
 
 
 @pytest.mark.parametrize("fmt", FMTS)

@@ -277,9 +277,9 @@ def _variations(fmt):
 
 @pytest.mark.parametrize("fmt", FMTS)
 def test_the_pure_rule_is_the_c_entries_rule(fmt):
-    """ops._q_skinny_group_rule on plain facts against ptd_lowrank_skinny_group_q and ptd_lowrank_skinny_gated_q on the
-    same facts with a 16-byte workspace: PTD_ERR_WORKSPACE exactly where the rule holds, PTD_ERR_UNSUPPORTED where it does
-    not, nothing launched either way."""
+    """ops._q_group_rule(f, "skinny", ...) on plain facts against ptd_lowrank_skinny_group_q and
+    ptd_lowrank_skinny_gated_q on the same facts with a 16-byte workspace: PTD_ERR_WORKSPACE exactly where the rule
+    holds, PTD_ERR_UNSUPPORTED where it does not, nothing launched either way."""
     import ptdeco_amd  # noqa: F401
     from ptdeco_amd import _hip, ops
 
@@ -288,25 +288,25 @@ def test_the_pure_rule_is_the_c_entries_rule(fmt):
     served = unserved = 0
     for kw in _variations(f):
         x, ms, group, gated = _case(ops, f, **kw)
-        want = ops._q_skinny_group_rule(f, x, ms)
+        want = ops._q_group_rule(f, "skinny", x, ms)
         rc = lib.ptd_lowrank_skinny_group_q(*group)
         assert rc == (WORKSPACE if want else UNSUPPORTED), (fmt, kw, want, rc, lib.ptd_last_error())
         if gated is not None:
-            want2 = ops._q_skinny_group_rule(f, x, ms[:2])
+            want2 = ops._q_group_rule(f, "skinny", x, ms[:2])
             rc = lib.ptd_lowrank_skinny_gated_q(*gated)
             assert rc == (WORKSPACE if want2 else UNSUPPORTED), (fmt, kw, want2, rc, lib.ptd_last_error())
-        assert not (want and ops._q_group_rule(f, x, ms))      # the decode rule and this one never both hold
+        assert not (want and ops._q_group_rule(f, "decode", x, ms))      # the decode rule and this one never both hold
         served += want
         unserved += not want
     assert served >= 40 and unserved >= 30, (served, unserved)
     x, ms, _, _ = _case(ops, f)
-    assert not ops._q_skinny_group_rule(f, x, []) and not ops._q_skinny_group_rule(f, x, ms * 2 + ms[:1])      # count 0, 5
+    assert not ops._q_group_rule(f, "skinny", x, []) and not ops._q_group_rule(f, "skinny", x, ms * 2 + ms[:1])  # count 0, 5
     _, other, _, _ = _case(ops, f, n_i=128)
-    assert not ops._q_skinny_group_rule(f, x, [ms[0], other[1]])                    # a member with another n_i
+    assert not ops._q_group_rule(f, "skinny", x, [ms[0], other[1]])                    # a member with another n_i
     for T, holds in ((16, False), (17, False), (31, False), (32, True), (96, True), (97, False)):
         xT, msT, _, _ = _case(ops, f, T=T)
-        assert ops._q_skinny_group_rule(f, xT, msT) is holds, T
-        assert ops._q_group_rule(f, xT, msT) is (T == 16), T
+        assert ops._q_group_rule(f, "skinny", xT, msT) is holds, T
+        assert ops._q_group_rule(f, "decode", xT, msT) is (T == 16), T
 
 
 @pytest.mark.parametrize("fmt", FMTS)
