@@ -2619,7 +2619,8 @@ static int syrk16_single(const unsigned short* Y, int64_t T, int64_t n, int64_t 
   dim3 grid((unsigned)tiles, (unsigned)ksplit);
   if (e_f64) hipLaunchKernelGGL((gemm_bf16_kernel<EL, false, false, EPI_ACC_F64>), grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((gemm_bf16_kernel<EL, false, false, EPI_ACC_F32>), grid, dim3(256), 0, st, a);
-  PTD_CHECK_LAUNCH("syrk_bf16");
+  if (ksplit > 1) PTD_CHECK_LAUNCH("syrk_bf16 (generic, split K)");
+  else PTD_CHECK_LAUNCH("syrk_bf16 (generic)");
   return PTD_OK;
 }
 
@@ -2640,7 +2641,8 @@ static int launch_syrk_ring(const SyrkRingArgs& r, int grid, hipStream_t st) {
   PTD_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(syrk_bf16_ring_kernel<EL, EPI, TS, NBUF, NW>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
   hipLaunchKernelGGL((syrk_bf16_ring_kernel<EL, EPI, TS, NBUF, NW>), dim3((unsigned)grid), dim3(NW * 64), LDS, st, r);
-  PTD_CHECK_LAUNCH("syrk_bf16 (ring)");
+  if (TS == 128) PTD_CHECK_LAUNCH("syrk_bf16 (ring, 128-wide tiles)");
+  else PTD_CHECK_LAUNCH("syrk_bf16 (ring, 64-wide tiles)");
   return PTD_OK;
 }
 

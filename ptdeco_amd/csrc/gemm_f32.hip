@@ -595,13 +595,15 @@ int syrk_f32(const float* Y, int64_t T, int64_t n, int64_t ldy, void* E, int64_t
     dim3 grid((unsigned)(nbig + ndiag + 3 * npeel), 1);
     if (e_f64) hipLaunchKernelGGL((syrk_f32_mixed_kernel<EPI_ACC_F64>), grid, dim3(256), 0, st, a, nbig, ndiag);
     else hipLaunchKernelGGL((syrk_f32_mixed_kernel<EPI_ACC_F32>), grid, dim3(256), 0, st, a, nbig, ndiag);
-    PTD_CHECK_LAUNCH("syrk_f32");
+    PTD_CHECK_LAUNCH("syrk_f32 (mixed tiles)");
     return PTD_OK;
   }
   dim3 grid((unsigned)tiles, (unsigned)ksplit);
   if (e_f64) hipLaunchKernelGGL((gemm_f32_kernel<false, false, EPI_ACC_F64>), grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((gemm_f32_kernel<false, false, EPI_ACC_F32>), grid, dim3(256), 0, st, a);
-  PTD_CHECK_LAUNCH("syrk_f32");
+  // (one launch site, two schedules: the label tells a test which one a call reached)
+  if (ksplit > 1) PTD_CHECK_LAUNCH("syrk_f32 (split K)");
+  else PTD_CHECK_LAUNCH("syrk_f32 (uniform tiles)");
   return PTD_OK;
 }
 

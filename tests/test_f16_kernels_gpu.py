@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import ptdeco_oracle as orc
+from syrk_cases import GENERIC, GENERIC_SPLITK, LDSDMA, RING64, RING128      # (f16 launches carry the 16-bit labels)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -30,39 +31,84 @@ def _rand(shape, seed, scale=1.0):
 
 
 # ---------------------------------------------------------------- covariance accumulate
-@pytest.mark.parametrize("T,n,ld", [(5, 10, 10), (300, 100, 104), (1000, 1152, 1152), (333, 2560, 2568), (640, 4096, 4096),
-                                    (72, 4224, 4224), (2048, 1024, 1024)])
+def _shape_ids(rows, k):
+    """Test ids from the first k values of each row: the label column leaves the ids of the cases as they were."""
+    return ["-".join(str(v) for v in r[:k]) for r in rows]
+
+
+_SINGLE_CASES = [
+    (5, 10, 10, [GENERIC]),                     # one tile, one K range
+    (300, 100, 104, [GENERIC_SPLITK]),          # one tile, 300 rows: two K ranges of 192
+    (1000, 1152, 1152, [RING64, GENERIC]),      # 162 items of 64, 15 K steps; the last 40 rows generic
+    (333, 2560, 2568, [RING128, GENERIC]),      # 200 items of 128, 5 K steps; the last 13 rows generic
+    (640, 4096, 4096, [RING128]),
+    (72, 4224, 4224, [LDSDMA, GENERIC]),        # one K step: no ring; 561 tiles: LDS-DMA, the last 8 rows generic
+    (2048, 1024, 1024, [RING64]),
+]
+
+
+@pytest.mark.parametrize("T,n,ld,labels", _SINGLE_CASES, ids=_shape_ids(_SINGLE_CASES, 3))
 @pytest.mark.parametrize("edt", [torch.float64, torch.float32])
-def test_syrk_f16_exact_on_small_integers(ops, T, n, ld, edt):
+def test_syrk_f16_exact_on_small_integers(ops, T, n, ld, labels, edt):
     """Single steps: the generic kernel (few tiles, ragged rows), the LDS-DMA one (192 .. 2080 tiles), the ring."""
     big = _ints((T, ld), -3, 3, T + n).to(DEV)
     y = big[:, :n]
     e0 = torch.randint(-5, 6, (n, n), generator=torch.Generator().manual_seed(n)).to(edt)
     e = e0.to(DEV)
-    ops.syrk_accumulate(e, y, 1.0)
+    with ops.launch_trace() as trace:
+        ops.syrk_accumulate(e, y, 1.0)
+    assert list(trace) == labels
     ref = e0.double() + y.double().T.cpu() @ y.double().cpu()
     got = e.cpu().double()
     assert torch.equal(torch.tril(got), torch.tril(ref))
     assert torch.equal(torch.triu(got, 1), torch.triu(e0.double(), 1))
 
 
+# expected launch labels of test_syrk_multi_f16_exact_on_small_integers per (T, n) and number of steps, by hand from
+# syrk16_multi (gemm_bf16.hip): the ring needs 4 (TS = 128) or 8 (TS = 64) K steps of 64 rows over the steps of a call
+_MULTI_F16_LABELS = {
+    (2048, 4096): {s: [RING128] for s in (1, 2, 3, 8)},
+    (2048, 1024): {s: [RING64] for s in (1, 2, 3, 8)},
+    # 3 K steps a step, 128 items of 64: one or two steps are too short for the ring (36 tiles, one K range each); from
+    # three steps on the ring, then the 8 ragged rows of every step
+    (200, 1024): {1: [GENERIC], 2: [GENERIC] * 2, 3: [RING64] + [GENERIC] * 3, 8: [RING64] + [GENERIC] * 8},
+    # 2 K steps a step, 200 items of 128: a single step takes LDS-DMA (210 tiles) and the generic kernel for 2 rows
+    (130, 2560): {1: [LDSDMA, GENERIC], 2: [RING128] + [GENERIC] * 2, 3: [RING128] + [GENERIC] * 3,
+                  8: [RING128] + [GENERIC] * 8},
+    # 1 K step a step: LDS-DMA step by step until 8 steps fill the ring
+    (64, 4096): {1: [LDSDMA], 2: [LDSDMA] * 2, 3: [LDSDMA] * 3, 8: [RING128]},
+}
+
+
 @pytest.mark.parametrize("T,n", [(2048, 4096), (2048, 1024), (200, 1024), (130, 2560), (64, 4096)])
 @pytest.mark.parametrize("steps", [1, 2, 3, 8])
 def test_syrk_multi_f16_exact_on_small_integers(ops, T, n, steps):
     """ptd_syrk_accumulate_multi: one pass over E for up to 8 calibration steps (the ring kernel, TS = 128 / 64), the
-    generic kernel for the ragged rows of each step."""
+    generic kernel for the ragged rows of each step; calls too short for the ring go step by step."""
     ys = [_ints((T, n), -2, 2, 7 * s + T).to(DEV) for s in range(steps)]
     e = torch.zeros(n, n, dtype=torch.float64, device=DEV)
-    ops.syrk_accumulate_multi(e, ys, 1.0)
+    with ops.launch_trace() as trace:
+        ops.syrk_accumulate_multi(e, ys, 1.0)
+    assert list(trace) == _MULTI_F16_LABELS[(T, n)][steps]
     ref = sum(y.double().T @ y.double() for y in ys)
     assert torch.equal(torch.tril(e), torch.tril(ref))
 
 
-@pytest.mark.parametrize("T,n,steps", [(300, 100, 1), (2048, 1024, 4), (2048, 4096, 8), (777, 1000, 3)])
-def test_syrk_f16_matches_f64_of_the_upcast_inputs(ops, T, n, steps):
+_F64_CASES = [
+    (300, 100, 1, [GENERIC_SPLITK]),            # pitch 100: not a multiple of 8; one tile, two K ranges
+    (2048, 1024, 4, [RING64]),
+    (2048, 4096, 8, [RING128]),
+    (777, 1000, 3, [GENERIC_SPLITK] * 3),       # n no multiple of 64: step by step, 36 tiles, 4 K ranges each
+]
+
+
+@pytest.mark.parametrize("T,n,steps,labels", _F64_CASES, ids=_shape_ids(_F64_CASES, 3))
+def test_syrk_f16_matches_f64_of_the_upcast_inputs(ops, T, n, steps, labels):
     ys = [(_rand((T, n), 3 * s + n).float() * torch.logspace(0, -2, n)).to(H).to(DEV) for s in range(steps)]
     e = torch.zeros(n, n, dtype=torch.float64, device=DEV)
-    ops.syrk_accumulate_multi(e, ys, 1.0 / T)
+    with ops.launch_trace() as trace:
+        ops.syrk_accumulate_multi(e, ys, 1.0 / T)
+    assert list(trace) == labels
     ref = sum(y.double().T @ y.double() for y in ys) / T
     err = (torch.tril(e) - torch.tril(ref)).abs().max().item()
     assert err <= 4e-6 * max(1.0, ref.abs().max().item()), err

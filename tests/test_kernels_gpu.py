@@ -32,16 +32,39 @@ def _lower(a):
 
 
 # ---------------------------------------------------------------- covariance accumulate
-@pytest.mark.parametrize("T,n", [(5, 10), (72, 32), (300, 100), (1024, 129), (4096, 512), (777, 1000)])
+# The launch labels every covariance call below must record (ops.launch_trace), written by hand from syrk_f32
+# (gemm_f32.hip) and syrk16_multi / syrk16_single (gemm_bf16.hip); tests/syrk_cases.py explains the rules beside its
+# own cases.  The trace is the arbiter: where a comment and the trace disagreed, the comment was corrected.
+from syrk_cases import F32_MIXED, F32_SPLITK, GENERIC, GENERIC_SPLITK, LDSDMA, RING64, RING128  # noqa: E402
+
+
+def _shape_ids(rows, k):
+    """Test ids from the first k values of each row: the label column leaves the ids of the cases as they were."""
+    return ["-".join(str(v) for v in r[:k]) for r in rows]
+
+
+_ACCUMULATE_CASES = [
+    (5, 10, F32_MIXED, GENERIC),                # one tile, T <= 128: one K range (f32: a fully quartered diagonal tile)
+    (72, 32, F32_MIXED, GENERIC),
+    (300, 100, F32_SPLITK, GENERIC_SPLITK),     # one tile: f32 3 ranges of 128 rows, bf16 2 of 192 (pitch 100: no ring)
+    (1024, 129, F32_SPLITK, GENERIC_SPLITK),    # 3 tiles: f32 8 ranges, bf16 4
+    (4096, 512, F32_SPLITK, GENERIC_SPLITK),    # 10 tiles: f32 32 ranges, bf16 16 (32 ring items of 64: too few)
+    (777, 1000, F32_SPLITK, GENERIC_SPLITK),    # 36 tiles: f32 7 ranges, bf16 4
+]
+
+
+@pytest.mark.parametrize("T,n,f32_label,bf16_label", _ACCUMULATE_CASES, ids=_shape_ids(_ACCUMULATE_CASES, 2))
 @pytest.mark.parametrize("ydt,edt", [(torch.float32, torch.float64), (torch.float32, torch.float32),
                                      (torch.bfloat16, torch.float64), (torch.bfloat16, torch.float32)])
-def test_syrk_accumulate(ops, T, n, ydt, edt):
+def test_syrk_accumulate(ops, T, n, f32_label, bf16_label, ydt, edt):
     y = _rand((T, n), 11 * T + n, ydt)
     e0 = _rand((n, n), 5, edt)
     ref = e0.double() + (y.double().T @ y.double()) / T
     e = e0.to(DEV)
-    ops.syrk_accumulate(e, y.to(DEV), 1.0 / T)
-    ops.syrk_accumulate(e, y.to(DEV), 0.0)  # scale 0 adds nothing
+    with ops.launch_trace() as labels:
+        ops.syrk_accumulate(e, y.to(DEV), 1.0 / T)
+        ops.syrk_accumulate(e, y.to(DEV), 0.0)  # scale 0 adds nothing
+    assert list(labels) == [f32_label if ydt == torch.float32 else bf16_label] * 2
     got = e.cpu().double()
     # lower triangle updated, strict upper untouched
     assert torch.equal(torch.triu(got, 1), torch.triu(e0.double(), 1))
@@ -50,42 +73,63 @@ def test_syrk_accumulate(ops, T, n, ydt, edt):
     assert err <= tol * max(1.0, ref.abs().max().item()), err
 
 
-@pytest.mark.parametrize("T,n,ld", [(64, 128, 128), (200, 384, 392), (1000, 1152, 1152), (333, 2560, 2568),
-                                    (128, 4096, 4096), (640, 4096, 4096), (72, 4224, 4224)])
+_LDS_DMA_CASES = [
+    (64, 128, 128, [GENERIC]),                  # one tile, one K step: one K range
+    (200, 384, 392, [GENERIC]),                 # 6 tiles, T <= 256: one K range, padded row pitch
+    (1000, 1152, 1152, [RING64, GENERIC]),      # 15 K steps, 162 items of 64: the ring, the last 40 rows generic
+    (333, 2560, 2568, [RING128, GENERIC]),      # 5 K steps, 200 items of 128: the ring, the last 13 rows generic
+    (128, 4096, 4096, [LDSDMA]),                # 2 K steps: too few for either ring; 528 tiles, 16 diagonal ones peeled
+    (640, 4096, 4096, [RING128]),               # 10 K steps: the ring
+    (72, 4224, 4224, [LDSDMA, GENERIC]),        # 1 K step, 561 tiles: LDS-DMA, the last 8 rows generic
+]
+
+
+@pytest.mark.parametrize("T,n,ld,labels", _LDS_DMA_CASES, ids=_shape_ids(_LDS_DMA_CASES, 3))
 @pytest.mark.parametrize("edt", [torch.float64, torch.float32])
-def test_syrk_bf16_lds_dma_kernel_is_exact_on_small_integers(ops, T, n, ld, edt):
-    """The bf16 covariance kernels: the generic one (few tiles: split K with atomics) and, from 192 tiles on, the one
-    on the LDS-DMA schedule -- tile walk per XCD with a partial last group of tile rows (n = 2560), n = 4096
-    (528 tiles, 16 diagonal ones cut into K ranges added with atomics, here with fewer K steps than ranges), the ragged
-    last rows of T through the generic kernel, a padded row pitch.  Entries in -3 .. 3 keep every sum an integer
-    below 2^24: the result must equal the integer product, whatever the order of accumulation."""
+def test_syrk_bf16_lds_dma_kernel_is_exact_on_small_integers(ops, T, n, ld, labels, edt):
+    """The bf16 covariance kernels behind a single step: the generic one, the one on the LDS-DMA schedule where T is too
+    short for the ring (192 .. 2080 tiles: n = 4096 with 528 tiles, 16 diagonal ones cut into K ranges added with atomics,
+    here with fewer K steps than ranges; n = 4224), the ring kernels from 4 (8) K steps on, the ragged last rows of T
+    through the generic kernel, a padded row pitch.  Entries in -3 .. 3 keep every sum an integer below 2^24: the result
+    must equal the integer product, whatever the order of accumulation."""
     g = torch.Generator().manual_seed(T * 7 + n)
     big = torch.randint(-3, 4, (T, ld), generator=g).to(torch.bfloat16).to(DEV)
     y = big[:, :n]
     e = torch.full((n, n), 5.0, dtype=edt, device=DEV)
-    ops.syrk_accumulate(e, y, 2.0)
+    with ops.launch_trace() as trace:
+        ops.syrk_accumulate(e, y, 2.0)
+    assert list(trace) == labels
     yi = y.to(torch.float64)
     ref = 5.0 + 2.0 * (yi.T @ yi)
     assert torch.equal(torch.tril(e.double()), torch.tril(ref))
     assert torch.equal(torch.triu(e, 1), torch.full_like(e, 5.0).triu(1))
 
 
-@pytest.mark.parametrize("T,n,ld,steps", [
-    (192, 4096, 4096, 1),      # 3 K steps: below the ring's minimum (NBUF = 4 K steps at TS = 128) -> the one-step kernels
-    (256, 4096, 4096, 1),      # TS = 128 ring at its shortest (4 K steps = NBUF), 512 items = two per CU
-    (2048, 4096, 4096, 1),     # the calibration shape of a Llama q / o layer
-    (2048, 1024, 1024, 1),     # TS = 64 ring (k / v): 128 items
-    (448, 2048, 2056, 1),      # 7 K steps, n = 2048: TS = 128 ring (136 items < 192 -> TS = 64 needs 8 K steps: generic)
-    (512, 2048, 2056, 1),      # TS = 64 ring at its shortest (8 K steps = NBUF), padded row pitch, 528 items
-    (333, 2560, 2568, 3),      # TS = 128, 200 items (fewer than CUs), ragged rows through the generic kernel, 3 steps
-    (128, 4096, 4096, 8),      # 8 steps of 2 K steps each in one launch
-    (64, 4224, 4224, 11),      # 11 steps: one ring launch of 8 and a last chunk of 3 K steps (below the minimum: generic)
-    (64, 1088, 1088, 9),       # TS = 64: a launch of 8 steps and a last step too short for the ring (generic kernel)
-    (576, 4160, 4160, 2),      # n a multiple of 64 only -> TS = 64, 2113 items over 256 workgroups
-    (256, 14336, 14336, 2),    # 112 tile rows: 6272 items
-])
+_RING_CASES = [
+    # 3 K steps: below the ring's minimum (NBUF = 4 K steps at TS = 128) -> the one-step kernels: 528 tiles, LDS-DMA
+    (192, 4096, 4096, 1, [LDSDMA]),
+    (256, 4096, 4096, 1, [RING128]),      # TS = 128 ring at its shortest (4 K steps = NBUF), 512 items = two per CU
+    (2048, 4096, 4096, 1, [RING128]),     # the calibration shape of a Llama q / o layer
+    (2048, 1024, 1024, 1, [RING64]),      # TS = 64 ring (k / v): 128 items
+    # 7 K steps, n = 2048: 136 items of 128 < 192 and TS = 64 needs 8 K steps -> generic, 136 tiles: 2 K ranges
+    (448, 2048, 2056, 1, [GENERIC_SPLITK]),
+    (512, 2048, 2056, 1, [RING64]),       # TS = 64 ring at its shortest (8 K steps = NBUF), padded row pitch, 528 items
+    # TS = 128, 200 items (fewer than CUs), 3 steps in one launch, the 13 ragged rows of each through the generic kernel
+    (333, 2560, 2568, 3, [RING128] + [GENERIC] * 3),
+    (128, 4096, 4096, 8, [RING128]),      # 8 steps of 2 K steps each in one launch
+    # 11 steps: one ring launch of 8 and a last chunk of 3 K steps, below the ring's minimum: step by step, and with 561
+    # tiles and T = 64 >= one K step each of them takes the LDS-DMA kernel (not the generic one)
+    (64, 4224, 4224, 11, [RING128] + [LDSDMA] * 3),
+    # TS = 64: a launch of 8 steps and a last step too short for the ring (n % 128 != 0: generic kernel, one K range)
+    (64, 1088, 1088, 9, [RING64, GENERIC]),
+    (576, 4160, 4160, 2, [RING64]),       # n a multiple of 64 only -> TS = 64, 2113 items over 256 workgroups
+    (256, 14336, 14336, 2, [RING128]),    # 112 tile rows: 6272 items
+]
+
+
+@pytest.mark.parametrize("T,n,ld,steps,labels", _RING_CASES, ids=_shape_ids(_RING_CASES, 4))
 @pytest.mark.parametrize("edt", [torch.float64, torch.float32])
-def test_syrk_bf16_ring_kernel_and_multi_step_entry_are_exact_on_small_integers(ops, T, n, ld, steps, edt):
+def test_syrk_bf16_ring_kernel_and_multi_step_entry_are_exact_on_small_integers(ops, T, n, ld, steps, labels, edt):
     """Round 5: the persistent ring kernel behind ptd_syrk_accumulate / ptd_syrk_accumulate_multi (bf16 activations):
     both tile sizes, both accumulator dtypes, the strictly-lower walk and the diagonal pairs, an odd number of tile
     rows (a diagonal tile without a partner), grids below and far above the CU count, the step boundaries inside one
@@ -97,10 +141,12 @@ def test_syrk_bf16_ring_kernel_and_multi_step_entry_are_exact_on_small_integers(
     bigs = [torch.randint(-2, 3, (T, ld), generator=g).to(torch.bfloat16).to(DEV) for _ in range(steps)]
     ys = [b[:, :n] for b in bigs]
     e = torch.full((n, n), 5.0, dtype=edt, device=DEV)
-    if steps == 1:
-        ops.syrk_accumulate(e, ys[0], 2.0)
-    else:
-        ops.syrk_accumulate_multi(e, ys, 2.0)
+    with ops.launch_trace() as trace:
+        if steps == 1:
+            ops.syrk_accumulate(e, ys[0], 2.0)
+        else:
+            ops.syrk_accumulate_multi(e, ys, 2.0)
+    assert list(trace) == labels
     ref = torch.full((n, n), 5.0, dtype=torch.float64, device=DEV)
     for y in ys:
         yi = y.to(torch.float64)
@@ -118,20 +164,28 @@ def test_syrk_multi_step_entry_equals_the_sum_of_single_steps(ops):
     ys = [(torch.randn(T, n, generator=g) * torch.logspace(0, -2, n)).to(torch.bfloat16).to(DEV) for _ in range(D)]
     e0 = torch.randn(n, n, generator=g, dtype=torch.float64).to(DEV)
     a, b = e0.clone(), e0.clone()
-    ops.syrk_accumulate_multi(a, ys, 1.0 / T)
-    for y in ys:
-        ops.syrk_accumulate(b, y, 1.0 / T)
+    with ops.launch_trace() as trace:
+        ops.syrk_accumulate_multi(a, ys, 1.0 / T)
+    assert list(trace) == [RING128]                 # 8 K steps a step, 200 items: the five steps in one launch
+    with ops.launch_trace() as trace:
+        for y in ys:
+            ops.syrk_accumulate(b, y, 1.0 / T)
+    assert list(trace) == [RING128] * D
     assert (torch.tril(a) - torch.tril(b)).abs().max().item() <= 1e-14 * b.abs().max().item()
     assert torch.equal(torch.triu(a, 1), torch.triu(e0, 1))
     ys32 = [y.float() for y in ys]
     a, b = e0.clone(), e0.clone()
-    ops.syrk_accumulate_multi(a, ys32, 1.0 / T)
-    for y in ys32:
-        ops.syrk_accumulate(b, y, 1.0 / T)
+    with ops.launch_trace() as trace:
+        ops.syrk_accumulate_multi(a, ys32, 1.0 / T)
+        for y in ys32:
+            ops.syrk_accumulate(b, y, 1.0 / T)
+    assert list(trace) == [F32_MIXED] * (2 * D)     # 210 tiles >= 192: one K range whatever T
     assert torch.equal(a, b)
     # matrices of different shapes are added one by one
     c = e0.clone()
-    ops.syrk_accumulate_multi(c, [ys[0], ys[1][:256]], 0.5)
+    with ops.launch_trace() as trace:
+        ops.syrk_accumulate_multi(c, [ys[0], ys[1][:256]], 0.5)
+    assert list(trace) == [RING128, RING128]        # (256 rows: 4 K steps, the ring at its shortest)
     d = e0.clone()
     ops.syrk_accumulate(d, ys[0], 0.5)
     ops.syrk_accumulate(d, ys[1][:256], 0.5)
@@ -147,7 +201,9 @@ def test_syrk_matches_oracle_product_in_activation_dtype(ops):
     e = torch.zeros((32, 32), dtype=torch.float64, device=DEV)
     for x in rows:
         y = ops.matmul(x.to(DEV), w.to(DEV).T)
-        ops.syrk_accumulate(e, y, 1.0 / y.shape[0])
+        with ops.launch_trace() as trace:
+            ops.syrk_accumulate(e, y, 1.0 / y.shape[0])
+        assert list(trace) == [F32_MIXED]       # 72 rows a batch: one K range
     err = (_lower(e.cpu()) - _lower(eyyt)).abs().max().item()
     assert err <= 1e-6 * eyyt.abs().max().item()
 
@@ -156,7 +212,9 @@ def test_syrk_strided_rows(ops):
     big = _rand((200, 96), 3).to(DEV)
     y = big[:, :64]  # ldy = 96
     e = torch.zeros((64, 64), dtype=torch.float64, device=DEV)
-    ops.syrk_accumulate(e, y, 0.5)
+    with ops.launch_trace() as trace:
+        ops.syrk_accumulate(e, y, 0.5)
+    assert list(trace) == [F32_SPLITK]      # one tile, 200 rows: two K ranges of 128
     ref = 0.5 * (y.cpu().double().T @ y.cpu().double())
     assert (_lower(e.cpu()) - _lower(ref)).abs().max().item() <= 2e-6 * ref.abs().max().item()
 
