@@ -56,7 +56,10 @@ extern "C" {
                              *    ptd_lowrank_decode_group_q_workspace_bytes, ptd_lowrank_decode_group_q,
                              *    ptd_lowrank_decode_gated_q_workspace_bytes, ptd_lowrank_decode_gated_q,
                              *    ptd_lowrank_skinny_group_q_workspace_bytes, ptd_lowrank_skinny_group_q,
-                             *    ptd_lowrank_skinny_gated_q_workspace_bytes, ptd_lowrank_skinny_gated_q) */
+                             *    ptd_lowrank_skinny_gated_q_workspace_bytes, ptd_lowrank_skinny_gated_q,
+                             *    ptd_mxfp8_quantize_rows, ptd_mx_product_a8,
+                             *    ptd_lowrank_a8_w4_workspace_bytes, ptd_lowrank_a8_w4,
+                             *    ptd_lowrank_a8_w6_workspace_bytes, ptd_lowrank_a8_w6) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -637,6 +640,56 @@ int ptd_lowrank_tile_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                         const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
                         const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
                         void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+
+/* MXFP8 activations on the block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4): OPT-IN entries beside the ones above,
+ * because quantising the activations changes numerics.  D = bf16 / f16.
+ *
+ * Q8 of a row of n values of D, n a multiple of 32, per block of 32 consecutive elements with m = max |v_j|:
+ *   s = clamp(floor(log2 m) - 8 + 127, 0, 254) (0 for an all-zero block), the e8m0 scale byte;
+ *   code_j = e4m3fn (OCP), round to nearest even, of clamp(v_j 2^(127 - s), -448, 448); value_j = val(code_j) 2^(s - 127).
+ * A block whose scaled maximum lies in (464, 512) saturates, as OCP MX specifies.  Finite inputs only: an Inf becomes
+ * +-448 2^120 and a NaN -448 2^(s - 127), neither is propagated.
+ *
+ * ptd_mxfp8_quantize_rows: x [T, n] of D (pitch ldx elements) -> codes [T, n] bytes (pitch ldc) and scales [T, n / 32]
+ * bytes (pitch lds), bit for bit Q8.  One launch, a lane per block.  Served: bf16 / f16, n a positive multiple of 32
+ * below 2^30, x 16-byte aligned with ldx a multiple of 8, codes 16-byte aligned with ldc a multiple of 16, T <= 2^24 and
+ * T n < 2^40; anything else PTD_ERR_UNSUPPORTED, null pointers / T < 1 / short pitches PTD_ERR_INVALID.
+ *
+ * ptd_mx_product_a8: out [T, N] (pitch ldo elements) = round_D(Xq^ W^^T + bias) in one launch, with Xq^ the values of
+ * (xq [T, K] codes, ex [T, K / 32] scales) and W^ [N, K] the MXFP4 (q_format PTD_Q_MXFP4; Wq [N, K / 2]) or MXFP6 e2m3
+ * (PTD_Q_MXFP6_E2M3; Wq [N, 3 K / 4]) factor of ptd_lowrank_decode_w4 / _w6, its scale bytes ew [N, K / 32] clamped to
+ * [114, 140] / [116, 140] before they reach the instruction.  Sums in f32 across the K steps; inside a step the
+ * instruction aligns its 128 products before it adds them and is coarser than an f32 sum (measured: up to 2^-15 of
+ * sum |a b|; exact where the products share a grid),
+ * one accumulator per output over the whole of K in ascending steps of 128: row t of out depends on row t of xq alone
+ * and is the same bits at every T.  Served: bf16 / f16 (out and bias), K a positive multiple of 32 (not of 128: lanes
+ * beyond K feed zero codes), any N >= 1 below 2^30, xq 16-byte aligned with ldxq a multiple of 16, Wq 8-byte aligned with
+ * ldw a multiple of 8, bias 2-byte aligned and optional, T <= 2^24, T max(K, N) < 2^40.
+ *
+ * ptd_lowrank_a8_w4 / _w6 (arguments of ptd_lowrank_tile_w4 / _w6):
+ *   h = round_D(Q8(x) A^^T)        y = round_D(Q8(h) B^^T + bias)
+ * in four launches on the caller's stream -- quantise x, product, quantise h, product -- bit for bit the composition of
+ * the two entries above.  The workspace holds Q8(x), h and Q8(h) (each part 256-aligned):
+ *   align256(T n_i) + align256(T n_i / 32) + align256(2 T r) + align256(T r) + align256(T r / 32)
+ * bytes; nothing outlives the call, no host read, no allocation: the call can be captured in a graph.  Served: the
+ * operands of ptd_lowrank_tile_w4 / _w6 at 1 <= T <= 2^24 with T max(n_i, r, n_o) < 2^40.  Anything else, a wrong w_format
+ * included, returns PTD_ERR_UNSUPPORTED before a kernel is launched; null pointers, a leading dimension below its row
+ * length or a misaligned workspace PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  No reference counterpart. */
+int ptd_mxfp8_quantize_rows(const void* x, int64_t ldx, int64_t T, int64_t n, void* codes, int64_t ldc, void* scales,
+                            int64_t lds, int dtype, void* stream);
+int ptd_mx_product_a8(const void* xq, int64_t ldxq, const void* ex, int64_t ldex, int64_t T, int64_t K,
+                      const void* Wq, int64_t ldw, const void* ew, int64_t ldew, int64_t N, const void* bias,
+                      void* out, int64_t ldo, int dtype, int q_format, void* stream);
+size_t ptd_lowrank_a8_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype);
+int ptd_lowrank_a8_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                      const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
+                      const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
+                      void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+size_t ptd_lowrank_a8_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype);
+int ptd_lowrank_a8_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                      const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
+                      const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
+                      void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 
 /* The gated pair of a decomposed MLP at the same 32 <= T <= 96 tokens in bf16 / f16, y = act(gate(x)) * up(x) (arguments
  * and activations as ptd_lowrank_decode_gated), in three launches on the caller's stream: both first products, both

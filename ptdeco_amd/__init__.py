@@ -9,6 +9,7 @@ from . import dwain  # noqa: F401
 from . import falor  # noqa: F401
 from . import utils  # noqa: F401
 from .lowrank import (LowRankConv1x1, LowRankLinear, LowRankLinearW4, LowRankLinearW6, LowRankLinearW8,  # noqa: F401
-                      lowrank_gated, lowrank_group, lowrank_mlp, quantize_pair, quantize_pairs_in_place)
+                      lowrank_gated, lowrank_group, lowrank_mlp, quantize_pair, quantize_pairs_in_place,
+                      set_pair_activations)
 
 __version__ = "0.1.0"

@@ -37,6 +37,11 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
                                                              ops.lowrank_tile_w6 where ops.lowrank_tile_w6_serves
                                                              (above 96; 17 ... 31 where measured to win),
                                                              else the torch expression on 16-bit copies
+    lowrank_forward_w4a8 / lowrank_forward_w6a8(Tensor x2d, Tensor Aq, Tensor ea, Tensor Bq, Tensor eb, Tensor? bias)
+        -> Tensor                                            the same factors with MXFP8 activations (opt-in, other
+                                                             numerics): ops.lowrank_a8_w4 / _w6 where
+                                                             ops.lowrank_a8_w4_serves / _w6_serves, else the a8 torch
+                                                             expression
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -345,6 +350,92 @@ def lowrank_forward_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq
 @lowrank_forward_w6.register_fake
 def _(x2d, Aq, ea, Bq, eb, bias):
     return _mx_fake("lowrank_forward_w6", lambda n: 3 * n // 4, "Aq [r, 3 n_i / 4], Bq [n_o, 3 r / 4]", x2d, Aq, ea, Bq, eb,
+                    bias)
+
+
+# MXFP8 activations (OCP MX, e4m3 elements, block 32) for the MX pairs on the block-scaled MFMA: the definition the kernels
+# of csrc/lowrank_a8.hip are tested against.
+A8_BLOCK = 32
+E4M3_MAX = 448.0
+
+
+def mxfp8_quantize_rows_reference(v: torch.Tensor):
+    """Q8 of the rows of v [T, n] (bf16 / f16 / f32 values, n a multiple of 32): (codes [T, n], scales [T, n / 32]),
+    uint8.  Per block of 32 consecutive elements with m = max |v_j|: the scale byte s = clamp(floor(log2 m) - 8 + 127,
+    0, 254) (0 for an all-zero block) and the codes round-to-nearest-even e4m3fn of v_j 2^(127 - s), saturated to +-448
+    (clamped BEFORE torch's cast, which turns 465 into NaN) -- so a block whose scaled maximum lies in (464, 512)
+    saturates, as OCP MX specifies.  The value of a code is e4m3(code) 2^(s - 127).  Finite inputs only."""
+    T, n = v.shape
+    if n % A8_BLOCK:
+        raise ValueError(f"mxfp8_quantize_rows_reference: rows of a multiple of {A8_BLOCK} elements, got {n}")
+    b = v.detach().to(torch.float64).reshape(T, n // A8_BLOCK, A8_BLOCK)
+    m = b.abs().amax(dim=-1)
+    _, exponent = torch.frexp(m)             # m = f 2^exponent with 0.5 <= f < 1: floor(log2 m) = exponent - 1
+    s = torch.where(m > 0, (exponent.long() - 1 - 8 + 127).clamp(0, 254), torch.zeros_like(exponent, dtype=torch.long))
+    scaled = torch.ldexp(b, (127 - s)[:, :, None]).clamp(-E4M3_MAX, E4M3_MAX)
+    codes = scaled.to(torch.float32).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes.reshape(T, n).contiguous(), s.to(torch.uint8).contiguous()
+
+
+def mxfp8_dequant(codes: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The values e4m3(code) 2^(s - 127) of MXFP8 rows (codes [T, n], scales [T, n / 32], uint8) in ``dtype``: exact in
+    float32 and float64 wherever the value is a normal number of the type."""
+    T, n = codes.shape
+    vals = codes.view(torch.float8_e4m3fn).to(torch.float64).reshape(T, n // A8_BLOCK, A8_BLOCK)
+    return torch.ldexp(vals, (scales.long() - 127)[:, :, None]).reshape(T, n).to(dtype)
+
+
+def _a8_expression(dequant, x, Aq, ea, Bq, eb, bias):
+    """h = round_D(Q8(x) A^^T), y = round_D(Q8(h) B^^T + bias) in torch, D = x.dtype: the quantised activations and the
+    factors as f32 values (exact), f32 products and sums, h and y rounded once each."""
+    linear = torch.nn.functional.linear
+    h = linear(mxfp8_dequant(*mxfp8_quantize_rows_reference(x)), dequant(Aq, ea, torch.float32)).to(x.dtype)
+    y = linear(mxfp8_dequant(*mxfp8_quantize_rows_reference(h)), dequant(Bq, eb, torch.float32))
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(x.dtype)
+
+
+def lowrank_w4a8_expression(x: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                            bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The semantics of the MXFP4 pair with MXFP8 activations in torch: ``mxfp8_quantize_rows_reference`` on x and on h,
+    ``lowrank_w4_dequant`` on the factors, sums in f32, h and y rounded once each to x.dtype."""
+    return _a8_expression(lowrank_w4_dequant, x, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_w6a8_expression(x: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                            bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """``lowrank_w4a8_expression`` for the MXFP6 (e2m3) factors (``lowrank_w6_dequant``)."""
+    return _a8_expression(lowrank_w6_dequant, x, Aq, ea, Bq, eb, bias)
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_w4a8", mutates_args=())
+def lowrank_forward_w4a8(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                         bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The MXFP4 pair (operands of lowrank_forward_w4) with MXFP8 activations: y = round(Q8(h) B^^T + bias) with
+    h = round(Q8(x2d) A^^T), Q8 the on-the-fly e4m3 / block-32 quantiser -- other numerics than lowrank_forward_w4, by
+    the activation noise (a noise-to-signal ratio near 2e-3 on Gaussian data).  Where ops.lowrank_a8_w4_serves on
+    ptd_lowrank_a8_w4 (the block-scaled MFMA on the stored codes, four launches), elsewhere
+    ``lowrank_w4a8_expression``.  Inference only: no autograd formula."""
+    return _route_q("w4", ("a8",), lowrank_w4a8_expression, x2d, Aq, ea, Bq, eb, bias)
+
+
+@lowrank_forward_w4a8.register_fake
+def _(x2d, Aq, ea, Bq, eb, bias):
+    return _mx_fake("lowrank_forward_w4a8", lambda n: n // 2, "Aq [r, n_i / 2], Bq [n_o, r / 2]", x2d, Aq, ea, Bq, eb, bias)
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_w6a8", mutates_args=())
+def lowrank_forward_w6a8(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                         bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The MXFP6 (e2m3) pair (operands of lowrank_forward_w6) with MXFP8 activations, as lowrank_forward_w4a8: where
+    ops.lowrank_a8_w6_serves on ptd_lowrank_a8_w6, elsewhere ``lowrank_w6a8_expression``.  Inference only."""
+    return _route_q("w6", ("a8",), lowrank_w6a8_expression, x2d, Aq, ea, Bq, eb, bias)
+
+
+@lowrank_forward_w6a8.register_fake
+def _(x2d, Aq, ea, Bq, eb, bias):
+    return _mx_fake("lowrank_forward_w6a8", lambda n: 3 * n // 4, "Aq [r, 3 n_i / 4], Bq [n_o, 3 r / 4]", x2d, Aq, ea, Bq, eb,
                     bias)
 
 

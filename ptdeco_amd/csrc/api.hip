@@ -1017,6 +1017,78 @@ int ptd_lowrank_tile_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, cons
   return lowrank_tile_mx_products(x, ldx, T, n_i, r, n_o, bias, y, ldy, ws, ws_bytes, dtype, stream);
 }
 
+// MXFP8 activations on the block-scaled MFMA (lowrank_a8.hip)
+int ptd_mxfp8_quantize_rows(const void* x, int64_t ldx, int64_t T, int64_t n, void* codes, int64_t ldc, void* scales,
+                            int64_t lds, int dtype, void* stream) {
+  PTD_REQUIRE(x && codes && scales, "ptd_mxfp8_quantize_rows: null pointer");
+  PTD_REQUIRE(T >= 1, "ptd_mxfp8_quantize_rows: T must be positive");
+  PTD_REQUIRE(ldx >= n && ldc >= n && lds >= n / 32, "ptd_mxfp8_quantize_rows: bad leading dimension");
+  if (!lowrank_a8_quantize_serves(x, ldx, T, n, codes, ldc, dtype)) {
+    set_error("ptd_mxfp8_quantize_rows: not served (T=%lld n=%lld dtype=%d: bf16 / f16, n a positive multiple of 32, "
+              "16-byte aligned rows of x and of the codes)", (long long)T, (long long)n, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  return lowrank_a8_quantize(x, ldx, T, n, codes, ldc, scales, lds, dtype, "ptd_mxfp8_quantize_rows",
+                             static_cast<hipStream_t>(stream));
+}
+
+int ptd_mx_product_a8(const void* xq, int64_t ldxq, const void* ex, int64_t ldex, int64_t T, int64_t K, const void* Wq,
+                      int64_t ldw, const void* ew, int64_t ldew, int64_t N, const void* bias, void* out, int64_t ldo,
+                      int dtype, int q_format, void* stream) {
+  PTD_REQUIRE(xq && ex && Wq && ew && out, "ptd_mx_product_a8: null pointer");
+  PTD_REQUIRE(T >= 1, "ptd_mx_product_a8: T must be positive");
+  const int64_t code_w = q_format == PTD_Q_MXFP6_E2M3 ? 3 * (K / 4) : K / 2;      // (an unknown format is refused below)
+  PTD_REQUIRE(ldxq >= K && ldex >= K / 32 && ldw >= code_w && ldew >= K / 32 && ldo >= N,
+              "ptd_mx_product_a8: bad leading dimension");
+  if (!lowrank_a8_product_serves(xq, ldxq, T, K, Wq, ldw, N, bias, dtype, q_format)) {
+    set_error("ptd_mx_product_a8: not served (T=%lld K=%lld N=%lld dtype=%d q_format=%d: bf16 / f16, PTD_Q_MXFP4 / "
+              "PTD_Q_MXFP6_E2M3, K a positive multiple of 32, 16-byte aligned activation code rows, 8-byte aligned weight "
+              "code rows)", (long long)T, (long long)K, (long long)N, dtype, q_format);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  return lowrank_a8_product(xq, ldxq, ex, ldex, T, K, Wq, ldw, ew, ldew, N, bias, out, ldo, dtype, q_format,
+                            static_cast<hipStream_t>(stream));
+}
+
+size_t ptd_lowrank_a8_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype) {
+  (void)n_o, (void)dtype;
+  return lowrank_a8_workspace_bytes(T, n_i, r);
+}
+
+int ptd_lowrank_a8_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                      const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                      int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
+                      int dtype, int w_format, void* stream) {
+  const int rc = q_entry_checks("ptd_lowrank_a8_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o,
+                                y, ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2, true,
+                                lowrank_a8_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                "PTD_W4_MXFP4, 1 <= T <= 2^24, r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
+                                lowrank_a8_workspace_bytes(T, n_i, r));
+  if (rc != PTD_OK) return rc;
+  return lowrank_a8_w4(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
+                       static_cast<hipStream_t>(stream));
+}
+
+size_t ptd_lowrank_a8_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype) {
+  (void)n_o, (void)dtype;
+  return lowrank_a8_workspace_bytes(T, n_i, r);
+}
+
+int ptd_lowrank_a8_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                      const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                      int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
+                      int dtype, int w_format, void* stream) {
+  const int rc = q_entry_checks("ptd_lowrank_a8_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o,
+                                y, ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4), true,
+                                lowrank_a8_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                "PTD_W6_MXFP6_E2M3, 1 <= T <= 2^24, r >= 32, n_i and r multiples of 32, 8-byte aligned code "
+                                "rows",
+                                lowrank_a8_workspace_bytes(T, n_i, r));
+  if (rc != PTD_OK) return rc;
+  return lowrank_a8_w6(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
+                       static_cast<hipStream_t>(stream));
+}
+
 int ptd_lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap) {
   PTD_REQUIRE(out, "ptd_lowrank_plan: null pointer");
   PTD_REQUIRE(cap >= PTD_PLAN_LEN, "ptd_lowrank_plan: out holds %d values, the plan has %d", cap, PTD_PLAN_LEN);

@@ -266,6 +266,30 @@ int lowrank_tile_w6_dequant(const void* Aq, int64_t lda, const void* ea, int64_t
                             const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o, void* ws, int dtype,
                             hipStream_t st);
 
+// lowrank_a8.hip: MXFP8 (e4m3, block 32) activations on the block-scaled MFMA.  The row quantiser (ptd_mxfp8_quantize_rows),
+// the product of MXFP8 activations with an MXFP4 / MXFP6 factor (ptd_mx_product_a8; q_format PTD_Q_MXFP4 / PTD_Q_MXFP6_E2M3)
+// and the pair made of them (ptd_lowrank_a8_w4 / _w6): quantise x, product, quantise h, product, everything between in
+// the workspace.  *_serves: the rule of the entry; the pair's is the tile MX rule on the operands at any T the grids index
+bool lowrank_a8_quantize_serves(const void* x, int64_t ldx, int64_t T, int64_t n, const void* codes, int64_t ldc, int dtype);
+int lowrank_a8_quantize(const void* x, int64_t ldx, int64_t T, int64_t n, void* codes, int64_t ldc, void* scales,
+                        int64_t lds, int dtype, const char* what, hipStream_t st);
+bool lowrank_a8_product_serves(const void* xq, int64_t ldxq, int64_t T, int64_t K, const void* wq, int64_t ldw, int64_t N,
+                               const void* bias, int dtype, int q_format);
+int lowrank_a8_product(const void* xq, int64_t ldxq, const void* ex, int64_t ldex, int64_t T, int64_t K, const void* wq,
+                       int64_t ldw, const void* ew, int64_t ldew, int64_t N, const void* bias, void* out, int64_t ldo,
+                       int dtype, int q_format, hipStream_t st);
+size_t lowrank_a8_workspace_bytes(int64_t T, int64_t n_i, int64_t r);
+bool lowrank_a8_w4_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
+                          int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias);
+bool lowrank_a8_w6_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
+                          int64_t ldx, const void* Aq, int64_t lda, const void* Bq, int64_t ldb, const void* bias);
+int lowrank_a8_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea,
+                  int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
+                  const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
+int lowrank_a8_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea,
+                  int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
+                  const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
+
 // lowrank_plan.hip: what a launch of one serving family would do, from the host rules the launchers call (ptd_lowrank_plan);
 // fills out[PTD_PLAN_*], PTD_OK or PTD_ERR_UNSUPPORTED
 int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out);

@@ -20,6 +20,7 @@ import logging
 import torch
 
 from . import _torch_ops  # (registers torch.ops.ptdeco_amd.*)
+from . import ops
 
 _lowrank_forward = torch.ops.ptdeco_amd.lowrank_forward.default
 _lowrank_forward_nchw = torch.ops.ptdeco_amd.lowrank_forward_nchw.default
@@ -28,6 +29,8 @@ _lowrank_forward_gated = torch.ops.ptdeco_amd.lowrank_forward_gated.default
 _lowrank_forward_w8 = torch.ops.ptdeco_amd.lowrank_forward_w8.default
 _lowrank_forward_w4 = torch.ops.ptdeco_amd.lowrank_forward_w4.default
 _lowrank_forward_w6 = torch.ops.ptdeco_amd.lowrank_forward_w6.default
+_lowrank_forward_w4a8 = torch.ops.ptdeco_amd.lowrank_forward_w4a8.default
+_lowrank_forward_w6a8 = torch.ops.ptdeco_amd.lowrank_forward_w6a8.default
 _lowrank_forward_group_q = torch.ops.ptdeco_amd.lowrank_forward_group_q.default
 _lowrank_forward_gated_q = torch.ops.ptdeco_amd.lowrank_forward_gated_q.default
 
@@ -171,17 +174,30 @@ _W4_FORMAT = "mxfp4"
 _W6_FORMAT = "mxfp6_e2m3"
 _MX_BLOCK = _torch_ops.W4_BLOCK      # (= W6_BLOCK: weights per scale byte, whatever the element type)
 _QUANT_FORMATS = tuple(_W8_FORMATS) + (_W4_FORMAT, _W6_FORMAT)
+_ACTIVATIONS = ("16bit", "mxfp8")      # what an MX pair feeds the matrix cores beside its weights
+
+
+def _check_activations(who: str, activations) -> str:
+    if activations not in _ACTIVATIONS:
+        raise ValueError(f"{who}: activations must be one of {_ACTIVATIONS}, got {activations!r}")
+    return activations
 
 
 class _LowRankLinearMX(_QuantizedPair):
     """An MX pair whatever the element type: uint8 code rows of ``_code_cols(n)`` bytes per n weights, one e8m0 scale
     byte per block of 32.  A subclass names its format (``_mx_name``, for the messages) and supplies ``_code_cols``,
-    the custom op (``_forward_op``) and the torch expression of the same semantics (``_expression``)."""
+    the custom op (``_forward_op``) and the torch expression of the same semantics (``_expression``).
+
+    ``activations`` ("16bit", the default, or "mxfp8") is a plain attribute, not a buffer: it adds no ``state_dict`` key,
+    and a state dict loads into a module of either setting.  With "mxfp8" the token counts of ``ops.lowrank_a8_takes`` -- 17 to
+    31, the measured class that is won -- call ``_forward_op_a8``, the pair with MXFP8 activations on the block-scaled
+    MFMA; every other token count runs what it runs with "16bit"."""
 
     def __init__(self, in_features: int, rank: int, out_features: int, bias: bool = True,
-                 dtype: torch.dtype = torch.bfloat16, device=None) -> None:
+                 dtype: torch.dtype = torch.bfloat16, device=None, activations: str = "16bit") -> None:
         super().__init__()
         cls = type(self).__name__
+        self.activations = _check_activations(cls, activations)
         if dtype not in _W8_DTYPES:
             raise ValueError(f"{cls}: the activation dtype must be bfloat16 or float16, got {dtype}")
         if in_features % _MX_BLOCK or rank % _MX_BLOCK or rank < _MX_BLOCK or in_features < _MX_BLOCK:
@@ -211,8 +227,15 @@ class _LowRankLinearMX(_QuantizedPair):
                                       "on 16-bit copies of the factors instead")
             return self._expression(x, *operands)
         x2d = x.reshape(-1, self.in_features)
-        y = self._forward_op(x2d, *operands)
+        T = x2d.shape[0]
+        if self.activations == "mxfp8" and ops.lowrank_a8_takes(T):
+            y = self._forward_op_a8(x2d, *operands)
+        else:
+            y = self._forward_op(x2d, *operands)
         return y.reshape(*x.shape[:-1], self.out_features)
+
+    def extra_repr(self) -> str:
+        return f"{super().extra_repr()}, activations={self.activations}"
 
 
 class LowRankLinearW4(_LowRankLinearMX):
@@ -244,10 +267,22 @@ class LowRankLinearW4(_LowRankLinearMX):
     noise-to-signal ratio of about 2.5e-2 on Gaussian factors, against 1.4e-3 for fp8 -- so it is meant to be chosen
     layer by layer (``quantize_pairs_in_place(model, "mxfp4", names=...)``).  ``.to(device)`` moves the module; a dtype
     cast (``.half()``, ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the packed buffers
-    as they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place``, or empty for ``load_state_dict``."""
+    as they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place``, or empty for ``load_state_dict``.
+
+    ``activations="mxfp8"`` (opt-in; the constructor, ``quantize_pair(..., activations=)`` or
+    ``set_pair_activations``) sends 17 to 31 tokens (``ops.lowrank_a8_takes``; above the skinny cap the a8 entry is
+    measured slower than the tile pair in every cell, so those token counts keep it) to
+    ``torch.ops.ptdeco_amd.lowrank_forward_w4a8`` instead: x and h are quantised on the fly to MXFP8 (e4m3 codes, one
+    e8m0 scale per 32 elements) and both products run on v_mfma_scale_f32_16x16x128_f8f6f4 straight from the stored
+    codes (ptd_lowrank_a8_w4).  That changes numerics: THE TOKEN COUNTS THAT TAKE THIS PATH AND THE
+    OTHERS (decode among them) THEN DIFFER BY THE ACTIVATION NOISE (a noise-to-signal ratio near 2e-3 on Gaussian
+    data, an order of magnitude below the weight format's own).  ``lowrank_group`` and ``lowrank_gated(quantized="fused")``
+    ignore the option: they serve 1 to 16 and 32 to 96 tokens only, so nothing collides."""
 
     _mx_name = _q_fmt = "MXFP4"
+    _skinny_cap = "_SKINNY_W4_MAX_T"
     _forward_op = staticmethod(_lowrank_forward_w4)
+    _forward_op_a8 = staticmethod(_lowrank_forward_w4a8)
     _expression = staticmethod(_torch_ops.lowrank_w4_expression)
 
     @staticmethod
@@ -285,10 +320,18 @@ class LowRankLinearW6(_LowRankLinearMX):
     keeps fp8's three mantissa bits: round to nearest gives a noise-to-signal ratio of about 1.6e-3 on Gaussian
     factors, fp8's class (1.3 .. 1.5e-3) and a sixteenth of MXFP4's.  ``.to(device)`` moves the module; a dtype cast
     (``.half()``, ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the packed buffers as
-    they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place`` with ``"mxfp6_e2m3"``, or empty for ``load_state_dict``."""
+    they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place`` with ``"mxfp6_e2m3"``, or empty for ``load_state_dict``.
+
+    ``activations="mxfp8"`` (opt-in, as on ``LowRankLinearW4``) sends 17 to 31 tokens to
+    ``torch.ops.ptdeco_amd.lowrank_forward_w6a8`` (ptd_lowrank_a8_w6: MXFP8 activations on the block-scaled
+    MFMA).  Those token counts and the others then differ by the activation noise (a noise-to-signal ratio near 2e-3 on Gaussian
+    data, the class of the weight format's own); ``lowrank_group`` and ``lowrank_gated(quantized="fused")`` ignore the
+    option."""
 
     _mx_name = _q_fmt = "MXFP6"
+    _skinny_cap = "_SKINNY_W6_MAX_T"
     _forward_op = staticmethod(_lowrank_forward_w6)
+    _forward_op_a8 = staticmethod(_lowrank_forward_w6a8)
     _expression = staticmethod(_torch_ops.lowrank_w6_expression)
 
     @staticmethod
@@ -380,7 +423,7 @@ def _quantize_mxfp6_e2m3(w: torch.Tensor):
     return _torch_ops.lowrank_w6_pack(codes.reshape(rows, cols)), (e + 127).to(torch.uint8).contiguous()
 
 
-def _quantize_pair_mx(first, second, dtype, cls, quantize, name):
+def _quantize_pair_mx(first, second, dtype, cls, quantize, name, activations="16bit"):
     n_i, r, n_o = first.in_features, first.out_features, second.out_features
     if n_i % _MX_BLOCK:
         raise ValueError(f"quantize_pair: {name} needs in_features to be a multiple of {_MX_BLOCK}, got {n_i}")
@@ -389,21 +432,22 @@ def _quantize_pair_mx(first, second, dtype, cls, quantize, name):
     if stored != r:
         wa = torch.cat([wa, wa.new_zeros(stored - r, n_i)], 0)
         wb = torch.cat([wb, wb.new_zeros(n_o, stored - r)], 1)
-    out = cls(n_i, stored, n_o, bias=second.bias is not None, dtype=dtype, device=first.weight.device)
+    out = cls(n_i, stored, n_o, bias=second.bias is not None, dtype=dtype, device=first.weight.device,
+              activations=activations)
     out.weight_a_q, out.scale_a = quantize(wa)
     out.weight_b_q, out.scale_b = quantize(wb)
     return out
 
 
-def _quantize_pair_mxfp4(first, second, dtype) -> LowRankLinearW4:
-    return _quantize_pair_mx(first, second, dtype, LowRankLinearW4, _quantize_mxfp4, "mxfp4")
+def _quantize_pair_mxfp4(first, second, dtype, activations="16bit") -> LowRankLinearW4:
+    return _quantize_pair_mx(first, second, dtype, LowRankLinearW4, _quantize_mxfp4, "mxfp4", activations)
 
 
-def _quantize_pair_mxfp6(first, second, dtype) -> LowRankLinearW6:
-    return _quantize_pair_mx(first, second, dtype, LowRankLinearW6, _quantize_mxfp6_e2m3, "mxfp6_e2m3")
+def _quantize_pair_mxfp6(first, second, dtype, activations="16bit") -> LowRankLinearW6:
+    return _quantize_pair_mx(first, second, dtype, LowRankLinearW6, _quantize_mxfp6_e2m3, "mxfp6_e2m3", activations)
 
 
-def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3"):
+def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3", *, activations: str = "16bit"):
     """An installed ``LowRankLinear`` with bf16 or f16 weights as a ``LowRankLinearW8``: each factor row stored as
     float8_e4m3fn values times one f32 scale (s = amax|row| / 448, round to nearest), the bias as it is.  Every
     element satisfies |w - s q| <= max(2^-4 |w|, 2^-10 s).  With ``fmt="mxfp4"`` a ``LowRankLinearW4`` instead: OCP MXFP4
@@ -412,9 +456,15 @@ def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3"):
     noise-to-signal ratio near 2.5e-2 on Gaussian factors, so a format to choose layer by layer.  With
     ``fmt="mxfp6_e2m3"`` a ``LowRankLinearW6``: OCP MXFP6 blocks of 32 e2m3 weights (``_quantize_mxfp6_e2m3``:
     |w - w^| <= amax_block / 8 where the block exponent is not clamped), the same shape rules, 0.39 of the 16-bit pair's
-    bytes at a noise-to-signal ratio near 1.6e-3, fp8's class.  The pair itself is not modified."""
+    bytes at a noise-to-signal ratio near 1.6e-3, fp8's class.  ``activations="mxfp8"`` (MX formats only; the fp8
+    pair's f32 row scales have no place in the block-scaled instruction) opts the new module into MXFP8 activations
+    at prefill sizes (``LowRankLinearW4``).  The pair itself is not modified."""
     if fmt not in _QUANT_FORMATS:
         raise ValueError(f"quantize_pair: fmt must be one of {sorted(_QUANT_FORMATS)}, got {fmt!r}")
+    _check_activations("quantize_pair", activations)
+    if activations != "16bit" and fmt not in (_W4_FORMAT, _W6_FORMAT):
+        raise ValueError(f"quantize_pair: activations={activations!r} needs an MX format ({_W4_FORMAT!r} or "
+                         f"{_W6_FORMAT!r}), got {fmt!r}")
     if not isinstance(pair, LowRankLinear):
         raise TypeError(f"quantize_pair: expected an installed LowRankLinear, got {type(pair).__name__}")
     first, second = pair[0], pair[1]
@@ -423,7 +473,7 @@ def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3"):
         raise ValueError(f"quantize_pair: the pair's weights must be bfloat16 or float16 (got {dtype} / "
                          f"{second.weight.dtype}); cast the model first -- the fp8, mxfp4 and mxfp6 kernels take 16-bit activations")
     if fmt in (_W4_FORMAT, _W6_FORMAT):
-        out = (_quantize_pair_mxfp4 if fmt == _W4_FORMAT else _quantize_pair_mxfp6)(first, second, dtype)
+        out = (_quantize_pair_mxfp4 if fmt == _W4_FORMAT else _quantize_pair_mxfp6)(first, second, dtype, activations)
         if second.bias is not None:
             out.bias = second.bias.detach().to(dtype).clone()
         return out.train(pair.training)
@@ -437,15 +487,19 @@ def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3"):
     return out.train(pair.training)
 
 
-def quantize_pairs_in_place(model: torch.nn.Module, fmt: str = "fp8_e4m3", names=None) -> list:
+def quantize_pairs_in_place(model: torch.nn.Module, fmt: str = "fp8_e4m3", names=None, *,
+                            activations: str = "16bit") -> list:
     """Replace the installed ``LowRankLinear`` modules of ``model`` whose weights are bf16 or f16 -- all of them, or
     those listed in ``names`` -- by their ``quantize_pair`` in ``fmt`` ("fp8_e4m3", "mxfp4" or "mxfp6_e2m3"); returns the replaced
     names in module order.  To be applied
     after ``apply_decompose_config_in_place`` and ``load_state_dict`` (the config and the 16-bit state dict describe
     the unquantised pairs).  ``LowRankConv1x1``, ``nn.Linear`` and everything else stay as they are; a name in ``names``
-    that is not such a pair raises."""
+    that is not such a pair raises.  ``activations`` is handed to ``quantize_pair``."""
     if fmt not in _QUANT_FORMATS:
         raise ValueError(f"quantize_pairs_in_place: fmt must be one of {sorted(_QUANT_FORMATS)}, got {fmt!r}")
+    _check_activations("quantize_pairs_in_place", activations)
+    if activations != "16bit" and fmt not in (_W4_FORMAT, _W6_FORMAT):
+        raise ValueError(f"quantize_pairs_in_place: activations={activations!r} needs an MX format, got {fmt!r}")
     modules = dict(model.named_modules())
     if names is not None:
         names = list(names)
@@ -459,8 +513,28 @@ def quantize_pairs_in_place(model: torch.nn.Module, fmt: str = "fp8_e4m3", names
         if names is None and mod[0].weight.dtype not in _W8_DTYPES:
             continue
         parent, _, leaf = name.rpartition(".")
-        setattr(modules[parent], leaf, quantize_pair(mod, fmt))
+        setattr(modules[parent], leaf, quantize_pair(mod, fmt, activations=activations))
         done.append(name)
+    return done
+
+
+def set_pair_activations(model: torch.nn.Module, activations: str, names=None) -> list:
+    """Set ``activations`` ("mxfp8" or "16bit") on the ``LowRankLinearW4`` / ``LowRankLinearW6`` modules of ``model`` --
+    all of them (``model`` itself included), or those listed in ``names`` -- and return their names in module order: the
+    way to opt an already built or loaded model in or out (the choice is an attribute, not a buffer; a state dict does
+    not carry it).  A name in ``names`` that is not such a module raises."""
+    _check_activations("set_pair_activations", activations)
+    modules = dict(model.named_modules())
+    if names is not None:
+        names = list(names)
+        for name in names:
+            if not isinstance(modules.get(name), _LowRankLinearMX):
+                raise ValueError(f"set_pair_activations: {name!r} is not a LowRankLinearW4 / LowRankLinearW6 of the model")
+    done = []
+    for name, mod in modules.items():
+        if isinstance(mod, _LowRankLinearMX) and (names is None or name in names):
+            mod.activations = activations
+            done.append(name)
     return done
 
 

@@ -606,7 +606,7 @@ def _q_call(fmt: _QFormat, regime: str, x2d, Aq, ea, Bq, eb, bias) -> torch.Tens
     y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
     lib = _hip.load()
     entry = f"ptd_lowrank_{regime}_{fmt.tag}"
-    shape = (T, n_i, r, n_o) if regime == "tile" else (T, n_i, r)      # (the tile entry holds both factors too)
+    shape = (T, n_i, r, n_o) if regime in ("tile", "a8") else (T, n_i, r)      # (the tile entry holds both factors too)
     ws_bytes = getattr(lib, entry + "_workspace_bytes")(*shape, _code(x2d))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
     a = (Aq.data_ptr(), Aq.stride(0), ea.data_ptr()) + ((ea.stride(0),) if fmt.scale_rank == 2 else ())
@@ -1191,6 +1191,124 @@ def lowrank_tile_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: t
     workspace (exactly), the 16-bit tile pair runs on them.  The bits of ``lowrank_forward(x2d, A^, B^, bias)``.
     Operands the C entry does not serve raise."""
     return _q_call(_MXFP6, "tile", x2d, Aq, ea, Bq, eb, bias)
+
+
+# MXFP8 activations on the block-scaled MFMA (csrc/lowrank_a8.hip).  OPT-IN (``activations="mxfp8"`` on a LowRankLinearW4 /
+# W6, ``torch.ops.ptdeco_amd.lowrank_forward_w4a8`` / ``_w6a8``): x and h are quantised on the fly to e4m3 codes with one
+# e8m0 scale per 32 elements (Q8, ``_torch_ops.mxfp8_quantize_rows_reference``) and the products run on
+# v_mfma_scale_f32_16x16x128_f8f6f4 straight from the stored weight codes.  ptd_lowrank_a8_w4 / _w6 serve the operands of
+# the tile MX entries at every T; the Python rule sends them the token counts an opted-in module has no decode or skinny
+# kernel for (17 ... 31 and above the format's skinny cap), less the class of cells measured as lost
+# (profiles/pair_a8.json, ``lowrank_a8_takes``: everything above the cap, which keeps the tile entries).  PTD_LOWRANK_A8=0 sends an opted-in module's calls through the a8 torch
+# expression instead.  The family has its own rule; ``_QFormat.pitch`` has no key for it.
+_A8 = os.environ.get("PTD_LOWRANK_A8", "1") != "0"
+_A8_MAX_T = 1 << 24
+_A8_MAX_CELLS = 1 << 40
+
+
+def _a8_operands(fmt: _QFormat, x: _Facts, Aq: _Facts, ea: _Facts, Bq: _Facts, eb: _Facts, bias: Optional[_Facts]) -> bool:
+    """The rule of ptd_lowrank_a8_<tag> on plain facts: the operands of the tile MX entry at the sizes the a8 grids index
+    (T <= 2^24, T max(n_i, r, n_o) < 2^40)."""
+    if not _q_operands(fmt, "tile", x, Aq, ea, Bq, eb, bias):
+        return False
+    (T, n_i), r, n_o = x.shape, Aq.shape[0], Bq.shape[0]
+    return T <= _A8_MAX_T and T * max(n_i, r, n_o) < _A8_MAX_CELLS
+
+
+def lowrank_a8_takes(T: int) -> bool:
+    """The token counts an opted-in module sends to the a8 operator, among those the decode and skinny kernels do not
+    serve (17 ... 31 and above the skinny cap): the measured class that is won (profiles/pair_a8.json).  17 ... 31: every
+    measured cell, at 0.17-0.43 of today's path.  Above the cap every measured cell is LOST -- the products load straight
+    from global memory with one K step in flight per wave and take 1.8-5.5 times the tile pair's time at T = 128 ... 2048
+    on the Llama-3-8B-width layers, 1.1-2.6 times on layers of 512 to 2048 (profiles/pair_a8_narrow.json) -- so those T
+    keep today's path.  (The C entries serve them all the same.)  A plain comparison on integers: the modules call this
+    under torch.compile."""
+    return _TILE_MX_MIN_T <= T < _SKINNY_MIN_T
+
+
+def _a8_takes(fmt: _QFormat, T: int, n_i: int, r: int, n_o: int) -> bool:
+    return lowrank_a8_takes(T)
+
+
+def _a8_rule(fmt: _QFormat, x: _Facts, Aq: _Facts, ea: _Facts, Bq: _Facts, eb: _Facts, bias: Optional[_Facts]) -> bool:
+    return _a8_operands(fmt, x, Aq, ea, Bq, eb, bias) and _a8_takes(fmt, x.shape[0], x.shape[1], Aq.shape[0], Bq.shape[0])
+
+
+def _a8_serves(fmt: _QFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
+    if not _A8:
+        return False
+    f = _facts(x2d, Aq, ea, Bq, eb, bias)
+    return f is not None and _a8_rule(fmt, *f)
+
+
+def mxfp8_quantize_rows(x: torch.Tensor):
+    """Q8 of the rows of x [T, n] (bf16 / f16 on a ROCm device, n a multiple of 32): (codes [T, n], scales [T, n / 32]),
+    both uint8 -- per block of 32 the e8m0 byte clamp(floor(log2 amax) - 8 + 127, 0, 254) and the e4m3fn codes of the
+    scaled values, round to nearest even, saturated to +-448: ptd_mxfp8_quantize_rows, bit for bit
+    ``_torch_ops.mxfp8_quantize_rows_reference``.  Finite inputs only."""
+    _dev(x)
+    x = _rows2d(x)
+    assert x.dtype in (torch.bfloat16, torch.float16) and x.shape[0] >= 1 and x.shape[1] >= 32 and x.shape[1] % 32 == 0
+    T, n = x.shape
+    codes = torch.empty((T, n), dtype=torch.uint8, device=x.device)
+    scales = torch.empty((T, n // 32), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _hip.load().ptd_mxfp8_quantize_rows(x.data_ptr(), x.stride(0), T, n, codes.data_ptr(), n, scales.data_ptr(),
+                                                 n // 32, _code(x), _stream(x))
+    _hip.check(rc, "ptd_mxfp8_quantize_rows")
+    return codes, scales
+
+
+def mx_product_a8(xq: torch.Tensor, ex: torch.Tensor, Wq: torch.Tensor, ew: torch.Tensor, bias: Optional[torch.Tensor],
+                  dtype: torch.dtype, fmt) -> torch.Tensor:
+    """round_D(Xq^ W^^T + bias) [T, N] in D = ``dtype`` (bf16 / f16): Xq^ the MXFP8 values of (xq [T, K] codes, ex
+    [T, K / 32] scales: ``mxfp8_quantize_rows``), W^ [N, K] the factor of format ``fmt`` ("MXFP4": Wq [N, K / 2], "MXFP6":
+    Wq [N, 3 K / 4]; ew [N, K / 32]) as ``lowrank_decode_w4`` / ``_w6`` define it, clamp included: ptd_mx_product_a8, one
+    launch on the block-scaled MFMA, sums in f32, rounded once.  Row t depends on row t of xq alone."""
+    fmt = _q_format(fmt)
+    assert fmt.scale_rank == 2, "mx_product_a8 takes the MX formats"
+    _dev(xq, ex, Wq, ew, bias)
+    xq, ex, Wq, ew = _rows2d(xq), _rows2d(ex), _rows2d(Wq), _rows2d(ew)
+    assert all(t.dtype == torch.uint8 for t in (xq, ex, Wq, ew)) and dtype in (torch.bfloat16, torch.float16)
+    (T, K), N = xq.shape, Wq.shape[0]
+    assert T >= 1 and K >= 32 and K % 32 == 0 and ex.shape == (T, K // 32)
+    assert Wq.shape == (N, fmt.row_bytes(K)) and ew.shape == (N, K // 32)
+    bias = None if bias is None else bias.to(dtype).contiguous()
+    out = torch.empty((T, N), dtype=dtype, device=xq.device)
+    with torch.cuda.device(xq.device):
+        rc = _hip.load().ptd_mx_product_a8(xq.data_ptr(), xq.stride(0), ex.data_ptr(), ex.stride(0), T, K, Wq.data_ptr(),
+                                           Wq.stride(0), ew.data_ptr(), ew.stride(0), N, _ptr(bias), out.data_ptr(), N,
+                                           _DT[dtype], _Q_CODES[fmt.name], _stream(xq))
+    _hip.check(rc, "ptd_mx_product_a8")
+    return out
+
+
+def lowrank_a8_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                         bias: Optional[torch.Tensor]) -> bool:
+    """Whether the a8 operator runs ``lowrank_a8_w4`` on these operands as they lie (without loading the library): the
+    operands of ``lowrank_tile_w4`` in the cells of ``lowrank_a8_takes``."""
+    return _a8_serves(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_a8_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                  bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """round(Q8(h) B^^T + bias) with h = round(Q8(x2d) A^^T) for any number of rows of x2d (bf16 / f16), A^ and B^ the
+    MXFP4 factors of ``lowrank_decode_w4``, Q8 the MXFP8 row quantiser: ptd_lowrank_a8_w4, four launches (quantise,
+    product, quantise, product) -- bit for bit ``mxfp8_quantize_rows`` and ``mx_product_a8`` composed.  Row t of the
+    result depends on row t of x2d alone, whatever T.  Operands the C entry does not serve raise."""
+    return _q_call(_MXFP4, "a8", x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_a8_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                         bias: Optional[torch.Tensor]) -> bool:
+    """``lowrank_a8_w4_serves`` for the MXFP6 (e2m3) factors of ``lowrank_tile_w6``."""
+    return _a8_serves(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_a8_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                  bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """``lowrank_a8_w4`` for the MXFP6 (e2m3) factors of ``lowrank_decode_w6``: ptd_lowrank_a8_w6."""
+    return _q_call(_MXFP6, "a8", x2d, Aq, ea, Bq, eb, bias)
 
 
 # The gated pair of an MLP at small batches, act(gate(x)) * up(x), runs on ptd_lowrank_skinny_gated: three launches (both
