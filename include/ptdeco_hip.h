@@ -59,7 +59,10 @@ extern "C" {
                              *    ptd_lowrank_skinny_gated_q_workspace_bytes, ptd_lowrank_skinny_gated_q,
                              *    ptd_mxfp8_quantize_rows, ptd_mx_product_a8,
                              *    ptd_lowrank_a8_w4_workspace_bytes, ptd_lowrank_a8_w4,
-                             *    ptd_lowrank_a8_w6_workspace_bytes, ptd_lowrank_a8_w6) */
+                             *    ptd_lowrank_a8_w6_workspace_bytes, ptd_lowrank_a8_w6,
+                             *    ptd_mx_product_a8_tile,
+                             *    ptd_lowrank_a8_tile_w4_workspace_bytes, ptd_lowrank_a8_tile_w4,
+                             *    ptd_lowrank_a8_tile_w6_workspace_bytes, ptd_lowrank_a8_tile_w6) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -687,6 +690,41 @@ int ptd_lowrank_a8_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                       void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 size_t ptd_lowrank_a8_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype);
 int ptd_lowrank_a8_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                      const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
+                      const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
+                      void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+
+/* MXFP8 activations at prefill sizes: the same mathematics on an LDS-staged tiled GEMM.  OPT-IN, as the entries above.
+ *
+ * ptd_mx_product_a8_tile: ptd_mx_product_a8 with the mapping of a GEMM -- a workgroup of four waves owns a tile of BN
+ * weight rows x BT tokens, (BN, BT) one of (128, 128), (64, 128), (64, 64), (32, 64): the first whose grid has 256
+ * workgroups, else the last; the activation codes and scale bytes of a K step of 128 are staged in LDS (two buffers, the
+ * next step's loads issued ahead of this step's MFMAs) and shared by the waves, the weights stream into registers.  One
+ * accumulator per output over the whole of K in ascending steps of 128, no K split, blocks beyond K fed as zero codes
+ * under scale byte 127, bias added in f32, one rounding: out is bit for bit ptd_mx_product_a8's at every shape and under
+ * every tile shape, and row t does not depend on T.  With outq / eout (both or neither) the launch also stores
+ * Q8(out): codes [T, N] bytes (pitch ldoq) and scale bytes [T, N / 32] (pitch ldeo), bit for bit
+ * ptd_mxfp8_quantize_rows of out; out may then be null (the D values are not stored).  Served: what ptd_mx_product_a8
+ * serves, with at least one of out and outq; outq needs N a multiple of 32, 16-byte alignment and ldoq a multiple of 16.
+ * Anything else PTD_ERR_UNSUPPORTED; null operands, outq without eout, T < 1 or short pitches PTD_ERR_INVALID.
+ *
+ * ptd_lowrank_a8_tile_w4 / _w6 (arguments of ptd_lowrank_tile_w4 / _w6): the pair of ptd_lowrank_a8_w4 / _w6 in three
+ * launches on the caller's stream -- quantise x, first product with the quantising epilogue (h leaves it as MXFP8 and
+ * never exists in D), second product -- bit for bit ptd_lowrank_a8_w4 / _w6.  The workspace holds Q8(x) and Q8(h)
+ * (each part 256-aligned):
+ *   align256(T n_i) + align256(T n_i / 32) + align256(T r) + align256(T r / 32)
+ * bytes.  Served and refused exactly as ptd_lowrank_a8_w4 / _w6 (every T >= 1 the grids index). */
+int ptd_mx_product_a8_tile(const void* xq, int64_t ldxq, const void* ex, int64_t ldex, int64_t T, int64_t K,
+                           const void* Wq, int64_t ldw, const void* ew, int64_t ldew, int64_t N, const void* bias,
+                           void* out, int64_t ldo, void* outq, int64_t ldoq, void* eout, int64_t ldeo,
+                           int dtype, int q_format, void* stream);
+size_t ptd_lowrank_a8_tile_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype);
+int ptd_lowrank_a8_tile_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                      const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
+                      const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
+                      void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+size_t ptd_lowrank_a8_tile_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype);
+int ptd_lowrank_a8_tile_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                       const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
                       const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
                       void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);

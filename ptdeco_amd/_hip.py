@@ -41,6 +41,10 @@ _MXFP8_QUANTIZE = (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int6
 # xq, ldxq, ex, ldex, T, K, Wq, ldw, ew, ldew, N, bias, out, ldo, dtype, q_format, stream
 _MX_PRODUCT_A8 = (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                           c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p])
+# xq, ldxq, ex, ldex, T, K, Wq, ldw, ew, ldew, N, bias, out, ldo, outq, ldoq, eout, ldeo, dtype, q_format, stream
+_MX_PRODUCT_A8_TILE = (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                               c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
+                               c_void_p])
 # the 16-bit gated pair: per side A, lda, r, B, ldb, bias; then n_ff, act
 _SIDE16 = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]
 _GATED16 = (c_int, _X + _SIDE16 + _SIDE16 + [c_int64, c_int] + _Y_WS + [c_int, c_void_p])
@@ -146,6 +150,11 @@ SIGNATURES = {
     "ptd_lowrank_a8_w4": _PAIR_MX,
     "ptd_lowrank_a8_w6_workspace_bytes": _TILE_WS,
     "ptd_lowrank_a8_w6": _PAIR_MX,
+    "ptd_mx_product_a8_tile": _MX_PRODUCT_A8_TILE,
+    "ptd_lowrank_a8_tile_w4_workspace_bytes": _TILE_WS,
+    "ptd_lowrank_a8_tile_w4": _PAIR_MX,
+    "ptd_lowrank_a8_tile_w6_workspace_bytes": _TILE_WS,
+    "ptd_lowrank_a8_tile_w6": _PAIR_MX,
     "ptd_lowrank_skinny_gated_workspace_bytes": _GATED_WS,
     "ptd_lowrank_skinny_gated": _GATED16,
     "ptd_lowrank_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),

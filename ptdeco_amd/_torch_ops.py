@@ -42,6 +42,10 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
                                                              numerics): ops.lowrank_a8_w4 / _w6 where
                                                              ops.lowrank_a8_w4_serves / _w6_serves, else the a8 torch
                                                              expression
+    lowrank_forward_w4a8_tile / lowrank_forward_w6a8_tile(same operands) -> Tensor
+                                                             the same semantics at prefill sizes: ops.lowrank_a8_tile_w4 /
+                                                             _w6 where ops.lowrank_a8_tile_w4_serves / _w6_serves, else
+                                                             the a8 torch expression
     lowrank_forward_nchw(Tensor x, Tensor A, Tensor B, Tensor? bias) -> Tensor           ops.lowrank_forward_nchw
     lowrank_backward(Tensor dy, Tensor x2d, Tensor A, Tensor B, bool has_bias, bool[] needs)
         -> (Tensor dx, Tensor dA, Tensor dB, Tensor dbias)                                ops.matmul
@@ -437,6 +441,35 @@ def lowrank_forward_w6a8(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, 
 def _(x2d, Aq, ea, Bq, eb, bias):
     return _mx_fake("lowrank_forward_w6a8", lambda n: 3 * n // 4, "Aq [r, 3 n_i / 4], Bq [n_o, 3 r / 4]", x2d, Aq, ea, Bq, eb,
                     bias)
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_w4a8_tile", mutates_args=())
+def lowrank_forward_w4a8_tile(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                              bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """lowrank_forward_w4a8 -- the same semantics, the same expression -- for prefill sizes: where
+    ops.lowrank_a8_tile_w4_serves on ptd_lowrank_a8_tile_w4 (the products as LDS-staged tiled GEMMs on the block-scaled
+    MFMA, h quantised in the first product's epilogue, three launches; bit for bit ptd_lowrank_a8_w4), elsewhere
+    ``lowrank_w4a8_expression``.  Other numerics than lowrank_forward_w4, by the activation noise.  Inference only."""
+    return _route_q("w4", ("a8_tile",), lowrank_w4a8_expression, x2d, Aq, ea, Bq, eb, bias)
+
+
+@lowrank_forward_w4a8_tile.register_fake
+def _(x2d, Aq, ea, Bq, eb, bias):
+    return _mx_fake("lowrank_forward_w4a8_tile", lambda n: n // 2, "Aq [r, n_i / 2], Bq [n_o, r / 2]", x2d, Aq, ea, Bq, eb, bias)
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_w6a8_tile", mutates_args=())
+def lowrank_forward_w6a8_tile(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                              bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """lowrank_forward_w4a8_tile for the MXFP6 (e2m3) factors: where ops.lowrank_a8_tile_w6_serves on
+    ptd_lowrank_a8_tile_w6, elsewhere ``lowrank_w6a8_expression``.  Inference only."""
+    return _route_q("w6", ("a8_tile",), lowrank_w6a8_expression, x2d, Aq, ea, Bq, eb, bias)
+
+
+@lowrank_forward_w6a8_tile.register_fake
+def _(x2d, Aq, ea, Bq, eb, bias):
+    return _mx_fake("lowrank_forward_w6a8_tile", lambda n: 3 * n // 4, "Aq [r, 3 n_i / 4], Bq [n_o, 3 r / 4]", x2d, Aq, ea, Bq,
+                    eb, bias)
 
 
 # What the grouped and gated operators of quantised members need of a format (``fmt``: the names of ops._Q_FORMATS): the

@@ -1089,6 +1089,66 @@ int ptd_lowrank_a8_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const 
                        static_cast<hipStream_t>(stream));
 }
 
+// MXFP8 activations at prefill sizes: the LDS-staged tiled product and the pair on it (lowrank_a8_tile.hip)
+int ptd_mx_product_a8_tile(const void* xq, int64_t ldxq, const void* ex, int64_t ldex, int64_t T, int64_t K, const void* Wq,
+                           int64_t ldw, const void* ew, int64_t ldew, int64_t N, const void* bias, void* out, int64_t ldo,
+                           void* outq, int64_t ldoq, void* eout, int64_t ldeo, int dtype, int q_format, void* stream) {
+  PTD_REQUIRE(xq && ex && Wq && ew, "ptd_mx_product_a8_tile: null pointer");
+  PTD_REQUIRE(!outq == !eout, "ptd_mx_product_a8_tile: outq and eout go together");
+  PTD_REQUIRE(T >= 1, "ptd_mx_product_a8_tile: T must be positive");
+  const int64_t code_w = q_format == PTD_Q_MXFP6_E2M3 ? 3 * (K / 4) : K / 2;      // (an unknown format is refused below)
+  PTD_REQUIRE(ldxq >= K && ldex >= K / 32 && ldw >= code_w && ldew >= K / 32 && (!out || ldo >= N) &&
+                  (!outq || (ldoq >= N && ldeo >= N / 32)),
+              "ptd_mx_product_a8_tile: bad leading dimension");
+  if (!lowrank_a8_tile_product_serves(xq, ldxq, T, K, Wq, ldw, N, bias, out, outq, ldoq, dtype, q_format)) {
+    set_error("ptd_mx_product_a8_tile: not served (T=%lld K=%lld N=%lld dtype=%d q_format=%d: what ptd_mx_product_a8 serves, "
+              "an output, and for outq N a multiple of 32 with 16-byte aligned code rows)", (long long)T, (long long)K,
+              (long long)N, dtype, q_format);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  return lowrank_a8_tile_product(xq, ldxq, ex, ldex, T, K, Wq, ldw, ew, ldew, N, bias, out, ldo, outq, ldoq, eout, ldeo, dtype,
+                                 q_format, static_cast<hipStream_t>(stream));
+}
+
+size_t ptd_lowrank_a8_tile_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype) {
+  (void)n_o, (void)dtype;
+  return lowrank_a8_tile_workspace_bytes(T, n_i, r);
+}
+
+int ptd_lowrank_a8_tile_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                           int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
+                           int dtype, int w_format, void* stream) {
+  const int rc = q_entry_checks("ptd_lowrank_a8_tile_w4", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb,
+                                n_o, y, ldy, ws, ws_bytes, dtype, w_format, n_i / 2, r / 2, true,
+                                lowrank_a8_w4_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                "PTD_W4_MXFP4, 1 <= T <= 2^24, r >= 32, n_i and r multiples of 32, 8-byte aligned code rows",
+                                lowrank_a8_tile_workspace_bytes(T, n_i, r));
+  if (rc != PTD_OK) return rc;
+  return lowrank_a8_tile_w4(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
+                            static_cast<hipStream_t>(stream));
+}
+
+size_t ptd_lowrank_a8_tile_w6_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype) {
+  (void)n_o, (void)dtype;
+  return lowrank_a8_tile_workspace_bytes(T, n_i, r);
+}
+
+int ptd_lowrank_a8_tile_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                           const void* scale_a, int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* scale_b,
+                           int64_t ldsb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes,
+                           int dtype, int w_format, void* stream) {
+  const int rc = q_entry_checks("ptd_lowrank_a8_tile_w6", x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb,
+                                n_o, y, ldy, ws, ws_bytes, dtype, w_format, 3 * (n_i / 4), 3 * (r / 4), true,
+                                lowrank_a8_w6_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, Bq, ldb, bias),
+                                "PTD_W6_MXFP6_E2M3, 1 <= T <= 2^24, r >= 32, n_i and r multiples of 32, 8-byte aligned code "
+                                "rows",
+                                lowrank_a8_tile_workspace_bytes(T, n_i, r));
+  if (rc != PTD_OK) return rc;
+  return lowrank_a8_tile_w6(x, ldx, T, n_i, Aq, lda, scale_a, ldsa, r, Bq, ldb, scale_b, ldsb, n_o, bias, y, ldy, ws, dtype,
+                            static_cast<hipStream_t>(stream));
+}
+
 int ptd_lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap) {
   PTD_REQUIRE(out, "ptd_lowrank_plan: null pointer");
   PTD_REQUIRE(cap >= PTD_PLAN_LEN, "ptd_lowrank_plan: out holds %d values, the plan has %d", cap, PTD_PLAN_LEN);

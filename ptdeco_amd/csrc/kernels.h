@@ -290,6 +290,23 @@ int lowrank_a8_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void
                   int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
                   const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_a8_tile.hip: the a8 product as an LDS-staged tiled GEMM (ptd_mx_product_a8_tile: D values, their Q8, or both) and
+// the pair on it (ptd_lowrank_a8_tile_w4 / _w6): quantise x, first product with the quantising epilogue, second product.
+// The pair's rule is lowrank_a8_w4_serves / _w6_serves; the results are bit for bit those of lowrank_a8.hip
+bool lowrank_a8_tile_product_serves(const void* xq, int64_t ldxq, int64_t T, int64_t K, const void* wq, int64_t ldw,
+                                    int64_t N, const void* bias, const void* out, const void* outq, int64_t ldoq, int dtype,
+                                    int q_format);
+int lowrank_a8_tile_product(const void* xq, int64_t ldxq, const void* ex, int64_t ldex, int64_t T, int64_t K, const void* wq,
+                            int64_t ldw, const void* ew, int64_t ldew, int64_t N, const void* bias, void* out, int64_t ldo,
+                            void* outq, int64_t ldoq, void* eout, int64_t ldeo, int dtype, int q_format, hipStream_t st);
+size_t lowrank_a8_tile_workspace_bytes(int64_t T, int64_t n_i, int64_t r);
+int lowrank_a8_tile_w4(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea,
+                       int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
+                       const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
+int lowrank_a8_tile_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const void* ea,
+                       int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
+                       const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
+
 // lowrank_plan.hip: what a launch of one serving family would do, from the host rules the launchers call (ptd_lowrank_plan);
 // fills out[PTD_PLAN_*], PTD_OK or PTD_ERR_UNSUPPORTED
 int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out);

@@ -28,6 +28,7 @@
 #include "elem16.h"
 #include "kernels.h"
 #include "lowrank_a8.h"
+#include "lowrank_a8_code.h"
 #include "lowrank_mx.h"
 #include "lowrank_w4.h"
 #include "lowrank_w6.h"
@@ -39,26 +40,7 @@ namespace {
 constexpr int A8_THREADS = 256;
 constexpr unsigned A8_SCALE_ONE = 127;
 
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef u32x4 u32x4_al16 __attribute__((aligned(16)));
-
-// the instruction's format code of a weight trait (cbsz; 0 = e4m3 is the activations' blgp)
-template <typename F>
-struct A8Code;
-template <>
-struct A8Code<MxFp4> {
-  static constexpr int CBSZ = 4;
-  static __device__ __forceinline__ i32x8 operand(const MxFp4::raw w) {
-    return i32x8{(int)w[0], (int)w[1], (int)w[2], (int)w[3], 0, 0, 0, 0};
-  }
-};
-template <>
-struct A8Code<MxFp6> {
-  static constexpr int CBSZ = 2;
-  static __device__ __forceinline__ i32x8 operand(const MxFp6::raw w) {
-    return i32x8{(int)w[0], (int)w[1], (int)w[2], (int)w[3], (int)w[4], (int)w[5], 0, 0};
-  }
-};
+typedef u32x4 u32x4_al16 __attribute__((aligned(16)));      // (A8Code<F>, i32x8: lowrank_a8_code.h)
 
 // ---------------------------------------------------------------------------------------------------- the quantiser
 

@@ -31,6 +31,8 @@ _lowrank_forward_w4 = torch.ops.ptdeco_amd.lowrank_forward_w4.default
 _lowrank_forward_w6 = torch.ops.ptdeco_amd.lowrank_forward_w6.default
 _lowrank_forward_w4a8 = torch.ops.ptdeco_amd.lowrank_forward_w4a8.default
 _lowrank_forward_w6a8 = torch.ops.ptdeco_amd.lowrank_forward_w6a8.default
+_lowrank_forward_w4a8_tile = torch.ops.ptdeco_amd.lowrank_forward_w4a8_tile.default
+_lowrank_forward_w6a8_tile = torch.ops.ptdeco_amd.lowrank_forward_w6a8_tile.default
 _lowrank_forward_group_q = torch.ops.ptdeco_amd.lowrank_forward_group_q.default
 _lowrank_forward_gated_q = torch.ops.ptdeco_amd.lowrank_forward_gated_q.default
 
@@ -174,7 +176,8 @@ _W4_FORMAT = "mxfp4"
 _W6_FORMAT = "mxfp6_e2m3"
 _MX_BLOCK = _torch_ops.W4_BLOCK      # (= W6_BLOCK: weights per scale byte, whatever the element type)
 _QUANT_FORMATS = tuple(_W8_FORMATS) + (_W4_FORMAT, _W6_FORMAT)
-_ACTIVATIONS = ("16bit", "mxfp8")      # what an MX pair feeds the matrix cores beside its weights
+_ACTIVATIONS = ("16bit", "mxfp8", "mxfp8_prefill")      # what an MX pair feeds the matrix cores beside its weights
+_A8_ACTIVATIONS = ("mxfp8", "mxfp8_prefill")
 
 
 def _check_activations(who: str, activations) -> str:
@@ -188,10 +191,12 @@ class _LowRankLinearMX(_QuantizedPair):
     byte per block of 32.  A subclass names its format (``_mx_name``, for the messages) and supplies ``_code_cols``,
     the custom op (``_forward_op``) and the torch expression of the same semantics (``_expression``).
 
-    ``activations`` ("16bit", the default, or "mxfp8") is a plain attribute, not a buffer: it adds no ``state_dict`` key,
+    ``activations`` ("16bit", the default, "mxfp8" or "mxfp8_prefill") is a plain attribute, not a buffer: it adds no ``state_dict`` key,
     and a state dict loads into a module of either setting.  With "mxfp8" the token counts of ``ops.lowrank_a8_takes`` -- 17 to
     31, the measured class that is won -- call ``_forward_op_a8``, the pair with MXFP8 activations on the block-scaled
-    MFMA; every other token count runs what it runs with "16bit"."""
+    MFMA; every other token count runs what it runs with "16bit".  "mxfp8_prefill" does all of that and in addition sends
+    the cells of ``ops.lowrank_a8_tile_takes`` (token counts above the skinny cap, by shape: the measured class that is
+    won) to ``_forward_op_a8_tile``, the same pair on LDS-staged tiled GEMMs; everything else runs what "16bit" runs."""
 
     def __init__(self, in_features: int, rank: int, out_features: int, bias: bool = True,
                  dtype: torch.dtype = torch.bfloat16, device=None, activations: str = "16bit") -> None:
@@ -228,8 +233,11 @@ class _LowRankLinearMX(_QuantizedPair):
             return self._expression(x, *operands)
         x2d = x.reshape(-1, self.in_features)
         T = x2d.shape[0]
-        if self.activations == "mxfp8" and ops.lowrank_a8_takes(T):
+        if self.activations in _A8_ACTIVATIONS and ops.lowrank_a8_takes(T):
             y = self._forward_op_a8(x2d, *operands)
+        elif self.activations == "mxfp8_prefill" and ops.lowrank_a8_tile_takes(self._q_fmt, T, self.in_features, self.rank,
+                                                                              self.out_features):
+            y = self._forward_op_a8_tile(x2d, *operands)
         else:
             y = self._forward_op(x2d, *operands)
         return y.reshape(*x.shape[:-1], self.out_features)
@@ -277,12 +285,20 @@ class LowRankLinearW4(_LowRankLinearMX):
     codes (ptd_lowrank_a8_w4).  That changes numerics: THE TOKEN COUNTS THAT TAKE THIS PATH AND THE
     OTHERS (decode among them) THEN DIFFER BY THE ACTIVATION NOISE (a noise-to-signal ratio near 2e-3 on Gaussian
     data, an order of magnitude below the weight format's own).  ``lowrank_group`` and ``lowrank_gated(quantized="fused")``
-    ignore the option: they serve 1 to 16 and 32 to 96 tokens only, so nothing collides."""
+    ignore the option: they serve 1 to 16 and 32 to 96 tokens only, so nothing collides.
+
+    ``activations="mxfp8_prefill"`` (opt-in in the same places) does everything "mxfp8" does and in addition sends the
+    cells of ``ops.lowrank_a8_tile_takes`` -- token counts above the skinny cap on the shapes measured as won
+    (profiles/pair_a8_tile.json) -- to ``torch.ops.ptdeco_amd.lowrank_forward_w4a8_tile`` (ptd_lowrank_a8_tile_w4: the
+    same mathematics and bits as the a8 entry, the products as LDS-staged tiled GEMMs, h quantised in the first
+    product's epilogue).  THE TOKEN COUNTS ON THIS PATH DIFFER FROM THE OTHERS BY THE SAME ACTIVATION NOISE; every other
+    cell runs what "16bit" runs."""
 
     _mx_name = _q_fmt = "MXFP4"
     _skinny_cap = "_SKINNY_W4_MAX_T"
     _forward_op = staticmethod(_lowrank_forward_w4)
     _forward_op_a8 = staticmethod(_lowrank_forward_w4a8)
+    _forward_op_a8_tile = staticmethod(_lowrank_forward_w4a8_tile)
     _expression = staticmethod(_torch_ops.lowrank_w4_expression)
 
     @staticmethod
@@ -326,12 +342,15 @@ class LowRankLinearW6(_LowRankLinearMX):
     ``torch.ops.ptdeco_amd.lowrank_forward_w6a8`` (ptd_lowrank_a8_w6: MXFP8 activations on the block-scaled
     MFMA).  Those token counts and the others then differ by the activation noise (a noise-to-signal ratio near 2e-3 on Gaussian
     data, the class of the weight format's own); ``lowrank_group`` and ``lowrank_gated(quantized="fused")`` ignore the
-    option."""
+    option.  ``activations="mxfp8_prefill"`` adds the cells of ``ops.lowrank_a8_tile_takes`` above the skinny cap
+    (``torch.ops.ptdeco_amd.lowrank_forward_w6a8_tile``, ptd_lowrank_a8_tile_w6), which then differ from the other token
+    counts by the same activation noise."""
 
     _mx_name = _q_fmt = "MXFP6"
     _skinny_cap = "_SKINNY_W6_MAX_T"
     _forward_op = staticmethod(_lowrank_forward_w6)
     _forward_op_a8 = staticmethod(_lowrank_forward_w6a8)
+    _forward_op_a8_tile = staticmethod(_lowrank_forward_w6a8_tile)
     _expression = staticmethod(_torch_ops.lowrank_w6_expression)
 
     @staticmethod
@@ -458,7 +477,8 @@ def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3", *, activations: st
     |w - w^| <= amax_block / 8 where the block exponent is not clamped), the same shape rules, 0.39 of the 16-bit pair's
     bytes at a noise-to-signal ratio near 1.6e-3, fp8's class.  ``activations="mxfp8"`` (MX formats only; the fp8
     pair's f32 row scales have no place in the block-scaled instruction) opts the new module into MXFP8 activations
-    at prefill sizes (``LowRankLinearW4``).  The pair itself is not modified."""
+    at 17 to 31 tokens, ``activations="mxfp8_prefill"`` also at the prefill cells measured as won (``LowRankLinearW4``;
+    token counts on those paths differ from the others by the activation noise).  The pair itself is not modified."""
     if fmt not in _QUANT_FORMATS:
         raise ValueError(f"quantize_pair: fmt must be one of {sorted(_QUANT_FORMATS)}, got {fmt!r}")
     _check_activations("quantize_pair", activations)
@@ -519,7 +539,7 @@ def quantize_pairs_in_place(model: torch.nn.Module, fmt: str = "fp8_e4m3", names
 
 
 def set_pair_activations(model: torch.nn.Module, activations: str, names=None) -> list:
-    """Set ``activations`` ("mxfp8" or "16bit") on the ``LowRankLinearW4`` / ``LowRankLinearW6`` modules of ``model`` --
+    """Set ``activations`` ("mxfp8", "mxfp8_prefill" or "16bit") on the ``LowRankLinearW4`` / ``LowRankLinearW6`` modules of ``model`` --
     all of them (``model`` itself included), or those listed in ``names`` -- and return their names in module order: the
     way to opt an already built or loaded model in or out (the choice is an attribute, not a buffer; a state dict does
     not carry it).  A name in ``names`` that is not such a module raises."""

@@ -606,7 +606,7 @@ def _q_call(fmt: _QFormat, regime: str, x2d, Aq, ea, Bq, eb, bias) -> torch.Tens
     y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
     lib = _hip.load()
     entry = f"ptd_lowrank_{regime}_{fmt.tag}"
-    shape = (T, n_i, r, n_o) if regime in ("tile", "a8") else (T, n_i, r)      # (the tile entry holds both factors too)
+    shape = (T, n_i, r, n_o) if regime in ("tile", "a8", "a8_tile") else (T, n_i, r)      # (the tile entry holds both factors too)
     ws_bytes = getattr(lib, entry + "_workspace_bytes")(*shape, _code(x2d))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
     a = (Aq.data_ptr(), Aq.stride(0), ea.data_ptr()) + ((ea.stride(0),) if fmt.scale_rank == 2 else ())
@@ -1309,6 +1309,96 @@ def lowrank_a8_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: tor
                   bias: Optional[torch.Tensor]) -> torch.Tensor:
     """``lowrank_a8_w4`` for the MXFP6 (e2m3) factors of ``lowrank_decode_w6``: ptd_lowrank_a8_w6."""
     return _q_call(_MXFP6, "a8", x2d, Aq, ea, Bq, eb, bias)
+
+
+# MXFP8 activations at prefill sizes (csrc/lowrank_a8_tile.hip).  OPT-IN (``activations="mxfp8_prefill"`` on a
+# LowRankLinearW4 / W6, ``torch.ops.ptdeco_amd.lowrank_forward_w4a8_tile`` / ``_w6a8_tile``): the mathematics and the bits of
+# the a8 entries above, with the products as LDS-staged tiled GEMMs and h leaving the first product as MXFP8 (three
+# launches, no h in D).  ptd_lowrank_a8_tile_w4 / _w6 serve the operands of the a8 entries (``_a8_operands``) at every T;
+# the Python rule sends them the cells measured as won against today's path (profiles/pair_a8_tile.json,
+# ``lowrank_a8_tile_takes``).  PTD_LOWRANK_A8_TILE=0 sends the operators' calls through the a8 torch expression instead.
+_A8_TILE = os.environ.get("PTD_LOWRANK_A8_TILE", "1") != "0"
+
+
+def lowrank_a8_tile_takes(fmt, T: int, n_i: int, r: int, n_o: int) -> bool:
+    """The cells an ``activations="mxfp8_prefill"`` module sends to the a8_tile operator: none at the token counts the
+    decode and skinny kernels serve or at 17 ... 31 (the a8 entry's), and above the format's skinny cap the measured
+    class that is won against today's path -- the dequantisation launch and the 16-bit tile pair -- in every round
+    (profiles/pair_a8_tile.json; tests/test_a8_tile_rules_cpu.py holds this rule against that table).  Won: 4 cells of
+    48, MXFP4 at 4096 -> 1024 -> 4096 and 4096 -> 1024 -> 14336 with 128 and 512 tokens, at 0.86-0.97 of today's time;
+    n_o and T between those neighbours are taken with them.  LOST: everything else -- MXFP6 (1.11-3.2 times today's
+    time), r = 256 and n_i = 14336 (the first product has too few row tiles to fill the chip without a K split, and its K
+    loop keeps one step in flight: 1.15-2.4 times), and T = 2048 and 8192 everywhere (1.03-1.9 times: the products reach
+    7-19 % of the fp8 peak, the 16-bit tile pair more of its own).  (The C entries serve every cell all the same, ahead
+    of the a8 entries in all 48.)  ``fmt`` is the format's name ("MXFP4" / "MXFP6") or its ``_QFormat``.  Plain
+    comparisons on integers: the modules call this under torch.compile."""
+    name = fmt if isinstance(fmt, str) else fmt.name
+    return name == "MXFP4" and n_i == 4096 and r == 1024 and 4096 <= n_o <= 14336 and 128 <= T <= 512
+
+
+def _a8_tile_serves(fmt: _QFormat, x2d, Aq, ea, Bq, eb, bias) -> bool:
+    if not _A8_TILE:
+        return False
+    f = _facts(x2d, Aq, ea, Bq, eb, bias)
+    if f is None or not _a8_operands(fmt, *f):
+        return False
+    (T, n_i), r, n_o = f[0].shape, f[1].shape[0], f[3].shape[0]
+    return lowrank_a8_tile_takes(fmt, T, n_i, r, n_o)
+
+
+def mx_product_a8_tile(xq: torch.Tensor, ex: torch.Tensor, Wq: torch.Tensor, ew: torch.Tensor, bias: Optional[torch.Tensor],
+                       dtype: torch.dtype, fmt, quantize: bool = False):
+    """``mx_product_a8`` as an LDS-staged tiled GEMM (ptd_mx_product_a8_tile, one launch): the same operands, the same
+    bits at every shape.  With ``quantize=True`` (N a multiple of 32) the launch also emits Q8 of its rounded output and
+    the call returns ``(out, codes [T, N], scales [T, N / 32])``, the latter two bit for bit
+    ``mxfp8_quantize_rows(out)``."""
+    fmt = _q_format(fmt)
+    assert fmt.scale_rank == 2, "mx_product_a8_tile takes the MX formats"
+    _dev(xq, ex, Wq, ew, bias)
+    xq, ex, Wq, ew = _rows2d(xq), _rows2d(ex), _rows2d(Wq), _rows2d(ew)
+    assert all(t.dtype == torch.uint8 for t in (xq, ex, Wq, ew)) and dtype in (torch.bfloat16, torch.float16)
+    (T, K), N = xq.shape, Wq.shape[0]
+    assert T >= 1 and K >= 32 and K % 32 == 0 and ex.shape == (T, K // 32)
+    assert Wq.shape == (N, fmt.row_bytes(K)) and ew.shape == (N, K // 32)
+    assert not quantize or N % 32 == 0, "the quantising epilogue takes N a multiple of 32"
+    bias = None if bias is None else bias.to(dtype).contiguous()
+    out = torch.empty((T, N), dtype=dtype, device=xq.device)
+    codes = torch.empty((T, N), dtype=torch.uint8, device=xq.device) if quantize else None
+    scales = torch.empty((T, N // 32), dtype=torch.uint8, device=xq.device) if quantize else None
+    with torch.cuda.device(xq.device):
+        rc = _hip.load().ptd_mx_product_a8_tile(xq.data_ptr(), xq.stride(0), ex.data_ptr(), ex.stride(0), T, K,
+                                                Wq.data_ptr(), Wq.stride(0), ew.data_ptr(), ew.stride(0), N, _ptr(bias),
+                                                out.data_ptr(), N, _ptr(codes), N, _ptr(scales), N // 32, _DT[dtype],
+                                                _Q_CODES[fmt.name], _stream(xq))
+    _hip.check(rc, "ptd_mx_product_a8_tile")
+    return (out, codes, scales) if quantize else out
+
+
+def lowrank_a8_tile_w4_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                              bias: Optional[torch.Tensor]) -> bool:
+    """Whether the a8_tile operator runs ``lowrank_a8_tile_w4`` on these operands as they lie (without loading the
+    library): the operands of ``lowrank_a8_w4`` in the cells of ``lowrank_a8_tile_takes``."""
+    return _a8_tile_serves(_MXFP4, x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_a8_tile_w4(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                       bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """``lowrank_a8_w4``, bit for bit, on ptd_lowrank_a8_tile_w4: three launches (quantise x, the first product as a
+    tiled GEMM whose epilogue quantises h, the second product as a tiled GEMM).  Row t of the result depends on row t of
+    x2d alone, whatever T.  Operands the C entry does not serve raise."""
+    return _q_call(_MXFP4, "a8_tile", x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_a8_tile_w6_serves(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                              bias: Optional[torch.Tensor]) -> bool:
+    """``lowrank_a8_tile_w4_serves`` for the MXFP6 (e2m3) factors."""
+    return _a8_tile_serves(_MXFP6, x2d, Aq, ea, Bq, eb, bias)
+
+
+def lowrank_a8_tile_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: torch.Tensor, eb: torch.Tensor,
+                       bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """``lowrank_a8_tile_w4`` for the MXFP6 (e2m3) factors: ptd_lowrank_a8_tile_w6, bit for bit ``lowrank_a8_w6``."""
+    return _q_call(_MXFP6, "a8_tile", x2d, Aq, ea, Bq, eb, bias)
 
 
 # The gated pair of an MLP at small batches, act(gate(x)) * up(x), runs on ptd_lowrank_skinny_gated: three launches (both
