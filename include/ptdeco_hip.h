@@ -62,7 +62,8 @@ extern "C" {
                              *    ptd_lowrank_a8_w6_workspace_bytes, ptd_lowrank_a8_w6,
                              *    ptd_mx_product_a8_tile,
                              *    ptd_lowrank_a8_tile_w4_workspace_bytes, ptd_lowrank_a8_tile_w4,
-                             *    ptd_lowrank_a8_tile_w6_workspace_bytes, ptd_lowrank_a8_tile_w6) */
+                             *    ptd_lowrank_a8_tile_w6_workspace_bytes, ptd_lowrank_a8_tile_w6,
+                             *    ptd_nsr_plan) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -864,20 +865,47 @@ int ptd_lowrank_forward_nchw(const void* x, int64_t batch, int64_t n_i, int64_t 
  * for non_channel_dim = all leading dims. */
 /* (ABI 2) The workspace carries the arrival counters of the one-launch reduction: initialise it ONCE with
  * ptd_nsr_workspace_init (any size >= the query for the shapes it will serve); ptd_nsr leaves it initialised, so the
- * same workspace serves any number of stream-ordered calls.  Calls that may overlap need a workspace each. */
+ * same workspace serves any number of stream-ordered calls.  Calls that may overlap need a workspace each.
+ * One row (R = 1) gives NaN, as torch.std of one sample does.  A NaN anywhere in x or y, or an infinity in y, gives NaN, and an
+ * infinity in x alone gives +inf, both as the reference does; the workspace is left initialised all the same, so the
+ * next call on it is right.
+ * Launch labels (ptd_launch_trace_*): "nsr (16-byte loads)" when the partial sums are formed with 16-byte loads,
+ * "nsr (one element per lane)" otherwise. */
 size_t ptd_nsr_workspace_bytes(int64_t R, int64_t C);
+/* Host diagnostic for tests, no device code and no GPU needed: what ptd_nsr would launch for x, y [R, C] of `dtype`,
+ * computed by the functions ptd_nsr itself calls.  `aligned`: non-zero when x and y both lie on 16-byte boundaries.
+ * The 16-byte form serves f32 (4 channels a lane) and bf16 / f16 (8 channels a lane) when C >= 64, C is a multiple of
+ * the lane's channels and both operands are aligned; everything else, f64 included, takes the one-element-per-lane
+ * form.  Writes PTD_NSR_PLAN_LEN values to out (cap = the room in out) and returns PTD_NSR_PLAN_LEN;
+ * PTD_ERR_INVALID for a null out, a cap too small or R, C < 1, PTD_ERR_UNSUPPORTED for an unknown dtype.  The chunk
+ * count of the 16-byte form honours the environment variable PTD_NSR_BLOCKS, read once per process. */
+#define PTD_NSR_PLAN_VEC 0             /* channels a lane loads at once: 4 or 8 in the 16-byte form, 0 otherwise */
+#define PTD_NSR_PLAN_CT 1              /* channels of a column tile (one workgroup): 64 lanes of vec channels, or Ct lanes */
+#define PTD_NSR_PLAN_RT 2              /* row lanes of a workgroup: (lanes of a tile) * Rt <= 256 threads work */
+#define PTD_NSR_PLAN_COLTILES 3        /* grid x of the partial kernel */
+#define PTD_NSR_PLAN_NCHUNK 4          /* grid y of the partial kernel: row chunks, none of them empty */
+#define PTD_NSR_PLAN_ROWS_PER_CHUNK 5  /* rows of every chunk but the last (clamped to INT32_MAX) */
+#define PTD_NSR_PLAN_FINAL_BLOCKS 6    /* workgroups of the final kernel: ceil(C / 64) */
+#define PTD_NSR_PLAN_LEN 7
+int ptd_nsr_plan(int64_t R, int64_t C, int dtype, int aligned, int32_t* out, int cap);
 int ptd_nsr_workspace_init(void* ws, size_t ws_bytes, void* stream);
 int ptd_nsr(const void* x, const void* y, int64_t R, int64_t C, int dtype, double eps, double* out,
             void* ws, size_t ws_bytes, void* stream);
 
 /* out[0] (f64) = mean_b max(KL(t_b || s_b), KL(s_b || t_b)) over softmax(dim=-1) of
- * logits s, t [B, C] (f32, bf16 or f16).  Replaces calc_kl_loss (losses.py:48-63). */
+ * logits s, t [B, C] (f32, bf16 or f16).  Replaces calc_kl_loss (losses.py:48-63).
+ * Computed from log-probabilities (row maximum subtracted, log-sum-exp in f64): finite logits give a finite result,
+ * also where the reference program forms softmax first, lets a probability underflow to 0 and returns NaN.  A row that
+ * holds a NaN or an infinite logit is NaN and makes out[0] NaN. */
 size_t ptd_sym_kl_workspace_bytes(int64_t B);
 int ptd_sym_kl(const void* s, const void* t, int64_t B, int64_t C, int dtype, double* out, void* ws,
                size_t ws_bytes, void* stream);
 
 /* rows[b] (f64) = KL(p_b || q_b) = sum_c p log(p / q) over softmax(dim=-1) of logits q, p [B, C].
- * f32, bf16 or f16.  Replaces calc_kl_divergence(q_logits, p_logits) (losses.py:48-54). */
+ * f32, bf16 or f16.  Replaces calc_kl_divergence(q_logits, p_logits) (losses.py:48-54).
+ * Finite logits give a finite row where the reference program underflows to NaN (see ptd_sym_kl).  A row that holds a
+ * NaN or an infinite logit is NaN; it stays in its own row: every other row of the call is bit for bit what it is
+ * without it. */
 int ptd_kl_rows(const void* q, const void* p, int64_t B, int64_t C, int dtype, double* rows, void* stream);
 
 #ifdef __cplusplus

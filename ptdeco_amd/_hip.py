@@ -162,6 +162,7 @@ SIGNATURES = {
     "ptd_lowrank_forward_nchw": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
                                          c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "ptd_nsr_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "ptd_nsr_plan": (c_int, [c_int64, c_int64, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),
     "ptd_nsr_workspace_init": (c_int, [c_void_p, c_size_t, c_void_p]),
     "ptd_nsr": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_void_p, c_size_t,
                         c_void_p]),

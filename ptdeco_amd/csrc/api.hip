@@ -1229,6 +1229,17 @@ int ptd_lowrank_forward_nchw(const void* x, int64_t batch, int64_t n_i, int64_t 
 
 size_t ptd_nsr_workspace_bytes(int64_t R, int64_t C) { return nsr_workspace_bytes(R, C); }
 
+int ptd_nsr_plan(int64_t R, int64_t C, int dtype, int aligned, int32_t* out, int cap) {
+  PTD_REQUIRE(out, "ptd_nsr_plan: null pointer");
+  PTD_REQUIRE(cap >= PTD_NSR_PLAN_LEN, "ptd_nsr_plan: out holds %d values, the plan has %d", cap, PTD_NSR_PLAN_LEN);
+  PTD_REQUIRE(R >= 1 && C >= 1, "ptd_nsr_plan: bad shape");
+  if (nsr_plan_query(R, C, dtype, aligned != 0, out) != PTD_OK) {
+    set_error("ptd_nsr_plan: unsupported dtype %d", dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  return PTD_NSR_PLAN_LEN;
+}
+
 int ptd_nsr_workspace_init(void* ws, size_t ws_bytes, void* stream) {
   return nsr_workspace_init(ws, ws_bytes, static_cast<hipStream_t>(stream));
 }

@@ -374,6 +374,7 @@ int colsum_accumulate(const void* y, int64_t T, int64_t n, int64_t ldy, int y_dt
                       double scale, hipStream_t st);
 size_t nsr_workspace_bytes(int64_t R, int64_t C);
 int nsr_workspace_init(void* ws, size_t ws_bytes, hipStream_t st);
+int nsr_plan_query(int64_t R, int64_t C, int dtype, bool aligned, int32_t* out);
 int nsr(const void* x, const void* y, int64_t R, int64_t C, int dtype, double eps, double* out, void* ws,
         size_t ws_bytes, hipStream_t st);
 int convert_f32_to_f64(const float* src, int64_t lds, double* dst, int64_t ldd, int64_t rows, int64_t cols, hipStream_t st);

@@ -1492,6 +1492,25 @@ def nsr(x: torch.Tensor, y: torch.Tensor, channels: int, eps: float = 1e-3) -> t
     return out[0]
 
 
+NSR_PLAN_FIELDS = ("vec", "Ct", "Rt", "coltiles", "nchunk", "rows_per_chunk", "final_blocks")   # PTD_NSR_PLAN_*
+
+
+def nsr_plan(R: int, C: int, dtype: torch.dtype, aligned: bool = True) -> dict:
+    """What ``nsr`` would launch for x, y viewed [R, C] of ``dtype`` (ptd_nsr_plan: host only, no GPU needed), as a dict
+    of ``NSR_PLAN_FIELDS``.  ``vec`` is 4 or 8 for the kernel with 16-byte loads (label "nsr (16-byte loads)"), 0 for the
+    one-element-per-lane kernel; ``aligned`` says whether both operands lie on 16-byte boundaries."""
+    try:
+        code = _DT[dtype]
+    except KeyError:
+        raise TypeError(f"unsupported dtype {dtype}") from None
+    out = (ctypes.c_int32 * len(NSR_PLAN_FIELDS))()
+    rc = _hip.load().ptd_nsr_plan(int(R), int(C), code, int(bool(aligned)), out, len(NSR_PLAN_FIELDS))
+    if rc < 0:
+        _hip.check(rc, "ptd_nsr_plan")
+    assert rc == len(NSR_PLAN_FIELDS), rc
+    return dict(zip(NSR_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def drop_cached_workspaces() -> None:
     """Forget the per-(device, stream) ptd_nsr workspaces (they are re-made and re-initialised on the next call).  The
     drivers call this when a metric comes back non-finite: a kernel that was aborted between its partial and its final

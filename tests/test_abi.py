@@ -53,6 +53,21 @@ def test_workspace_queries_and_argument_errors(lib):
     assert rc == -1
 
 
+def test_nsr_plan_query(lib):
+    """ptd_nsr_plan is a host-side function of (R, C, dtype, aligned): which partial kernel ptd_nsr launches and its grid
+    (tests/test_metric_cases_cpu.py has the properties)."""
+    from ptdeco_amd import _hip
+    assert "ptd_nsr_plan" in _declared() and "ptd_nsr_plan" in _hip.SIGNATURES and hasattr(lib, "ptd_nsr_plan")
+    l = _hip.load()
+    out = (ctypes.c_int32 * 7)()
+    assert l.ptd_nsr_plan(4096, 4096, _hip.F32, 1, out, 7) == 7 and out[0] == 4          # 16-byte loads
+    assert l.ptd_nsr_plan(4096, 4096, _hip.F32, 0, out, 7) == 7 and out[0] == 0          # an operand off 16 bytes
+    assert l.ptd_nsr_plan(4096, 4096, _hip.BF16, 1, out, 7) == 7 and out[0] == 8
+    assert l.ptd_nsr_plan(4096, 4096, _hip.F64, 1, out, 7) == 7 and out[0] == 0
+    assert l.ptd_nsr_plan(4096, 4096, _hip.F32, 1, out, 6) == -1 and b"ptd_nsr_plan" in l.ptd_last_error()
+    assert l.ptd_nsr_plan(4096, 4096, 9, 1, out, 7) == -2
+
+
 def test_eigh_route_query(monkeypatch):
     """ptd_eigh_route is a host-side function of (n, k, all_values) and the environment: the filtered subspace iteration
     for at most 2/7 of the spectrum of a large matrix whose eigenvalues below are not wanted, the direct reduction for
