@@ -63,7 +63,8 @@ extern "C" {
                              *    ptd_mx_product_a8_tile,
                              *    ptd_lowrank_a8_tile_w4_workspace_bytes, ptd_lowrank_a8_tile_w4,
                              *    ptd_lowrank_a8_tile_w6_workspace_bytes, ptd_lowrank_a8_tile_w6,
-                             *    ptd_nsr_plan) */
+                             *    ptd_nsr_plan,
+                             *    ptd_gemm_f64_form) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -338,6 +339,32 @@ size_t ptd_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int ab_dtype, i
 int ptd_gemm_ws(const void* A, int64_t sam, int64_t sak, const void* B, int64_t sbk, int64_t sbn,
                 void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int ab_dtype, int c_dtype,
                 double alpha, const void* bias, void* ws, size_t ws_bytes, void* stream);
+
+/* Diagnostic for tests: the f64 product in the forms the eigensolver calls it in, which ptd_gemm (always the plain form)
+ * does not reach.  The entry forwards to the functions the solver itself calls and has no arithmetic or routing of its
+ * own; operands are addressed as in ptd_gemm, C is row-major with ld ldc.
+ *   PTD_GEMM_F64_PLAIN       C  = alpha A B
+ *   PTD_GEMM_F64_ACCUMULATE  C += alpha A B                      (ksplit must be 1: see below)
+ *   PTD_GEMM_F64_SLABS       K is cut into at most `ksplit` ranges of a multiple of 16; range y writes alpha A(:, range)
+ *                            B(range, :) to C + y * slab (slab in elements, >= M * ldc); *nslabs gets the number of
+ *                            ranges.  lower_only != 0: tiles that lie entirely above the diagonal may be left unwritten
+ *   PTD_GEMM_F64_PAIR        C += alpha (A B + A2 B2), both pairs with the same strides; row0_out (optional) also gets the
+ *                            updated row 0 of C; batch > 1: the same update on `batch` operand sets, EVERY pointer
+ *                            (row0_out included) moving by bstride elements per member
+ * Arguments a form does not use are ignored (A2, B2, row0_out, nslabs may then be NULL).  PTD_ERR_INVALID for a null
+ * pointer the form needs, ldc < N, an operand without exactly one unit stride, a negative dimension or one of 2^31 or
+ * more, ksplit < 1, batch < 1, a negative bstride, slab < M * ldc or an unknown form.  ACCUMULATE with ksplit > 1 is the
+ * K split with f64 atomics: it has no caller, its result depends on scheduling, and this entry answers
+ * PTD_ERR_UNSUPPORTED for it.
+ * Launch labels: "gemm_f64 (lds-dma)" for the 128-row LDS-DMA kernel, "gemm_f64" for the 64 x 64 kernel. */
+#define PTD_GEMM_F64_PLAIN 0
+#define PTD_GEMM_F64_ACCUMULATE 1
+#define PTD_GEMM_F64_SLABS 2
+#define PTD_GEMM_F64_PAIR 3
+int ptd_gemm_f64_form(int form, const double* A, int64_t sam, int64_t sak, const double* B, int64_t sbk, int64_t sbn,
+                      const double* A2, const double* B2, double* C, int64_t ldc, int64_t slab, int64_t M, int64_t N,
+                      int64_t K, double alpha, int ksplit, int lower_only, int* nslabs, double* row0_out, int batch,
+                      int64_t bstride, void* stream);
 
 /* y[T,n_o] = (x[T,n_i] @ A[r,n_i]^T) @ B[n_o,r]^T (+ bias[n_o]), dtype f32, bf16 or f16.  The workspace holds the
  * [T, r] intermediate of the operand dtype and, for f32 operands with a small rank, the partial

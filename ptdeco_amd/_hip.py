@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libptdeco_hip.so")
 
 F32, F64, BF16, F16 = 0, 1, 2, 3
 ABI_VERSION = 6
+GEMM_F64_PLAIN, GEMM_F64_ACCUMULATE, GEMM_F64_SLABS, GEMM_F64_PAIR = 0, 1, 2, 3   # PTD_GEMM_F64_*: ptd_gemm_f64_form
 Q_FP8_E4M3, Q_MXFP4, Q_MXFP6_E2M3 = 1, 2, 3      # PTD_Q_*: q_format of the grouped and gated quantised decode entries
 
 # The argument lists the entries of the low-rank pair share, each named once (restype, argtypes): the regimes of a family
@@ -106,6 +107,11 @@ SIGNATURES = {
     "ptd_gemm_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int]),
     "ptd_gemm_ws": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                             c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # form, A, sam, sak, B, sbk, sbn, A2, B2, C, ldc, slab, M, N, K, alpha, ksplit, lower_only, nslabs, row0_out, batch,
+    # bstride, stream
+    "ptd_gemm_f64_form": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_double, c_int, c_int,
+                                  ctypes.POINTER(c_int), c_void_p, c_int, c_int64, c_void_p]),
     "ptd_lowrank_forward_workspace_bytes": _PAIR_WS,
     "ptd_lowrank_forward": _PAIR16,
     "ptd_lowrank_decode_workspace_bytes": _PAIR_WS,

@@ -394,6 +394,37 @@ int ptd_gemm_ws(const void* A, int64_t sam, int64_t sak, const void* B, int64_t 
   return PTD_ERR_UNSUPPORTED;
 }
 
+int ptd_gemm_f64_form(int form, const double* A, int64_t sam, int64_t sak, const double* B, int64_t sbk, int64_t sbn,
+                      const double* A2, const double* B2, double* C, int64_t ldc, int64_t slab, int64_t M, int64_t N,
+                      int64_t K, double alpha, int ksplit, int lower_only, int* nslabs, double* row0_out, int batch,
+                      int64_t bstride, void* stream) {
+  PTD_REQUIRE(form >= PTD_GEMM_F64_PLAIN && form <= PTD_GEMM_F64_PAIR, "ptd_gemm_f64_form: unknown form %d", form);
+  PTD_REQUIRE(A && B && C, "ptd_gemm_f64_form: null pointer");
+  PTD_REQUIRE(form != PTD_GEMM_F64_PAIR || (A2 && B2), "ptd_gemm_f64_form: null pointer (second operand pair)");
+  PTD_REQUIRE(form != PTD_GEMM_F64_SLABS || nslabs, "ptd_gemm_f64_form: null pointer (nslabs)");
+  PTD_REQUIRE(M >= 0 && N >= 0 && K >= 0 && ldc >= N, "ptd_gemm_f64_form: bad shape");
+  PTD_REQUIRE(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31), "ptd_gemm_f64_form: dimension too large");
+  PTD_REQUIRE((sam == 1) != (sak == 1) && (sbk == 1) != (sbn == 1),
+              "ptd_gemm_f64_form: exactly one stride of each operand must be 1");
+  PTD_REQUIRE(ksplit >= 1 && batch >= 1 && bstride >= 0, "ptd_gemm_f64_form: bad ksplit, batch or bstride");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (form) {
+    case PTD_GEMM_F64_PLAIN:
+      return gemm_f64(A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, alpha, false, ksplit, st);
+    case PTD_GEMM_F64_ACCUMULATE:
+      if (ksplit > 1) {
+        set_error("ptd_gemm_f64_form: ACCUMULATE with ksplit = %d is the atomic K split, which has no caller", ksplit);
+        return PTD_ERR_UNSUPPORTED;
+      }
+      return gemm_f64(A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, alpha, true, 1, st);
+    case PTD_GEMM_F64_SLABS:
+      PTD_REQUIRE(slab >= M * ldc, "ptd_gemm_f64_form: slab %lld < M * ldc", (long long)slab);
+      return gemm_f64_slabs(A, sam, sak, B, sbk, sbn, C, ldc, slab, M, N, K, alpha, ksplit, nslabs, lower_only != 0, st);
+    default:
+      return gemm_f64_pair(A, B, A2, B2, sam, sak, sbk, sbn, C, ldc, M, N, K, alpha, row0_out, st, batch, bstride);
+  }
+}
+
 static size_t elt_bytes(int dtype) { return dtype == PTD_F32 ? 4 : 2; }
 
 // the 16-bit products of an operand dtype (bf16 or f16: the same kernels, see gemm_bf16.hip)

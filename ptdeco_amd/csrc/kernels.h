@@ -324,6 +324,10 @@ int gemm_f64_slabs(const double* A, int64_t sam, int64_t sak, const double* B, i
                    int64_t ldc, int64_t slab, int64_t M, int64_t N, int64_t K, double alpha, int ksplit, int* nslabs,
                    bool lower_only, hipStream_t st);
 
+int gemm_f64_pair(const double* A, const double* B, const double* A2, const double* B2, int64_t sam, int64_t sak,
+                  int64_t sbk, int64_t sbn, double* C, int64_t ldc, int64_t M, int64_t N, int64_t K, double alpha,
+                  double* row0_out, hipStream_t st, int batch, int64_t bstride_elems);
+
 // eigh_tridiag.hip
 size_t tridiag_workspace_bytes(int64_t n);
 // ptd_set_concurrent_chains: how many eigendecompositions the caller runs at once on the current device (returns the

@@ -348,11 +348,46 @@ def matmul(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None
     # few output tiles (a ViT batch's 1576 rows against 768 columns): the K range is split through a workspace
     ws_bytes = lib.ptd_gemm_workspace_bytes(M, N, K, _code(a), _DT[out_dtype]) if _GEMM_WS else 0
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device) if ws_bytes else None
+    if M == 0 or N == 0:
+        return c
+    # K = 0: torch gives an empty operand a null data_ptr, which the entry refuses; nothing is read through it, so any
+    # valid address stands in and C comes out as alpha * 0 (+ bias)
     with torch.cuda.device(a.device):
-        rc = lib.ptd_gemm_ws(a.data_ptr(), sam, sak, b.data_ptr(), sbk, sbn, c.data_ptr(), N, M, N, K, _code(a),
-                             _DT[out_dtype], float(alpha), _ptr(bias), _ptr(ws), ws_bytes, _stream(a))
+        rc = lib.ptd_gemm_ws(a.data_ptr() or c.data_ptr(), sam, sak, b.data_ptr() or c.data_ptr(), sbk, sbn,
+                             c.data_ptr(), N, M, N, K, _code(a), _DT[out_dtype], float(alpha), _ptr(bias), _ptr(ws), ws_bytes, _stream(a))
     _hip.check(rc, "ptd_gemm")
     return c
+
+
+GEMM_F64_FORMS = {"plain": _hip.GEMM_F64_PLAIN, "accumulate": _hip.GEMM_F64_ACCUMULATE, "slabs": _hip.GEMM_F64_SLABS,
+                  "pair": _hip.GEMM_F64_PAIR}
+
+
+def gemm_f64_form(form: str, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, alpha: float = 1.0, *, ksplit: int = 1,
+                  slab: int = 0, lower_only: bool = False, a2: Optional[torch.Tensor] = None,
+                  b2: Optional[torch.Tensor] = None, row0_out: Optional[torch.Tensor] = None, batch: int = 1,
+                  bstride: int = 0) -> int:
+    """The f64 product in the forms the eigensolver calls it in (ptd_gemm_f64_form, a diagnostic for tests), written
+    into ``c`` in place.  ``a`` [M, K] and ``b`` [K, N] are f64 views with exactly one unit stride each and are passed
+    as they lie (no copies); ``c`` [M, N] has unit column stride.  "plain": c = alpha a b; "accumulate": c += alpha a b;
+    "slabs": K range y of at most ``ksplit`` goes to the memory ``slab`` elements times y behind ``c``; "pair":
+    c += alpha (a b + a2 b2), ``row0_out`` also gets row 0 of the result, and with ``batch`` > 1 every pointer moves by
+    ``bstride`` elements per member.  Returns the number of slabs written (1 for the other forms)."""
+    _dev(a, b, c, a2, b2, row0_out)
+    assert a.dtype == b.dtype == c.dtype == torch.float64 and a.dim() == b.dim() == c.dim() == 2
+    M, K = a.shape
+    N = b.shape[1]
+    assert b.shape[0] == K and c.shape == (M, N) and (c.stride(1) == 1 or N <= 1)
+    assert (a2 is None or a2.stride() == a.stride()) and (b2 is None or b2.stride() == b.stride())
+    nslabs = ctypes.c_int(1)
+    with torch.cuda.device(c.device):
+        # (an empty operand, K = 0, has a null data_ptr in torch: C's address stands in, nothing is read through it)
+        rc = _hip.load().ptd_gemm_f64_form(GEMM_F64_FORMS[form], a.data_ptr() or c.data_ptr(), a.stride(0), a.stride(1),
+                                           b.data_ptr() or c.data_ptr(), b.stride(0), b.stride(1), _ptr(a2), _ptr(b2), c.data_ptr(), c.stride(0),
+                                           int(slab), M, N, K, float(alpha), int(ksplit), int(bool(lower_only)),
+                                           ctypes.byref(nslabs), _ptr(row0_out), int(batch), int(bstride), _stream(c))
+    _hip.check(rc, "ptd_gemm_f64_form")
+    return nslabs.value
 
 
 def lowrank_forward(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:

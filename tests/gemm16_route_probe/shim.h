@@ -1,4 +1,4 @@
-// Force-included (-include) into a HOST-ONLY compile of ptdeco_amd/csrc/gemm_bf16.hip: every kernel launch becomes a
+// Force-included (-include) into a HOST-ONLY compile of ptdeco_amd/csrc/gemm_bf16.hip or gemm_f64.hip: every launch becomes a
 // call of a recorder, so the router can be driven on a machine without a GPU and without a HIP runtime.
 // The recorder gets the kernel's handle (the test names the exact template instance from it), the grid, the block and
 // the trailing launch arguments of arithmetic type.  Pointers are skipped, and so are structs: they have padding.

@@ -39,21 +39,23 @@ def _nm():
     return shutil.which("nm")
 
 
-def build(workdir):
-    """-> path of the probe program, built under workdir (str or Path)."""
+def build(workdir, source="gemm_bf16.hip", driver="driver.cpp", name="gemm16_route_probe"):
+    """-> path of the probe program, built under workdir (str or Path): `source` of ptdeco_amd/csrc compiled host-only
+    behind the shim, linked with `driver` of the probe directory."""
     workdir = str(workdir)
     cc = hipcc()
     host = [cc, "--cuda-host-only", "-O1", "-std=c++17", "-include", os.path.join(PROBE, "shim.h"), "-c"]
-    gemm_o, driver_o = os.path.join(workdir, "gemm_bf16.o"), os.path.join(workdir, "driver.o")
-    _run(host + [os.path.join(CSRC, "gemm_bf16.hip"), "-o", gemm_o])
-    _run(host + [os.path.join(PROBE, "driver.cpp"), "-o", driver_o])
+    gemm_o = os.path.join(workdir, os.path.splitext(source)[0] + ".o")
+    driver_o = os.path.join(workdir, os.path.splitext(driver)[0] + ".o")
+    _run(host + [os.path.join(CSRC, source), "-o", gemm_o])
+    _run(host + [os.path.join(PROBE, driver), "-o", driver_o])
     # the device image the host object expects to find linked in: a zeroed array under the name it asks for
     undefined = _run([_nm(), "-u", gemm_o]).stdout
     fatbin = re.search(r"\b(__hip_fatbin_\w*)", undefined).group(1)
     fatbin_c = os.path.join(workdir, "fatbin.c")
     with open(fatbin_c, "w") as f:
         f.write(f"const char {fatbin}[4096] __attribute__((aligned(4096))) = {{0}};\n")
-    exe = os.path.join(workdir, "gemm16_route_probe")
+    exe = os.path.join(workdir, name)
     _run([os.path.join(_llvm_bin(), "clang++"), "-no-pie", "-o", exe, gemm_o, driver_o, "-x", "c", fatbin_c])
     return exe
 
@@ -76,12 +78,12 @@ def _instances(exe):
     return names
 
 
-def _rows(exe, names, setting=None, args=()):
+def _rows(exe, names, setting=None, args=(), stdin=None):
     env = {k: v for k, v in os.environ.items() if not k.startswith("PTD_GEMM_")}
     if setting:
         key, value = setting.split("=")
         env[key] = value
-    out = _run([exe, *args], env=env).stdout
+    out = _run([exe, *args], env=env, input=stdin).stdout
     return [re.sub(r"@(0x[0-9a-f]+)", lambda m: names[int(m.group(1), 16)], line) for line in out.splitlines()]
 
 

@@ -68,6 +68,57 @@ def test_nsr_plan_query(lib):
     assert l.ptd_nsr_plan(4096, 4096, 9, 1, out, 7) == -2
 
 
+def test_gemm_f64_form_entry_and_refusals(lib):
+    """ptd_gemm_f64_form (the eigensolver's call forms of the f64 product, for tests): declared, bound, exported, ABI
+    still 6, and every refusal returns before anything is launched -- the pointers below are never dereferenced."""
+    from ptdeco_amd import _hip
+    assert "ptd_gemm_f64_form" in _declared() and "ptd_gemm_f64_form" in _hip.SIGNATURES and hasattr(lib, "ptd_gemm_f64_form")
+    src = open(HEADER).read()
+    assert re.search(r"#define PTD_ABI_VERSION 6\b", src)
+    assert "ptd_gemm_f64_form" in src.split("added since", 1)[1].split("*/", 1)[0]
+    for i, name in enumerate(("PLAIN", "ACCUMULATE", "SLABS", "PAIR")):
+        assert re.search(rf"#define PTD_GEMM_F64_{name} {i}\b", src) and getattr(_hip, "GEMM_F64_" + name) == i
+    l = _hip.load()
+    ns = ctypes.c_int(-7)
+    PA, PB, PC, PX = 0x10000, 0x20000, 0x30000, 0x40000
+
+    def call(form, A=PA, sam=64, sak=1, B=PB, sbk=64, sbn=1, A2=None, B2=None, C=PC, ldc=64, slab=0, M=64, N=64, K=64,
+             ksplit=1, nslabs=ns, row0=None, batch=1, bstride=0):
+        return l.ptd_gemm_f64_form(form, A, sam, sak, B, sbk, sbn, A2, B2, C, ldc, slab, M, N, K, 1.0, ksplit, 0,
+                                   nslabs, row0, batch, bstride, None)
+
+    def refused(rc, *words):
+        msg = l.ptd_last_error()
+        return rc == -1 and msg.startswith(b"ptd_gemm_f64_form") and all(w in msg for w in words)
+
+    P, ACC, SLABS, PAIR = _hip.GEMM_F64_PLAIN, _hip.GEMM_F64_ACCUMULATE, _hip.GEMM_F64_SLABS, _hip.GEMM_F64_PAIR
+    l.ptd_launch_trace_begin()
+    for form in (P, ACC, SLABS, PAIR):
+        for null in ("A", "B", "C"):
+            assert refused(call(form, A2=PX, B2=PX, slab=64 * 64, **{null: None}), b"null")
+        assert refused(call(form, A2=PX, B2=PX, slab=64 * 64, ldc=63), b"shape")
+        assert refused(call(form, A2=PX, B2=PX, slab=64 * 64, M=-1), b"shape")
+        for dim in ("M", "N", "K"):
+            assert refused(call(form, A2=PX, B2=PX, slab=1 << 62, ldc=1 << 31, **{dim: 1 << 31}), b"too large")
+        assert refused(call(form, A2=PX, B2=PX, slab=64 * 64, sam=1, sak=1), b"stride")       # both unit
+        assert refused(call(form, A2=PX, B2=PX, slab=64 * 64, sam=64, sak=64), b"stride")     # none
+        assert refused(call(form, A2=PX, B2=PX, slab=64 * 64, sbk=1, sbn=1), b"stride")
+        assert refused(call(form, A2=PX, B2=PX, slab=64 * 64, sbk=64, sbn=2), b"stride")
+        assert refused(call(form, A2=PX, B2=PX, slab=64 * 64, ksplit=0), b"ksplit")
+        assert refused(call(form, A2=PX, B2=PX, slab=64 * 64, batch=0), b"batch")
+    assert refused(call(PAIR, A2=None, B2=PX), b"null") and refused(call(PAIR, A2=PX, B2=None), b"null")
+    assert refused(call(SLABS, slab=64 * 64, nslabs=None), b"null")
+    assert refused(call(SLABS, slab=64 * 64 - 1), b"slab") and refused(call(SLABS, slab=0), b"slab")
+    assert refused(call(SLABS, slab=64 * 64, ldc=72), b"slab")                                # M * ldc, not M * N
+    assert refused(call(4), b"form") and refused(call(-1), b"form")
+    # the K split with atomics: no caller, scheduling-dependent -- not served through this entry
+    assert call(ACC, ksplit=2) == -2 and l.ptd_last_error().startswith(b"ptd_gemm_f64_form")
+    # an empty product is accepted and launches nothing
+    assert call(P, M=0) == 0 and call(ACC, N=0, ldc=0) == 0 and call(PAIR, A2=PX, B2=PX, M=0) == 0
+    buf = ctypes.create_string_buffer(64)
+    assert l.ptd_launch_trace_end(buf, 64) == 0 and ns.value == -7
+
+
 def test_eigh_route_query(monkeypatch):
     """ptd_eigh_route is a host-side function of (n, k, all_values) and the environment: the filtered subspace iteration
     for at most 2/7 of the spectrum of a large matrix whose eigenvalues below are not wanted, the direct reduction for

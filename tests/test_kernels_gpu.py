@@ -1225,8 +1225,12 @@ def test_gemm_f32_256_tile_deep_pipeline_exact_and_repeatable(ops):
 def test_gemm_f64_lds_dma_kernel_exact_integers(ops):
     """The f64 LDS-DMA kernel (gemm_f64_glds_kernel<NT, AM>: B rows N-contiguous, A rows K- or M-contiguous, 128 x 16 NT
     tiles) on integer operands -- every product and partial sum is exact in any order, so a wrong swizzle, a stale
-    buffer or a torn DMA piece shows.  Shapes pick every column-tile width (N = 1280: NT 5, 1024: 8, 768: 6, 320: 4 / 5,
-    64: 4) in both A layouts, operands that are slices of wider matrices, K of a single and of many steps, repeated."""
+    buffer or a torn DMA piece shows.  The widths these shapes really take (glds_nt prefers the narrowest tile that
+    divides N while one round of workgroups holds all tiles; tests/golden/gemm_f64_routes.txt has the rule's table):
+    NT 5 for (4096, 1280, 4096) -- 640 tiles of width 4 are two rounds, 512 of width 5 one -- and NT 4 for every other
+    shape, so only the three-buffer ring runs here; (384, 320, 48) is no LDS-DMA product at all (K < 64) and takes the
+    64 x 64 kernel.  NT 6 and NT 8, the two-buffer ring, and every call form are in test_gemm_f64_gpu.py.  Both A layouts,
+    operands that are slices of wider matrices, K of many steps, repeated; the launch label of every call is asserted."""
     g = torch.Generator().manual_seed(12)
     shapes = [(4096, 1280, 4096), (1280, 1280, 2048), (512, 1024, 64), (256, 768, 160), (384, 320, 48),
               (2048, 64, 1024), (256, 960, 4096)]
@@ -1237,14 +1241,15 @@ def test_gemm_f64_lds_dma_kernel_exact_integers(ops):
             av = a_full[:, 16:16 + M].T if am else a_full[:, 16:16 + K]      # [M, K] view, M- or K-contiguous rows
             bv = b_full[:, 16:16 + N]
             ref = (av.cpu() @ bv.cpu()).to(DEV)
+            label = "gemm_f64 (lds-dma)" if K >= 64 else "gemm_f64"
             for rep in range(2):
-                got = ops.matmul(av, bv)
+                got = _traced(ops, label, ops.matmul, av, bv)
                 assert torch.equal(got, ref), (M, N, K, am, rep)
     # random data against LAPACK-order f64 arithmetic on the host
     a = torch.randn(1024, 512, generator=g, dtype=torch.float64).to(DEV)
     b = torch.randn(512, 1280, generator=g, dtype=torch.float64).to(DEV)
     ref = (a.cpu() @ b.cpu())
-    assert (ops.matmul(a, b).cpu() - ref).abs().max().item() <= 1e-12 * ref.abs().max().item()
+    assert (_traced(ops, "gemm_f64 (lds-dma)", ops.matmul, a, b).cpu() - ref).abs().max().item() <= 1e-12 * ref.abs().max().item()
 
 
 def test_gemm_f32_exact_integers(ops):
