@@ -64,7 +64,8 @@ extern "C" {
                              *    ptd_lowrank_a8_tile_w4_workspace_bytes, ptd_lowrank_a8_tile_w4,
                              *    ptd_lowrank_a8_tile_w6_workspace_bytes, ptd_lowrank_a8_tile_w6,
                              *    ptd_nsr_plan,
-                             *    ptd_gemm_f64_form) */
+                             *    ptd_gemm_f64_form,
+                             *    ptd_lowrank_skinny_group_workspace_bytes, ptd_lowrank_skinny_group) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -773,6 +774,28 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                              const void* Ag, int64_t lda_g, int64_t r_g, const void* Bg, int64_t ldb_g, const void* bias_g,
                              const void* Au, int64_t lda_u, int64_t r_u, const void* Bu, int64_t ldb_u, const void* bias_u,
                              int64_t n_ff, int act, void* y, int64_t ldy,
+                             void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* 1 <= count <= PTD_LOWRANK_GROUP_MAX bf16 / f16 pairs that read the same x at the same 32 <= T <= 96 tokens (arguments of
+ * ptd_lowrank_decode_group; operands and semantics per member those of ptd_lowrank_skinny), in THREE launches on the
+ * caller's stream instead of three per pair: every member's first product into its own f32 slabs (the members' grids laid
+ * end to end by descending r[m] n_i, the token tile in the grid's z), every member's slab sum into its own 16-bit h, every
+ * member's second product into its own y[m] with row pitch ldy[m] (the column blocks of one [T, sum n_o] tensor, or
+ * unrelated buffers; by descending n_o[m] r[m]).  Each member keeps the K split (a function of n_i and r[m] alone), the
+ * slab order, the wave quarters, the step order and the rounding points of ptd_lowrank_skinny, so every y[m] holds the
+ * bits ptd_lowrank_skinny gives for that member alone and row t of y depends on row t of x alone, whatever T is.  The
+ * argument arrays are read before the call returns and not after it (the call may be captured in a graph).  Served when
+ * every member is served by ptd_lowrank_skinny with the common x, T, n_i and dtype; anything else, f32 and a count
+ * outside 1 .. PTD_LOWRANK_GROUP_MAX included, returns PTD_ERR_UNSUPPORTED before a kernel is launched.  Null pointers
+ * (bias, or an entry of it, may be NULL), a leading dimension below its row length or a misaligned workspace
+ * PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  The workspace is the sum of the members'
+ * ptd_lowrank_skinny workspaces in the caller's order (each a multiple of 256 bytes: the slabs, then h). */
+size_t ptd_lowrank_skinny_group_workspace_bytes(int count, int64_t T, int64_t n_i, const int64_t* r, int dtype);
+int ptd_lowrank_skinny_group(const void* x, int64_t ldx, int64_t T, int64_t n_i, int count,
+                             const void* const* A, const int64_t* lda, const int64_t* r,
+                             const void* const* B, const int64_t* ldb, const int64_t* n_o,
+                             const void* const* bias /* entries may be NULL; the array may be NULL */,
+                             void* const* y, const int64_t* ldy,
                              void* ws, size_t ws_bytes, int dtype, void* stream);
 
 /* 1 <= count <= PTD_LOWRANK_GROUP_MAX pairs with quantised factors of ONE format that read the same x at small batches,

@@ -49,6 +49,10 @@ _MX_PRODUCT_A8_TILE = (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_
 # the 16-bit gated pair: per side A, lda, r, B, ldb, bias; then n_ff, act
 _SIDE16 = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]
 _GATED16 = (c_int, _X + _SIDE16 + _SIDE16 + [c_int64, c_int] + _Y_WS + [c_int, c_void_p])
+# the 16-bit group (decode / skinny): x, ldx, T, n_i, count, then 9 arrays (A, lda, r, B, ldb, n_o, bias, y, ldy), ws,
+# ws_bytes, dtype, stream
+_GROUP16_WS = (c_size_t, [c_int, c_int64, c_int64, c_void_p, c_int])             # (count, T, n_i, r[], dtype)
+_GROUP16 = (c_int, _X + [c_int] + [c_void_p] * 9 + [c_void_p, c_size_t, c_int, c_void_p])
 # the quantised group: q_format, x, ldx, T, n_i, count, then 13 arrays (Aq, lda, sa, ldsa, r, Bq, ldb, sb, ldsb, n_o, bias,
 # y, ldy), ws, ws_bytes, dtype, stream
 _GROUP_Q = (c_int, [c_int] + _X + [c_int] + [c_void_p] * 13 + [c_void_p, c_size_t, c_int, c_void_p])
@@ -122,10 +126,8 @@ SIGNATURES = {
     "ptd_lowrank_decode_w4": _PAIR_MX,
     "ptd_lowrank_decode_w6_workspace_bytes": _PAIR_WS,
     "ptd_lowrank_decode_w6": _PAIR_MX,
-    "ptd_lowrank_decode_group_workspace_bytes": (c_size_t, [c_int, c_int64, c_int64, c_void_p, c_int]),
-    "ptd_lowrank_decode_group": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                         c_int, c_void_p]),
+    "ptd_lowrank_decode_group_workspace_bytes": _GROUP16_WS,
+    "ptd_lowrank_decode_group": _GROUP16,
     "ptd_lowrank_decode_gated_workspace_bytes": _GATED_WS,
     "ptd_lowrank_decode_gated": _GATED16,
     "ptd_lowrank_decode_group_q_workspace_bytes": _GROUP_Q_WS,
@@ -163,6 +165,8 @@ SIGNATURES = {
     "ptd_lowrank_a8_tile_w6": _PAIR_MX,
     "ptd_lowrank_skinny_gated_workspace_bytes": _GATED_WS,
     "ptd_lowrank_skinny_gated": _GATED16,
+    "ptd_lowrank_skinny_group_workspace_bytes": _GROUP16_WS,
+    "ptd_lowrank_skinny_group": _GROUP16,
     "ptd_lowrank_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),
     "ptd_lowrank_forward_nchw_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
     "ptd_lowrank_forward_nchw": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,

@@ -8,6 +8,9 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
                                                              ops.lowrank_decode_group where ops.lowrank_decode_group_serves
                                                              (1 to 4 pairs on one x2d, T <= 16), else member by member
                                                              as lowrank_forward chooses
+    lowrank_forward_group_fused(Tensor x2d, Tensor[] As, Tensor[] Bs, Tensor?[] biases) -> Tensor
+                                                             the same, with ops.lowrank_skinny_group where
+                                                             ops.lowrank_skinny_group_serves (32 ... 96) between the two
     lowrank_forward_gated(Tensor x2d, Tensor Ag, Tensor Bg, Tensor? bias_g, Tensor Au, Tensor Bu, Tensor? bias_u, str act)
         -> Tensor                                            act(g) * u of a gate and an up pair on one x2d:
                                                              ops.lowrank_decode_gated where ops.lowrank_decode_gated_serves
@@ -100,6 +103,11 @@ def lowrank_forward_group(x2d: torch.Tensor, As: List[torch.Tensor], Bs: List[to
     otherwise each member on the entry lowrank_forward picks for it.  Inference only: no autograd formula."""
     if ops.lowrank_decode_group_serves(x2d, As, Bs, biases):
         return ops.lowrank_decode_group(x2d, As, Bs, biases)
+    return _members(x2d, As, Bs, biases)
+
+
+def _members(x2d, As, Bs, biases):
+    """The members of a group one after the other, each on the entry ``_member`` picks, into their columns of y."""
     y = x2d.new_empty((x2d.shape[0], sum(B.shape[0] for B in Bs)))
     off = 0
     for A, B, bias in zip(As, Bs, biases):
@@ -109,7 +117,7 @@ def lowrank_forward_group(x2d: torch.Tensor, As: List[torch.Tensor], Bs: List[to
 
 
 @lowrank_forward_group.register_fake
-def _(x2d, As, Bs, biases):
+def _group_fake(x2d, As, Bs, biases):
     torch._check(len(As) >= 1 and len(Bs) == len(As) and len(biases) == len(As),
                  lambda: "lowrank_forward_group: As, Bs and biases must list the same members, at least one")
     torch._check(x2d.dim() == 2, lambda: "lowrank_forward_group: x2d must be 2-D")
@@ -121,6 +129,25 @@ def _(x2d, As, Bs, biases):
                      lambda: "lowrank_forward_group: every operand must be on x2d's device")
         torch._check(bias is None or tuple(bias.shape) == (B.shape[0],), lambda: "lowrank_forward_group: bias must be [n_o]")
     return x2d.new_empty((x2d.shape[0], sum(B.shape[0] for B in Bs)))
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_group_fused", mutates_args=())
+def lowrank_forward_group_fused(x2d: torch.Tensor, As: List[torch.Tensor], Bs: List[torch.Tensor],
+                                biases: List[Optional[torch.Tensor]]) -> torch.Tensor:
+    """``lowrank_forward_group`` with the group kernels of the small batches as well (the operator behind
+    ``lowrank_group(..., small_batches="fused")``): at decode shapes ptd_lowrank_decode_group, at 32 to 96 tokens
+    (ops.lowrank_skinny_group_serves: bf16 / f16, every member served by ops.lowrank_skinny) three launches for the group
+    on ptd_lowrank_skinny_group, every member's bits those of ops.lowrank_skinny; otherwise each member on the entry
+    lowrank_forward picks for it.  The same bits as lowrank_forward_group at every T.  Inference only: no autograd
+    formula."""
+    if ops.lowrank_decode_group_serves(x2d, As, Bs, biases):
+        return ops.lowrank_decode_group(x2d, As, Bs, biases)
+    if ops.lowrank_skinny_group_serves(x2d, As, Bs, biases):
+        return ops.lowrank_skinny_group(x2d, As, Bs, biases)
+    return _members(x2d, As, Bs, biases)
+
+
+lowrank_forward_group_fused.register_fake(_group_fake)
 
 
 # torch's own form of each activation ptd_lowrank_decode_gated knows (the names of ops.GATED_ACTS)

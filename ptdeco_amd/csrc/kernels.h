@@ -171,6 +171,17 @@ int lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i, con
                          const void* Bu, int64_t ldb_u, const void* bias_u, int64_t n_o, int act, void* y, int64_t ldy,
                          void* ws, int dtype, hipStream_t st);
 
+// lowrank_skinny_group.hip: 1 .. PTD_LOWRANK_GROUP_MAX bf16 / f16 pairs on one input at 32 <= T <= 96 tokens in three
+// launches (ptd_lowrank_skinny_group); every member's bits are lowrank_skinny's on that member alone
+bool lowrank_skinny_group_serves(int count, int64_t T, int64_t n_i, const int64_t* r, const int64_t* n_o, int dtype,
+                                 const void* x, int64_t ldx, const void* const* A, const int64_t* lda,
+                                 const void* const* B, const int64_t* ldb);
+size_t lowrank_skinny_group_workspace_bytes(int count, int64_t T, int64_t n_i, const int64_t* r, int dtype);
+int lowrank_skinny_group(const void* x, int64_t ldx, int64_t T, int64_t n_i, int count, const void* const* A,
+                         const int64_t* lda, const int64_t* r, const void* const* B, const int64_t* ldb,
+                         const int64_t* n_o, const void* const* bias, void* const* y, const int64_t* ldy, void* ws,
+                         int dtype, hipStream_t st);
+
 // lowrank_skinny_w8.hip (the kernel bodies of every quantised skinny pair: lowrank_skinny_q.h): the fp8 pair of
 // lowrank_decode_w8.hip at 32 <= T <= PTD_LOWRANK_SKINNY_W8_MAX_T tokens with the structure of lowrank_skinny.hip: three
 // launches, a lane's 16-byte load converted in registers, row scales where the sums are complete (ptd_lowrank_skinny_w8)

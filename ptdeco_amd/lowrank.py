@@ -25,6 +25,7 @@ from . import ops
 _lowrank_forward = torch.ops.ptdeco_amd.lowrank_forward.default
 _lowrank_forward_nchw = torch.ops.ptdeco_amd.lowrank_forward_nchw.default
 _lowrank_forward_group = torch.ops.ptdeco_amd.lowrank_forward_group.default
+_lowrank_forward_group_fused = torch.ops.ptdeco_amd.lowrank_forward_group_fused.default
 _lowrank_forward_gated = torch.ops.ptdeco_amd.lowrank_forward_gated.default
 _lowrank_forward_w8 = torch.ops.ptdeco_amd.lowrank_forward_w8.default
 _lowrank_forward_w4 = torch.ops.ptdeco_amd.lowrank_forward_w4.default
@@ -559,6 +560,7 @@ def set_pair_activations(model: torch.nn.Module, activations: str, names=None) -
 
 
 _QUANTIZED_MODES = ("members", "fused")
+_SMALL_BATCH_MODES = ("members", "fused")
 
 
 def _fused_format(x: torch.Tensor, pairs, quantized: str):
@@ -583,7 +585,7 @@ def _q_operands(p):
     return p.weight_a_q, p.scale_a, p.weight_b_q, p.scale_b, p.bias
 
 
-def lowrank_group(x: torch.Tensor, pairs, *, quantized: str = "members") -> torch.Tensor:
+def lowrank_group(x: torch.Tensor, pairs, *, quantized: str = "members", small_batches: str = "members") -> torch.Tensor:
     """The outputs of installed ``LowRankLinear`` modules that read the same x, side by side: [..., sum out_features],
     member m in the columns after those of the members before it (``y.split([p[1].out_features for p in pairs], -1)``
     are the members' outputs).  For the q / k / v and gate / up projections of a decomposed transformer block: at decode
@@ -598,7 +600,16 @@ def lowrank_group(x: torch.Tensor, pairs, *, quantized: str = "members") -> torc
     wanted, the group runs on ``torch.ops.ptdeco_amd.lowrank_forward_group_q`` -- at 1 to 16 tokens two launches for
     the group, at 32 to 96 tokens three, every member's columns bit for bit what the member returns alone; at other
     token counts each member as it runs alone.  A mix of formats, or a quantised member beside a 16-bit one, is the "members" path.  16-bit members
-    ignore the keyword; any other value raises ``ValueError``."""
+    ignore the keyword; any other value raises ``ValueError``.
+
+    ``small_batches`` says what happens to 16-bit members (``LowRankLinear``) between the decode shapes and the tile
+    path.  "members", the default: at 32 to 96 tokens each member runs as it does alone (three launches each) and is
+    copied into its columns.  "fused": the group runs on ``torch.ops.ptdeco_amd.lowrank_forward_group_fused`` -- at 32
+    to 96 tokens (bf16 / f16, up to four members) three launches for the group, every member storing straight into its
+    columns, bit for bit what the member returns alone; at every other token count what the default does.  Quantised
+    members ignore the keyword; any other value raises ``ValueError``."""
+    if small_batches not in _SMALL_BATCH_MODES:
+        raise ValueError(f"small_batches must be one of {_SMALL_BATCH_MODES}, got {small_batches!r}")
     pairs = list(pairs)
     fmt = _fused_format(x, pairs, quantized)
     if fmt is not None:
@@ -613,8 +624,8 @@ def lowrank_group(x: torch.Tensor, pairs, *, quantized: str = "members") -> torc
     if not fused:
         return torch.cat([p(x) for p in pairs], -1)
     x2d = x.reshape(-1, pairs[0][0].in_features)
-    y = _lowrank_forward_group(x2d, [p[0].weight for p in pairs], [p[1].weight for p in pairs],
-                               [p[1].bias for p in pairs])
+    group = _lowrank_forward_group_fused if small_batches == "fused" else _lowrank_forward_group
+    y = group(x2d, [p[0].weight for p in pairs], [p[1].weight for p in pairs], [p[1].bias for p in pairs])
     return y.reshape(*x.shape[:-1], y.shape[1])
 
 

@@ -730,6 +730,11 @@ def lowrank_decode_group(x2d: torch.Tensor, As: Sequence[torch.Tensor], Bs: Sequ
     """[(x2d @ A_m^T) @ B_m^T + bias_m for m] side by side: y [T, sum n_o] contiguous, member m in columns
     [off_m, off_m + n_o_m), for 1 <= T <= 16 rows of x2d and 1 to 4 members A_m [r_m, n_i], B_m [n_o_m, r_m]:
     ptd_lowrank_decode_group.  A group the entry does not serve (``lowrank_decode_group_serves``) raises."""
+    return _group16_call("decode", x2d, As, Bs, biases)
+
+
+def _group16_call(regime: str, x2d, As, Bs, biases) -> torch.Tensor:
+    """ptd_lowrank_<regime>_group on these operands: y and the workspace, the biases in x2d's dtype, the argument arrays."""
     count = len(As)
     assert 1 <= count and len(Bs) == count and len(biases) == count
     _dev(x2d, *As, *Bs, *biases)
@@ -744,16 +749,16 @@ def lowrank_decode_group(x2d: torch.Tensor, As: Sequence[torch.Tensor], Bs: Sequ
     offs = [sum(widths[:m]) * y.element_size() for m in range(count)]
     ptrs, i64s = ctypes.c_void_p * count, ctypes.c_int64 * count
     r = i64s(*[A.shape[0] for A in As])
-    lib = _hip.load()
-    ws_bytes = lib.ptd_lowrank_decode_group_workspace_bytes(count, T, n_i, r, _code(x2d))
+    lib, entry = _hip.load(), f"ptd_lowrank_{regime}_group"
+    ws_bytes = getattr(lib, entry + "_workspace_bytes")(count, T, n_i, r, _code(x2d))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
     with torch.cuda.device(x2d.device):
-        rc = lib.ptd_lowrank_decode_group(
+        rc = getattr(lib, entry)(
             x2d.data_ptr(), x2d.stride(0), T, n_i, count, ptrs(*[A.data_ptr() for A in As]),
             i64s(*[A.stride(0) for A in As]), r, ptrs(*[B.data_ptr() for B in Bs]), i64s(*[B.stride(0) for B in Bs]),
             i64s(*widths), ptrs(*[_ptr(b) for b in biases]), ptrs(*[y.data_ptr() + off for off in offs]),
             i64s(*[total] * count), ws.data_ptr(), ws_bytes, _code(x2d), _stream(x2d))
-    _hip.check(rc, "ptd_lowrank_decode_group")
+    _hip.check(rc, entry)
     return y
 
 
@@ -1005,6 +1010,31 @@ def lowrank_skinny(x2d: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Op
     ptd_lowrank_skinny.  A shape the entry does not serve (``lowrank_skinny_serves``) raises; row t of the result
     depends on row t of x2d alone."""
     return _pair16_call("skinny", x2d, A, B, bias)
+
+
+# Pairs that read one input at small batches (q / k / v, gate / up) can run on ptd_lowrank_skinny_group: three launches
+# for the group instead of three per pair and a copy each; every member's columns hold the bits lowrank_skinny gives for
+# that member alone.  Opt-in (lowrank_group(..., small_batches="fused")); PTD_LOWRANK_SKINNY_GROUP=0 makes the rule
+# false, and so does PTD_LOWRANK_SKINNY=0 through the members' rule.
+_SKINNY_GROUP = os.environ.get("PTD_LOWRANK_SKINNY_GROUP", "1") != "0"
+
+
+def lowrank_skinny_group_serves(x2d: torch.Tensor, As: Sequence[torch.Tensor], Bs: Sequence[torch.Tensor],
+                                biases: Sequence[Optional[torch.Tensor]]) -> bool:
+    """Whether ``lowrank_skinny_group`` takes these operands as they lie (the rule of ptd_lowrank_skinny_group, without
+    loading the library): 1 to 4 members, each served by ``lowrank_skinny`` on the common x2d."""
+    if not _SKINNY_GROUP or not 1 <= len(As) <= _GROUP_MAX or len(Bs) != len(As) or len(biases) != len(As):
+        return False
+    return all(lowrank_skinny_serves(x2d, A, B, bias) for A, B, bias in zip(As, Bs, biases))
+
+
+def lowrank_skinny_group(x2d: torch.Tensor, As: Sequence[torch.Tensor], Bs: Sequence[torch.Tensor],
+                         biases: Sequence[Optional[torch.Tensor]]) -> torch.Tensor:
+    """[(x2d @ A_m^T) @ B_m^T + bias_m for m] side by side: y [T, sum n_o] contiguous, member m in columns
+    [off_m, off_m + n_o_m), for 32 <= T <= _SKINNY_MAX_T rows of x2d (bf16 / f16) and 1 to 4 members A_m [r_m, n_i],
+    B_m [n_o_m, r_m]: ptd_lowrank_skinny_group, three launches.  A group the entry does not serve
+    (``lowrank_skinny_group_serves``) raises; row t of the result depends on row t of x2d alone."""
+    return _group16_call("skinny", x2d, As, Bs, biases)
 
 
 # The fp8 pair of lowrank_decode_w8 at small batches (32 <= T <= _SKINNY_W8_MAX_T tokens) runs on ptd_lowrank_skinny_w8:
