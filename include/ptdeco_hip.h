@@ -65,7 +65,8 @@ extern "C" {
                              *    ptd_lowrank_a8_tile_w6_workspace_bytes, ptd_lowrank_a8_tile_w6,
                              *    ptd_nsr_plan,
                              *    ptd_gemm_f64_form,
-                             *    ptd_lowrank_skinny_group_workspace_bytes, ptd_lowrank_skinny_group) */
+                             *    ptd_lowrank_skinny_group_workspace_bytes, ptd_lowrank_skinny_group,
+                             *    ptd_lowrank_tile_w8_workspace_bytes, ptd_lowrank_tile_w8, ptd_lowrank_tile_w8_plan) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -672,6 +673,45 @@ int ptd_lowrank_tile_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                         const void* Aq, int64_t lda, const void* scale_a, int64_t ldsa, int64_t r,
                         const void* Bq, int64_t ldb, const void* scale_b, int64_t ldsb, int64_t n_o, const void* bias,
                         void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+
+/* The pair with 8-bit factors (arguments, formats and semantics of ptd_lowrank_skinny_w8: h and y from f32 sums, each
+ * scaled in f32 and rounded ONCE) at every T >= PTD_LOWRANK_TILE_W8_MIN_T: two tiled W8A16 products of their own
+ * (csrc/lowrank_tile_w8.hip) -- activations staged through LDS, the e4m3 codes streamed into registers and converted
+ * there (exactly), the row scale applied to the finished f32 sum in the epilogue.  No dequantised copy of a factor
+ * exists.  The first product's K range is cut into S slabs of f32 partial sums where its tiles alone do not fill the
+ * chip; one small kernel adds them in ascending slab order, applies scale_a and rounds once to h (three launches); with
+ * S = 1 the first product writes h itself (two launches).  S is a pure function of (T, n_i, r); the tile shapes change
+ * no bit.  One f32 accumulator per output and slab, K ascending in steps of 64: row t of y depends on row t of x alone,
+ * and two calls with equal S give equal bits for equal rows.  No atomics; everything on the caller's stream without a
+ * host read or an allocation: the call can be captured in a graph.  Served: the operands of ptd_lowrank_skinny_w8 (dtype
+ * bf16 / f16, w_format PTD_W8_FP8_E4M3, r >= 16, n_i and r multiples of 16, lda and ldb multiples of 16, ldx a multiple
+ * of 8, x, Aq and Bq 16-byte aligned, the scales 4-byte aligned, bias 2-byte aligned and optional, n_i < 2^30, r < 2^27,
+ * 1 <= n_o < 2^30) at PTD_LOWRANK_TILE_W8_MIN_T <= T <= 2^24 with T max(n_i, r, n_o) < 2^40.  Anything else returns
+ * PTD_ERR_UNSUPPORTED before a kernel is launched; null pointers, a leading dimension below its row length or a
+ * misaligned workspace PTD_ERR_INVALID; a short workspace PTD_ERR_WORKSPACE.  The workspace holds the slabs (S > 1) and
+ * h.  Which T and shapes the Python package sends here is measured (profiles/pair_tile_w8.json).
+ *
+ * ptd_lowrank_tile_w8_plan: what a call would do for a shape, computed on the host by the functions the launcher calls
+ * (no GPU, no launch): out[PTD_TILE_W8_PLAN_*] -- the tile shape (weight rows x tokens) and the tile count of each
+ * product, S and the K range of a slab.  out holds cap >= PTD_TILE_W8_PLAN_LEN values.  PTD_ERR_UNSUPPORTED for a shape
+ * the entry does not serve (contiguous, aligned operands assumed), PTD_ERR_INVALID for a null or short out.
+ * No reference counterpart. */
+#define PTD_LOWRANK_TILE_W8_MIN_T 17
+#define PTD_TILE_W8_PLAN_XA_BN 0      /* first product: weight rows of a tile */
+#define PTD_TILE_W8_PLAN_XA_BT 1      /* ... its tokens */
+#define PTD_TILE_W8_PLAN_NSLABS 2     /* S */
+#define PTD_TILE_W8_PLAN_KSLAB 3      /* k of a slab (the last one may be shorter); a multiple of 64 */
+#define PTD_TILE_W8_PLAN_XA_TILES 4   /* tiles of the first product (its grid is tiles x S) */
+#define PTD_TILE_W8_PLAN_HB_BN 5      /* second product: weight rows of a tile */
+#define PTD_TILE_W8_PLAN_HB_BT 6      /* ... its tokens */
+#define PTD_TILE_W8_PLAN_HB_TILES 7   /* tiles (= workgroups) of the second product */
+#define PTD_TILE_W8_PLAN_LEN 8
+size_t ptd_lowrank_tile_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype);
+int ptd_lowrank_tile_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                        const void* Aq, int64_t lda, const float* scale_a, int64_t r,
+                        const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o, const void* bias,
+                        void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+int ptd_lowrank_tile_w8_plan(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap);
 
 /* MXFP8 activations on the block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4): OPT-IN entries beside the ones above,
  * because quantising the activations changes numerics.  D = bf16 / f16.

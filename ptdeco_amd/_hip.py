@@ -152,6 +152,9 @@ SIGNATURES = {
     "ptd_lowrank_tile_w4": _PAIR_MX,
     "ptd_lowrank_tile_w6_workspace_bytes": _TILE_WS,
     "ptd_lowrank_tile_w6": _PAIR_MX,
+    "ptd_lowrank_tile_w8_workspace_bytes": _TILE_WS,
+    "ptd_lowrank_tile_w8": _PAIR_FP8,
+    "ptd_lowrank_tile_w8_plan": (c_int, [c_int64, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),
     "ptd_mxfp8_quantize_rows": _MXFP8_QUANTIZE,
     "ptd_mx_product_a8": _MX_PRODUCT_A8,
     "ptd_lowrank_a8_w4_workspace_bytes": _TILE_WS,

@@ -22,8 +22,10 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
                                                              the pair with fp8 (e4m3fn) factors and f32 row scales:
                                                              ops.lowrank_decode_w8 where ops.lowrank_decode_w8_serves
                                                              (T <= 16), ops.lowrank_skinny_w8 where
-                                                             ops.lowrank_skinny_w8_serves (32 ... 96), else the torch
-                                                             expression on 16-bit copies
+                                                             ops.lowrank_skinny_w8_serves (32 ... 96),
+                                                             ops.lowrank_tile_w8 where ops.lowrank_tile_w8_serves
+                                                             (17 ... 31 and above 96, where measured to win),
+                                                             else the torch expression on 16-bit copies
     lowrank_forward_w4(Tensor x2d, Tensor Aq, Tensor ea, Tensor Bq, Tensor eb, Tensor? bias) -> Tensor
                                                              the pair with OCP MXFP4 factors (packed e2m1 codes, e8m0
                                                              block scales): ops.lowrank_decode_w4 where
@@ -223,10 +225,12 @@ def lowrank_forward_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq
     [n_o] f32 scales per factor row, bias [n_o] of x2d's dtype or None; y [T, n_o] contiguous,
     y = round(sb * (h Bq^T) + bias) with h = round(sa * (x2d Aq^T)).  At decode shapes (1 <= T <= 16, aligned operands:
     ops.lowrank_decode_w8_serves) on the weight-streaming kernels of ptd_lowrank_decode_w8, at small batches (32 <= T <=
-    96: ops.lowrank_skinny_w8_serves) on the skinny products of ptd_lowrank_skinny_w8; both keep the sums in f32 and
-    round h and y once each.  Elsewhere ``lowrank_w8_expression``: torch's products on transient 16-bit copies of the
-    factors, which round once more than the kernels do, inside ``F.linear``.  Inference only: no autograd formula."""
-    return _route_q("w8", ("decode", "skinny"), lowrank_w8_expression, x2d, Aq, sa, Bq, sb, bias)
+    96: ops.lowrank_skinny_w8_serves) on the skinny products of ptd_lowrank_skinny_w8, where ops.lowrank_tile_w8_serves
+    (17 ... 31 and above 96 tokens, in the classes it is measured to win) on the tiled W8A16 products of
+    ptd_lowrank_tile_w8; all three keep the sums in f32, apply the row scale to the finished sum and round h and y once
+    each.  Elsewhere ``lowrank_w8_expression``: torch's products on transient 16-bit copies of the factors, which round
+    once more than the kernels do, inside ``F.linear``.  Inference only: no autograd formula."""
+    return _route_q("w8", ("decode", "skinny", "tile"), lowrank_w8_expression, x2d, Aq, sa, Bq, sb, bias)
 
 
 def _w8_fake(op, x2d, Aq, sa, Bq, sb, bias):
@@ -502,7 +506,7 @@ def _(x2d, Aq, ea, Bq, eb, bias):
 # What the grouped and gated operators of quantised members need of a format (``fmt``: the names of ops._Q_FORMATS): the
 # tag, the regimes and the expression of the member's own operator, and its fake kernel's checks.
 _Q_MEMBER = {
-    "fp8": ("w8", ("decode", "skinny"), lowrank_w8_expression, _w8_fake),
+    "fp8": ("w8", ("decode", "skinny", "tile"), lowrank_w8_expression, _w8_fake),
     "MXFP4": ("w4", ("decode", "skinny", "tile"), lowrank_w4_expression,
               lambda op, *w: _mx_fake(op, lambda n: n // 2, "Aq [r, n_i / 2], Bq [n_o, r / 2]", *w)),
     "MXFP6": ("w6", ("decode", "skinny", "tile"), lowrank_w6_expression,

@@ -921,6 +921,43 @@ int ptd_lowrank_skinny_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, co
                            static_cast<hipStream_t>(stream));
 }
 
+size_t ptd_lowrank_tile_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype) {
+  (void)n_o;
+  (void)dtype;
+  return lowrank_tile_w8_workspace_bytes(T, n_i, r);
+}
+
+int ptd_lowrank_tile_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                        const float* scale_a, int64_t r, const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o,
+                        const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format,
+                        void* stream) {
+  const int rc = q_entry_checks("ptd_lowrank_tile_w8", x, ldx, T, n_i, Aq, lda, scale_a, 0, r, Bq, ldb, scale_b, 0, n_o, y,
+                                ldy, ws, ws_bytes, dtype, w_format, n_i, r, false,
+                                lowrank_tile_w8_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, scale_a, Bq, ldb,
+                                                       scale_b, bias),
+                                "PTD_W8_FP8_E4M3, T >= " PTD_STR(PTD_LOWRANK_TILE_W8_MIN_T)
+                                ", r >= 16, n_i and r multiples of 16, 16-byte aligned rows",
+                                lowrank_tile_w8_workspace_bytes(T, n_i, r));
+  if (rc != PTD_OK) return rc;
+  return lowrank_tile_w8(x, ldx, T, n_i, Aq, lda, scale_a, r, Bq, ldb, scale_b, n_o, bias, y, ldy, ws, dtype,
+                         static_cast<hipStream_t>(stream));
+}
+
+int ptd_lowrank_tile_w8_plan(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap) {
+  PTD_REQUIRE(out, "ptd_lowrank_tile_w8_plan: null pointer");
+  PTD_REQUIRE(cap >= PTD_TILE_W8_PLAN_LEN, "ptd_lowrank_tile_w8_plan: out holds %d values, the plan has %d", cap,
+              PTD_TILE_W8_PLAN_LEN);
+  // (the operands of a plan are contiguous and aligned: address 0 passes every alignment test of the serving rule)
+  if (!lowrank_tile_w8_serves(T, n_i, r, n_o, dtype, PTD_W8_FP8_E4M3, nullptr, n_i, nullptr, n_i, nullptr, nullptr, r,
+                              nullptr, nullptr)) {
+    set_error("ptd_lowrank_tile_w8_plan: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d)", (long long)T,
+              (long long)n_i, (long long)r, (long long)n_o, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  lowrank_tile_w8_plan(T, n_i, r, n_o, out);
+  return PTD_OK;
+}
+
 size_t ptd_lowrank_skinny_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
   return lowrank_skinny_w4_workspace_bytes(T, n_i, r, dtype);
 }

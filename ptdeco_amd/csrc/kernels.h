@@ -318,6 +318,19 @@ int lowrank_a8_tile_w6(const void* x, int64_t ldx, int64_t T, int64_t n_i, const
                        int64_t ldsa, int64_t r, const void* Bq, int64_t ldb, const void* eb, int64_t ldsb, int64_t n_o,
                        const void* bias, void* y, int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_tile_w8.hip: the fp8 pair of lowrank_skinny_w8.hip at every T >= 17 as two tiled W8A16 products (activations
+// through LDS, codes streamed and converted in registers, row scales on the f32 sums), the first with a K split into f32
+// slabs where its tiles do not fill the chip (ptd_lowrank_tile_w8).  lowrank_tile_w8_plan: out[PTD_TILE_W8_PLAN_*] of a
+// served shape
+bool lowrank_tile_w8_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x,
+                            int64_t ldx, const void* Aq, int64_t lda, const float* sa, const void* Bq, int64_t ldb,
+                            const float* sb, const void* bias);
+size_t lowrank_tile_w8_workspace_bytes(int64_t T, int64_t n_i, int64_t r);
+void lowrank_tile_w8_plan(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int32_t* out);
+int lowrank_tile_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const float* sa,
+                    int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
+                    int64_t ldy, void* ws, int dtype, hipStream_t st);
+
 // lowrank_plan.hip: what a launch of one serving family would do, from the host rules the launchers call (ptd_lowrank_plan);
 // fills out[PTD_PLAN_*], PTD_OK or PTD_ERR_UNSUPPORTED
 int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out);

@@ -559,7 +559,7 @@ class _QFormat:
 
 
 _FP8 = _QFormat("fp8", "w8", W8_FP8_E4M3, 8, torch.float8_e4m3fn, torch.float32, 1, 4, 16, 0,
-                {"decode": (16, 16), "skinny": (16, 16)})
+                {"decode": (16, 16), "skinny": (16, 16)})      # (its tile entry takes the skinny entry's operands)
 _MXFP4 = _QFormat("MXFP4", "w4", W4_MXFP4, 4, torch.uint8, torch.uint8, 2, 1, 32, 32,
                   {"decode": (16, 16), "skinny": (8, 8), "tile": (8, 8)})      # (skinny: a lane's piece is half a block)
 _MXFP6 = _QFormat("MXFP6", "w6", W6_MXFP6_E2M3, 6, torch.uint8, torch.uint8, 2, 1, 32, 32,
@@ -587,7 +587,8 @@ def _q_operands(fmt: _QFormat, regime: str, x: _Facts, Aq: _Facts, ea: _Facts, B
     if bias is not None and (len(bias.shape) != 1 or bias.shape[0] != n_o or bias.dtype != x.dtype
                              or (n_o > 1 and bias.stride[0] != 1)):
         return False
-    for t, (vec, align) in ((x, (8, 16)), (Aq, fmt.pitch[regime]), (Bq, fmt.pitch[regime])):
+    pitch = fmt.pitch.get(regime, fmt.pitch["skinny"])
+    for t, (vec, align) in ((x, (8, 16)), (Aq, pitch), (Bq, pitch)):
         if t.stride[1] != 1 or t.stride[0] < t.shape[1] or t.stride[0] % vec or t.ptr % align:
             return False
     for e in (ea, eb):      # (unit inner stride; scale rows need no alignment, row scales that of an f32)
@@ -607,6 +608,8 @@ def _q_rule(fmt: _QFormat, regime: str, x: _Facts, Aq: _Facts, ea: _Facts, Bq: _
         return 1 <= T <= _DECODE_MAX_T
     if regime == "skinny":
         return _SKINNY_MIN_T <= T <= globals()[fmt.skinny_cap]
+    if fmt is _FP8:
+        return _tile_w8_takes(T, x.shape[1], Aq.shape[0], Bq.shape[0])
     return _tile_mx_takes(fmt, T, x.shape[1], Bq.shape[0])
 
 
@@ -1256,6 +1259,56 @@ def lowrank_tile_w6(x2d: torch.Tensor, Aq: torch.Tensor, ea: torch.Tensor, Bq: t
     workspace (exactly), the 16-bit tile pair runs on them.  The bits of ``lowrank_forward(x2d, A^, B^, bias)``.
     Operands the C entry does not serve raise."""
     return _q_call(_MXFP6, "tile", x2d, Aq, ea, Bq, eb, bias)
+
+
+# The fp8 pair at every other token count (17 <= T < _SKINNY_MIN_T and T > _SKINNY_W8_MAX_T: prompt processing) runs on
+# ptd_lowrank_tile_w8 (csrc/lowrank_tile_w8.hip): two tiled W8A16 products of its own -- activations through LDS, the
+# e4m3 codes streamed into registers and converted there, the row scale on the finished f32 sum -- with the first
+# product's K range cut into f32 slabs where its tiles do not fill the chip.  h and y are rounded once each, as the decode
+# and skinny fp8 kernels round them; capturable in a graph.  PTD_LOWRANK_TILE_W8=0 sends these T through the torch
+# expression again.  The rule is on T and the shapes alone, whatever the decode and skinny switches say, and admits the
+# classes the measurement shows are won (profiles/pair_tile_w8.json; ``_tile_w8_takes``); what it excludes keeps the
+# expression (the C entry serves it all the same).
+_TILE_W8 = os.environ.get("PTD_LOWRANK_TILE_W8", "1") != "0"
+_TILE_W8_MIN_T = _DECODE_MAX_T + 1
+_TILE_W8_MAX_XA = 1 << 33
+_TILE_W8_PLAN_FIELDS = ("xa_bn", "xa_bt", "nslabs", "kslab", "xa_tiles", "hb_bn", "hb_bt", "hb_tiles")
+
+
+def _tile_w8_takes(T: int, n_i: int, r: int, n_o: int) -> bool:
+    """The (T, shape) cells ptd_lowrank_tile_w8 owns: every T the decode and skinny fp8 kernels leave, as long as the first
+    product is at most _TILE_W8_MAX_XA = 2^33 multiply-adds -- the largest measured as won (4096 -> 1024 at T = 2048, 0.74
+    of the expression's time); the one cell measured beyond it (14336 -> 1024 at T = 2048, 3.0e10) is lost at 1.05."""
+    if T * r * n_i > _TILE_W8_MAX_XA:
+        return False
+    return _TILE_W8_MIN_T <= T < _SKINNY_MIN_T or T > _SKINNY_W8_MAX_T
+
+
+def lowrank_tile_w8_serves(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                           bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``lowrank_tile_w8`` takes these operands as they lie (without loading the library): the operands of
+    ``lowrank_skinny_w8_serves`` at 17 <= T < _SKINNY_MIN_T and at T > _SKINNY_W8_MAX_T, in the measured classes of
+    ``_tile_w8_takes`` -- by T and the shapes alone, whatever the decode and skinny switches say."""
+    return _q_serves(_FP8, "tile", x2d, Aq, sa, Bq, sb, bias)
+
+
+def lowrank_tile_w8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                    bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """round(sb * (h @ Bq^T) + bias) with h = round(sa * (x2d @ Aq^T)) for T >= 17 rows of x2d (bf16 / f16), the fp8
+    factors of ``lowrank_skinny_w8``: ptd_lowrank_tile_w8, two tiled products on the stored codes (sums in f32, each
+    scaled in f32 and rounded once to x2d's dtype), two or three launches on x2d's stream and no host read: safe under
+    graph capture.  Operands the C entry does not serve raise; row t of the result depends on row t of x2d alone."""
+    return _q_call(_FP8, "tile", x2d, Aq, sa, Bq, sb, bias)
+
+
+def lowrank_tile_w8_plan(T: int, n_i: int, r: int, n_o: int, dtype: torch.dtype = torch.bfloat16) -> dict:
+    """What ``lowrank_tile_w8`` would launch for a shape (ptd_lowrank_tile_w8_plan; host only, no GPU): the tile shape
+    (weight rows ``*_bn`` x tokens ``*_bt``) and tile count of the first (``xa_``) and second (``hb_``) product, the slab
+    count ``nslabs`` (S) and the K range of a slab ``kslab``.  A shape the entry does not serve raises."""
+    out = (ctypes.c_int32 * len(_TILE_W8_PLAN_FIELDS))()
+    rc = _hip.load().ptd_lowrank_tile_w8_plan(T, n_i, r, n_o, _DT[dtype], out, len(out))
+    _hip.check(rc, "ptd_lowrank_tile_w8_plan")
+    return dict(zip(_TILE_W8_PLAN_FIELDS, out))
 
 
 # MXFP8 activations on the block-scaled MFMA (csrc/lowrank_a8.hip).  OPT-IN (``activations="mxfp8"`` on a LowRankLinearW4 /
