@@ -66,7 +66,10 @@ extern "C" {
                              *    ptd_nsr_plan,
                              *    ptd_gemm_f64_form,
                              *    ptd_lowrank_skinny_group_workspace_bytes, ptd_lowrank_skinny_group,
-                             *    ptd_lowrank_tile_w8_workspace_bytes, ptd_lowrank_tile_w8, ptd_lowrank_tile_w8_plan) */
+                             *    ptd_lowrank_tile_w8_workspace_bytes, ptd_lowrank_tile_w8, ptd_lowrank_tile_w8_plan,
+                             *    ptd_lowrank_tile_group_q_workspace_bytes, ptd_lowrank_tile_group_q,
+                             *    ptd_lowrank_tile_gated_q_workspace_bytes, ptd_lowrank_tile_gated_q,
+                             *    ptd_lowrank_tile_group_q_plan) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -712,6 +715,73 @@ int ptd_lowrank_tile_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                         const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o, const void* bias,
                         void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 int ptd_lowrank_tile_w8_plan(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap);
+
+/* 1 <= count <= PTD_LOWRANK_GROUP_MAX fp8 pairs that read the same x at the token counts of ptd_lowrank_tile_w8 (the
+ * q / k / v or gate / up projections of a block at prompt sizes; arguments of ptd_lowrank_skinny_group_q, q_format
+ * PTD_Q_FP8_E4M3 alone: ldsa and ldsb are ignored and may be NULL), in THREE launches on the caller's stream
+ * (csrc/lowrank_tile_group_q.hip): every member's first product in one grid -- the members' (tile, slab) items laid end
+ * to end, each member with the S and the slab length ptd_lowrank_tile_w8 gives it alone --, one slab sum over the
+ * members with S > 1 (skipped when there is none: TWO launches), every member's second product in one grid, stored
+ * straight into y[m] with pitch ldy[m].  Member m's output is bit for bit what ptd_lowrank_tile_w8 writes for that member
+ * alone, signed zeros included; row t depends on row t of x alone; no atomics, one writer per element, no host read:
+ * capturable in a graph.  Served when every member is served by ptd_lowrank_tile_w8 with the common x, T, n_i and dtype,
+ * every n_o is a multiple of 4, every y[m] is 8-byte aligned with ldy[m] a multiple of 4 (every element then takes the
+ * 8-byte store form, as the member alone does in a contiguous [T, n_o] result: the f16 rounding of the two store forms
+ * is not the same instruction sequence), T sum r < 2^34 and T sum max(n_o, 16) < 2^38 (the grids laid end to end);
+ * anything else, PTD_Q_MXFP4 /
+ * PTD_Q_MXFP6_E2M3 and count outside 1 .. PTD_LOWRANK_GROUP_MAX included, returns PTD_ERR_UNSUPPORTED before a kernel is
+ * launched.  Null pointers, a leading dimension below its row length or a misaligned workspace PTD_ERR_INVALID; a short
+ * workspace PTD_ERR_WORKSPACE.  The workspace is the sum of the members' ptd_lowrank_tile_w8 workspaces.
+ *
+ * ptd_lowrank_tile_gated_q: y = act(gate(x)) * up(x) for two such pairs (arguments of ptd_lowrank_skinny_gated_q), the
+ * first two launches of the group on (gate, up), then one kernel in which a workgroup forms both second products for the
+ * same rows and tokens in two accumulator sets and applies the activation and the product in the lanes that hold both
+ * sums: g = round_D(sb_g * acc_g + bias_g) and u likewise are the bits of ptd_lowrank_tile_w8 on gate and up,
+ * y = round_D(round_D(act(g)) * u).  Served as the group of (gate, up) with one n_ff (a multiple of 4), y 8-byte aligned,
+ * ldy a multiple of 4 and act one of PTD_ACT_*.
+ *
+ * ptd_lowrank_tile_group_q_plan: what the two entries would do for a group, on the host (no GPU, no launch):
+ * out[PTD_TILE_GROUP_PLAN_*], then PTD_TILE_GROUP_PLAN_MEMBER_LEN values per member from PTD_TILE_GROUP_PLAN_MEMBERS on.
+ * The gated fields are those of a gated call with n_ff = n_o[0].  out holds cap >= PTD_TILE_GROUP_PLAN_LEN values.
+ * PTD_ERR_UNSUPPORTED for a group the entry does not serve (contiguous, aligned operands assumed), PTD_ERR_INVALID for a
+ * null pointer or a short out.  No reference counterpart. */
+#define PTD_TILE_GROUP_PLAN_XA_BN 0      /* first products: weight rows of a tile */
+#define PTD_TILE_GROUP_PLAN_XA_BT 1      /* ... its tokens */
+#define PTD_TILE_GROUP_PLAN_HB_BN 2      /* second products of the group: weight rows of a tile */
+#define PTD_TILE_GROUP_PLAN_HB_BT 3      /* ... its tokens */
+#define PTD_TILE_GROUP_PLAN_GATED_BN 4   /* the gated kernel: rows of B_gate and of B_up of a tile */
+#define PTD_TILE_GROUP_PLAN_GATED_BT 5   /* ... its tokens */
+#define PTD_TILE_GROUP_PLAN_XA_GRID 6    /* workgroups of the first launch */
+#define PTD_TILE_GROUP_PLAN_HB_GRID 7    /* workgroups of the group's last launch */
+#define PTD_TILE_GROUP_PLAN_LAUNCHES 8   /* 3, or 2 where every member has S = 1 */
+#define PTD_TILE_GROUP_PLAN_MEMBERS 9    /* member m's values start at MEMBERS + m * MEMBER_LEN */
+#define PTD_TILE_GROUP_PLAN_NSLABS 0     /* S of the member */
+#define PTD_TILE_GROUP_PLAN_KSLAB 1      /* k of one of its slabs */
+#define PTD_TILE_GROUP_PLAN_XA_FIRST 2   /* its first workgroup in the first launch */
+#define PTD_TILE_GROUP_PLAN_HB_FIRST 3   /* ... in the group's last launch */
+#define PTD_TILE_GROUP_PLAN_MEMBER_LEN 4
+#define PTD_TILE_GROUP_PLAN_LEN (PTD_TILE_GROUP_PLAN_MEMBERS + 4 * PTD_TILE_GROUP_PLAN_MEMBER_LEN)
+size_t ptd_lowrank_tile_group_q_workspace_bytes(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r,
+                                                int dtype);
+int ptd_lowrank_tile_group_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, int count,
+                             const void* const* Aq, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                             const int64_t* r,
+                             const void* const* Bq, const int64_t* ldb, const void* const* sb, const int64_t* ldsb,
+                             const int64_t* n_o,
+                             const void* const* bias /* entries may be NULL; the array may be NULL */,
+                             void* const* y, const int64_t* ldy,
+                             void* ws, size_t ws_bytes, int dtype, void* stream);
+size_t ptd_lowrank_tile_gated_q_workspace_bytes(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u,
+                                                int dtype);
+int ptd_lowrank_tile_gated_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                             const void* Aq_g, int64_t lda_g, const void* sa_g, int64_t ldsa_g, int64_t r_g,
+                             const void* Bq_g, int64_t ldb_g, const void* sb_g, int64_t ldsb_g, const void* bias_g,
+                             const void* Aq_u, int64_t lda_u, const void* sa_u, int64_t ldsa_u, int64_t r_u,
+                             const void* Bq_u, int64_t ldb_u, const void* sb_u, int64_t ldsb_u, const void* bias_u,
+                             int64_t n_ff, int act, void* y, int64_t ldy,
+                             void* ws, size_t ws_bytes, int dtype, void* stream);
+int ptd_lowrank_tile_group_q_plan(int count, int64_t T, int64_t n_i, const int64_t* r, const int64_t* n_o, int dtype,
+                                  int32_t* out, int cap);
 
 /* MXFP8 activations on the block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4): OPT-IN entries beside the ones above,
  * because quantising the activations changes numerics.  D = bf16 / f16.

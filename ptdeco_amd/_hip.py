@@ -155,6 +155,13 @@ SIGNATURES = {
     "ptd_lowrank_tile_w8_workspace_bytes": _TILE_WS,
     "ptd_lowrank_tile_w8": _PAIR_FP8,
     "ptd_lowrank_tile_w8_plan": (c_int, [c_int64, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),
+    "ptd_lowrank_tile_group_q_workspace_bytes": _GROUP_Q_WS,
+    "ptd_lowrank_tile_group_q": _GROUP_Q,
+    "ptd_lowrank_tile_gated_q_workspace_bytes": _GATED_Q_WS,
+    "ptd_lowrank_tile_gated_q": _GATED_Q,
+    # count, T, n_i, r[], n_o[], dtype, out, cap
+    "ptd_lowrank_tile_group_q_plan": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_int,
+                                              ctypes.POINTER(ctypes.c_int32), c_int]),
     "ptd_mxfp8_quantize_rows": _MXFP8_QUANTIZE,
     "ptd_mx_product_a8": _MX_PRODUCT_A8,
     "ptd_lowrank_a8_w4_workspace_bytes": _TILE_WS,

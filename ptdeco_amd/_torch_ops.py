@@ -516,9 +516,9 @@ _Q_MEMBER = {
 
 def _route_fused_q(kind, fmt, *operands):
     """The fused entry of quantised members that serves them: ops.lowrank_<regime>_<kind>_serves, then
-    ops.lowrank_<regime>_<kind> (``kind`` "group_q" or "gated_q"; both looked up when the body runs), decode before
-    skinny; None where neither takes the operands as they lie."""
-    for regime in ("decode", "skinny"):
+    ops.lowrank_<regime>_<kind> (``kind`` "group_q" or "gated_q"; both looked up when the body runs), decode, then
+    skinny, then tile (fp8 alone); None where none takes the operands as they lie."""
+    for regime in ("decode", "skinny", "tile"):
         if getattr(ops, f"lowrank_{regime}_{kind}_serves")(fmt, *operands):
             return getattr(ops, f"lowrank_{regime}_{kind}")(fmt, *operands)
     return None
@@ -538,7 +538,9 @@ def lowrank_forward_group_q(x2d: torch.Tensor, Aqs: List[torch.Tensor], sas: Lis
     _w4 / _w6 -- in columns [off_m, off_m + n_o_m).  At decode shapes two launches for the group
     (ops.lowrank_decode_group_q_serves: ptd_lowrank_decode_group_q, every member's bits those of its own decode entry),
     at 32 to 96 tokens three (ops.lowrank_skinny_group_q_serves: ptd_lowrank_skinny_group_q, the bits of its own skinny
-    entry); otherwise each member as its own operator runs it.  Inference only: no autograd formula."""
+    entry), fp8 members at 17 to 31 and above 96 tokens three or two (ops.lowrank_tile_group_q_serves:
+    ptd_lowrank_tile_group_q, the bits of ptd_lowrank_tile_w8); otherwise each member as its own operator runs it.
+    Inference only: no autograd formula."""
     if fmt not in _Q_MEMBER:
         raise ValueError(f"fmt must be one of {sorted(_Q_MEMBER)}, got {fmt!r}")
     y = _route_fused_q("group_q", fmt, x2d, Aqs, sas, Bqs, sbs, biases)
@@ -574,8 +576,9 @@ def lowrank_forward_gated_q(x2d: torch.Tensor, Aq_g: torch.Tensor, s_a_g: torch.
     per member as in lowrank_forward_group_q), act "silu", "gelu_tanh" or "relu": y [T, n_ff] contiguous.  At decode
     shapes two launches (ops.lowrank_decode_gated_q_serves: ptd_lowrank_decode_gated_q; g and u are the members' own
     bits, the activation is the kernel's), at 32 to 96 tokens three (ops.lowrank_skinny_gated_q_serves:
-    ptd_lowrank_skinny_gated_q, likewise); otherwise g and u as each member's own operator forms them and torch's own
-    activation and product.  Inference only: no autograd formula."""
+    ptd_lowrank_skinny_gated_q, likewise), fp8 members at 17 to 31 and above 96 tokens three or two
+    (ops.lowrank_tile_gated_q_serves: ptd_lowrank_tile_gated_q, likewise); otherwise g and u as each member's own
+    operator forms them and torch's own activation and product.  Inference only: no autograd formula."""
     if fmt not in _Q_MEMBER:
         raise ValueError(f"fmt must be one of {sorted(_Q_MEMBER)}, got {fmt!r}")
     if act not in GATE_ACTS:

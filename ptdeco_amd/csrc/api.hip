@@ -958,6 +958,73 @@ int ptd_lowrank_tile_w8_plan(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int
   return PTD_OK;
 }
 
+size_t ptd_lowrank_tile_group_q_workspace_bytes(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r,
+                                                int dtype) {
+  if (!r || count < 1 || count > PTD_LOWRANK_GROUP_MAX) return 0;
+  return lowrank_tile_group_q_workspace_bytes(q_format, count, T, n_i, r, dtype);
+}
+
+int ptd_lowrank_tile_group_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, int count,
+                             const void* const* Aq, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                             const int64_t* r, const void* const* Bq, const int64_t* ldb, const void* const* sb,
+                             const int64_t* ldsb, const int64_t* n_o, const void* const* bias, void* const* y,
+                             const int64_t* ldy, void* ws, size_t ws_bytes, int dtype, void* stream) {
+  const int rc = q_group_entry_checks("ptd_lowrank_tile_group_q", "tile", lowrank_tile_group_q_serves,
+                                      lowrank_tile_group_q_workspace_bytes, q_format, x, ldx, T, n_i, count, Aq, lda, sa,
+                                      ldsa, r, Bq, ldb, sb, ldsb, n_o, bias, y, ldy, ws, ws_bytes, dtype);
+  if (rc != PTD_OK) return rc;
+  for (int m = 0; m < count; ++m)
+    if (!lowrank_tile_q_stores(y[m], ldy[m])) {
+      set_error("ptd_lowrank_tile_group_q: not served (member %d: y must be 8-byte aligned and ldy a multiple of 4)", m);
+      return PTD_ERR_UNSUPPORTED;
+    }
+  return lowrank_tile_group_q(x, ldx, T, n_i, count, Aq, lda, sa, r, Bq, ldb, sb, n_o, bias, y, ldy, ws, dtype,
+                              static_cast<hipStream_t>(stream));
+}
+
+size_t ptd_lowrank_tile_gated_q_workspace_bytes(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u,
+                                                int dtype) {
+  return lowrank_tile_gated_q_workspace_bytes(q_format, T, n_i, r_g, r_u, dtype);
+}
+
+int ptd_lowrank_tile_gated_q(int q_format, const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq_g,
+                             int64_t lda_g, const void* sa_g, int64_t ldsa_g, int64_t r_g, const void* Bq_g,
+                             int64_t ldb_g, const void* sb_g, int64_t ldsb_g, const void* bias_g, const void* Aq_u,
+                             int64_t lda_u, const void* sa_u, int64_t ldsa_u, int64_t r_u, const void* Bq_u,
+                             int64_t ldb_u, const void* sb_u, int64_t ldsb_u, const void* bias_u, int64_t n_ff, int act,
+                             void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, void* stream) {
+  const int rc = q_gated_entry_checks("ptd_lowrank_tile_gated_q", "tile", lowrank_tile_gated_q_serves,
+                                      lowrank_tile_gated_q_workspace_bytes, q_format, x, ldx, T, n_i, Aq_g, lda_g, sa_g,
+                                      ldsa_g, r_g, Bq_g, ldb_g, sb_g, ldsb_g, bias_g, Aq_u, lda_u, sa_u, ldsa_u, r_u, Bq_u,
+                                      ldb_u, sb_u, ldsb_u, bias_u, n_ff, act, y, ldy, ws, ws_bytes, dtype);
+  if (rc != PTD_OK) return rc;
+  if (!lowrank_tile_q_stores(y, ldy)) {
+    set_error("ptd_lowrank_tile_gated_q: not served (y must be 8-byte aligned and ldy a multiple of 4)");
+    return PTD_ERR_UNSUPPORTED;
+  }
+  return lowrank_tile_gated_q(x, ldx, T, n_i, Aq_g, lda_g, sa_g, r_g, Bq_g, ldb_g, sb_g, bias_g, Aq_u, lda_u, sa_u, r_u, Bq_u,
+                              ldb_u, sb_u, bias_u, n_ff, act, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
+}
+
+int ptd_lowrank_tile_group_q_plan(int count, int64_t T, int64_t n_i, const int64_t* r, const int64_t* n_o, int dtype,
+                                  int32_t* out, int cap) {
+  PTD_REQUIRE(r && n_o && out, "ptd_lowrank_tile_group_q_plan: null pointer");
+  PTD_REQUIRE(cap >= PTD_TILE_GROUP_PLAN_LEN, "ptd_lowrank_tile_group_q_plan: out holds %d values, the plan has %d", cap,
+              PTD_TILE_GROUP_PLAN_LEN);
+  // (the operands of a plan are contiguous and aligned: address 0 passes every alignment test of the serving rule)
+  const void* const null4[PTD_LOWRANK_GROUP_MAX] = {nullptr, nullptr, nullptr, nullptr};
+  int64_t lda[PTD_LOWRANK_GROUP_MAX] = {n_i, n_i, n_i, n_i}, ldb[PTD_LOWRANK_GROUP_MAX] = {0, 0, 0, 0};
+  for (int m = 0; m < count && m < PTD_LOWRANK_GROUP_MAX; ++m) ldb[m] = r[m];
+  if (!lowrank_tile_group_q_serves(PTD_Q_FP8_E4M3, count, T, n_i, r, n_o, dtype, nullptr, n_i, null4, lda, null4, null4, ldb,
+                                   null4, null4)) {
+    set_error("ptd_lowrank_tile_group_q_plan: not served (count=%d T=%lld n_i=%lld dtype=%d)", count, (long long)T,
+              (long long)n_i, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  lowrank_tile_group_q_plan(count, T, n_i, r, n_o, out);
+  return PTD_OK;
+}
+
 size_t ptd_lowrank_skinny_w4_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
   return lowrank_skinny_w4_workspace_bytes(T, n_i, r, dtype);
 }

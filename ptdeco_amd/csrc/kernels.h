@@ -331,6 +331,34 @@ int lowrank_tile_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const vo
                     int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
                     int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_tile_group_q.hip: 1 .. PTD_LOWRANK_GROUP_MAX fp8 pairs on one input at the token counts of lowrank_tile_w8 in
+// three launches (two where no member has slabs), every member's bits those of lowrank_tile_w8 on that member alone
+// (ptd_lowrank_tile_group_q), and act(gate x) * up x for two of them with both second products in one workgroup
+// (ptd_lowrank_tile_gated_q).  q_format other than PTD_Q_FP8_E4M3: not served.  lowrank_tile_group_q_plan:
+// out[PTD_TILE_GROUP_PLAN_*] of a served group
+bool lowrank_tile_group_q_serves(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r, const int64_t* n_o,
+                                 int dtype, const void* x, int64_t ldx, const void* const* Aq, const int64_t* lda,
+                                 const void* const* sa, const void* const* Bq, const int64_t* ldb, const void* const* sb,
+                                 const void* const* bias);
+size_t lowrank_tile_group_q_workspace_bytes(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r, int dtype);
+bool lowrank_tile_q_stores(const void* y, int64_t ldy);
+void lowrank_tile_group_q_plan(int count, int64_t T, int64_t n_i, const int64_t* r, const int64_t* n_o, int32_t* out);
+int lowrank_tile_group_q(const void* x, int64_t ldx, int64_t T, int64_t n_i, int count, const void* const* Aq,
+                         const int64_t* lda, const void* const* sa, const int64_t* r, const void* const* Bq,
+                         const int64_t* ldb, const void* const* sb, const int64_t* n_o, const void* const* bias,
+                         void* const* y, const int64_t* ldy, void* ws, int dtype, hipStream_t st);
+bool lowrank_tile_gated_q_serves(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int64_t n_o, int act,
+                                 int dtype, const void* x, int64_t ldx, const void* Ag, int64_t lda_g, const void* sa_g,
+                                 const void* Bg, int64_t ldb_g, const void* sb_g, const void* bias_g, const void* Au,
+                                 int64_t lda_u, const void* sa_u, const void* Bu, int64_t ldb_u, const void* sb_u,
+                                 const void* bias_u);
+size_t lowrank_tile_gated_q_workspace_bytes(int q_format, int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype);
+int lowrank_tile_gated_q(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Ag, int64_t lda_g, const void* sa_g,
+                         int64_t r_g, const void* Bg, int64_t ldb_g, const void* sb_g, const void* bias_g, const void* Au,
+                         int64_t lda_u, const void* sa_u, int64_t r_u, const void* Bu, int64_t ldb_u, const void* sb_u,
+                         const void* bias_u, int64_t n_o, int act, void* y, int64_t ldy, void* ws, int dtype,
+                         hipStream_t st);
+
 // lowrank_plan.hip: what a launch of one serving family would do, from the host rules the launchers call (ptd_lowrank_plan);
 // fills out[PTD_PLAN_*], PTD_OK or PTD_ERR_UNSUPPORTED
 int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out);

@@ -48,264 +48,30 @@
 // the sum order of an output is a function of (n_i, r, n_o, S) alone, row t of y depends on row t of x alone, and two
 // calls with equal S give equal bits for equal rows.  No atomics, one writer per element.  h is a 16-bit matrix in the
 // workspace.
-#include "common.h"
-#include "elem16.h"
-#include "kernels.h"
-#include "lowrank_w8.h"
+//
+// The statements of the kernels and the host rules for the shapes and the split are in lowrank_tile_w8_body.h, which
+// lowrank_tile_group_q.hip shares.
+#include "lowrank_tile_w8_body.h"
 
 namespace ptd {
 
 namespace {
 
-constexpr int TW_THREADS = 256;
-constexpr int TW_LINE = 128;           // bytes of a token in one K step
-constexpr int TW_MAX_SLABS = 16;
-constexpr int TW_MIN_KSLAB = 256;      // a slab is at least four K steps
-constexpr int64_t TW_FILL = 256;       // workgroups that give every CU one
-
-typedef unsigned short elem;
-typedef u32x4 u32x4_tw16 __attribute__((aligned(16)));
-typedef unsigned int u32x2_tw __attribute__((ext_vector_type(2)));
-
-struct W8Tile {
-  const unsigned char* x;        // activations [T, K] of D, pitch ldx elements, 16-byte aligned rows
-  const unsigned char* wq;       // e4m3 codes [N, K], pitch ldw bytes, 16-byte aligned rows
-  const float* scale;            // [N]
-  const elem* bias;              // [N] of D, or null
-  elem* out;                     // [T, N] of D, pitch ldo elements (the rounding epilogue)
-  float* slabs;                  // [S, T, N] f32 (the slab epilogue)
-  int64_t ldx, ldw, ldo;
-  int64_t T, N;
-  int K, kslab;                  // slab blockIdx.y sums k in [kslab blockIdx.y, min(that + kslab, K))
-  unsigned tiles_t;              // token tiles of a workgroup row
-  int vec;                       // out rows take 8-byte stores
-};
-
-__device__ __forceinline__ int tw_swz(const int t) { return ((t >> 1) & 7) ^ ((((t & 15) + 4) >> 2) & 2); }
-
 template <typename EL, int WN, int WT, int WAVES_N, bool SLAB>
 __global__ __launch_bounds__(TW_THREADS) void tile_w8_product_kernel(const W8Tile p) {
-  constexpr int WAVES_T = 4 / WAVES_N;
-  constexpr int BN = 16 * WN * WAVES_N, BT = 16 * WT * WAVES_T;
-  constexpr int PIECES = BT * 8 / TW_THREADS;                          // 16-byte pieces of a thread per step
-  constexpr int BUF = BT * TW_LINE;
-  static_assert(BT * 8 % TW_THREADS == 0, "tile shape");
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF];
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int li = lane & 15, lg = lane >> 4;
-  const int wave_n = wave % WAVES_N, wave_t = wave / WAVES_N;
-  const unsigned tile_n = blockIdx.x / p.tiles_t, tile_t = blockIdx.x - tile_n * p.tiles_t;
-  const int64_t n_base = (int64_t)tile_n * BN + wave_n * (16 * WN);
-  const int64_t t_block = (int64_t)tile_t * BT;
-  const int t_wave = wave_t * (16 * WT);                               // first token of the wave inside the tile
-  const int kbeg = (int)blockIdx.y * p.kslab;
-  const int kend = min(kbeg + p.kslab, p.K);                           // (multiples of 16: a piece is inside or outside)
-  const int steps = (kend - kbeg + W8_KSTEP - 1) / W8_KSTEP;
-
-  // what this thread stages: piece pc of tokens tid / 8 + 32 j
-  const int pc = tid & 7;
-  const unsigned char* xsrc[PIECES];
-  int xdst[PIECES];
-#pragma unroll
-  for (int j = 0; j < PIECES; ++j) {
-    const int tl = (tid >> 3) + 32 * j;
-    xsrc[j] = p.x + min(t_block + tl, p.T - 1) * p.ldx * 2;
-    xdst[j] = tl * TW_LINE + ((pc ^ tw_swz(tl)) << 4);
-  }
-  const unsigned char* wrow[WN];
-#pragma unroll
-  for (int w = 0; w < WN; ++w) wrow[w] = p.wq + min(n_base + 16 * w + li, p.N - 1) * p.ldw;
-
-  // where this lane reads its fragments: pieces 2 g and 2 g + 1 of token li of each token tile
-  int frag_lo[WT], frag_hi[WT];
-#pragma unroll
-  for (int t = 0; t < WT; ++t) {
-    const int tl = t_wave + 16 * t + li, sw = tw_swz(tl);
-    frag_lo[t] = tl * TW_LINE + (((2 * lg) ^ sw) << 4);
-    frag_hi[t] = tl * TW_LINE + (((2 * lg + 1) ^ sw) << 4);
-  }
-
+  using Tile = TwTile<EL, WN, WT, WAVES_N>;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[Tile::LDS_BYTES];
+  Tile tl;
   f32x4 acc[WN][WT];
-#pragma unroll
-  for (int w = 0; w < WN; ++w)
-#pragma unroll
-    for (int t = 0; t < WT; ++t) acc[w][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  u32x4 xs[PIECES];
-  u32x4 wr[WN];
-  const u32x4 zero4 = {0u, 0u, 0u, 0u};
-
-  // the loads of step s: every one from an address inside the row, what lies beyond the K range replaced in registers
-  auto load_x = [&](const int s) {
-    const int k = kbeg + s * W8_KSTEP + 8 * pc;
-    const bool live = k < kend;
-    const int64_t off = live ? 2 * (int64_t)k : 0;
-#pragma unroll
-    for (int j = 0; j < PIECES; ++j) {
-      const u32x4 v = *reinterpret_cast<const u32x4_tw16*>(xsrc[j] + off);
-      xs[j] = live ? v : zero4;
-    }
-  };
-  auto store_x = [&](unsigned char* buf) {
-#pragma unroll
-    for (int j = 0; j < PIECES; ++j) *reinterpret_cast<u32x4_tw16*>(buf + xdst[j]) = xs[j];
-  };
-  auto load_w = [&](const int s) {
-    const int k = kbeg + s * W8_KSTEP + W8_VEC * lg;
-    const bool live = k < kend;
-    const int64_t off = live ? k : 0;
-#pragma unroll
-    for (int w = 0; w < WN; ++w) {
-      const u32x4 v = *reinterpret_cast<const u32x4_tw16*>(wrow[w] + off);
-      wr[w] = live ? v : zero4;
-    }
-  };
-
-  load_x(0);
-  load_w(0);
-  store_x(lds);
-  __syncthreads();
-
-  // one K step on the buffer `cur`: the weight operands from the registers load_w filled (then free for the next step's
-  // loads, which `ahead` issues before the fragment reads), the activation fragments from LDS, the MFMAs
-  auto step = [&](const unsigned char* cur, auto ahead) {
-    s16x8 a_lo[WN], a_hi[WN];
-#pragma unroll
-    for (int w = 0; w < WN; ++w) w8_operands<EL>(wr[w], a_lo[w], a_hi[w]);
-    ahead();
-    s16x8 x_lo[WT], x_hi[WT];
-#pragma unroll
-    for (int t = 0; t < WT; ++t) {
-      x_lo[t] = __builtin_bit_cast(s16x8, *reinterpret_cast<const u32x4_tw16*>(cur + frag_lo[t]));
-      x_hi[t] = __builtin_bit_cast(s16x8, *reinterpret_cast<const u32x4_tw16*>(cur + frag_hi[t]));
-    }
-#pragma unroll
-    for (int w = 0; w < WN; ++w)
-#pragma unroll
-      for (int t = 0; t < WT; ++t) {
-        acc[w][t] = EL::mfma16(a_lo[w], x_lo[t], acc[w][t]);
-        acc[w][t] = EL::mfma16(a_hi[w], x_hi[t], acc[w][t]);
-      }
-  };
-  // (the last step is peeled so that the loop body is one basic block: the scheduling barrier then keeps the stores, and
-  // the wait for step s + 1's loads with them, behind step s's MFMAs)
-  for (int s = 0; s + 1 < steps; ++s) {
-    step(lds + (s & 1) * BUF, [&] {
-      load_x(s + 1);
-      load_w(s + 1);
-    });
-    __builtin_amdgcn_sched_barrier(0);
-    store_x(lds + ((s + 1) & 1) * BUF);
-    __syncthreads();
-  }
-  step(lds + ((steps - 1) & 1) * BUF, [] {});
-  // the accumulators are pinned here, in uniform control flow: the last step's MFMAs must not sink into the epilogue's
-  // per-lane branches (lowrank_a8_tile.hip says why)
-#pragma unroll
-  for (int w = 0; w < WN; ++w)
-#pragma unroll
-    for (int t = 0; t < WT; ++t) asm volatile("" : "+v"(acc[w][t]));
-
-#pragma unroll
-  for (int w = 0; w < WN; ++w) {
-    const int64_t n0 = n_base + 16 * w + 4 * lg;
-    if (n0 >= p.N) continue;
-    float sc[4], bv[4];
-    if (!SLAB) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int64_t n = min(n0 + g, p.N - 1);
-        sc[g] = p.scale[n];
-        bv[g] = p.bias ? EL::to_f32(p.bias[n]) : 0.f;
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < WT; ++t) {
-      const int64_t tok = t_block + t_wave + 16 * t + li;
-      if (tok >= p.T) continue;
-      const f32x4 c = acc[w][t];
-      if (SLAB) {      // (N is a multiple of 16 here: the four rows exist)
-        *reinterpret_cast<f32x4*>(p.slabs + ((int64_t)blockIdx.y * p.T + tok) * p.N + n0) = c;
-      } else {
-        elem* o = p.out + tok * p.ldo + n0;
-        if (p.vec && n0 + 3 < p.N) {
-          *reinterpret_cast<u32x2_tw*>(o) = u32x2_tw{EL::pack2(c[0] * sc[0] + bv[0], c[1] * sc[1] + bv[1]),
-                                                   EL::pack2(c[2] * sc[2] + bv[2], c[3] * sc[3] + bv[3])};
-        } else {
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            if (n0 + g < p.N) o[g] = EL::from_f32(c[g] * sc[g] + bv[g]);
-        }
-      }
-    }
-  }
+  tw_accumulate(tl, lds, p, blockIdx.x, blockIdx.y, acc);
+  tl.template epilogue<SLAB>(p, blockIdx.y, acc);
 }
 
-// h = round(sa (slab_0 + slab_1 + ...)) in slab order, four elements (of one token: r is a multiple of 4) per thread
 template <typename EL>
 __global__ __launch_bounds__(TW_THREADS) void tile_w8_combine_kernel(const float* __restrict__ slabs, const int nslabs,
                                                                      const int64_t items, const float* __restrict__ sa,
                                                                      const int r4, elem* __restrict__ h) {
-  const int64_t i = (int64_t)blockIdx.x * TW_THREADS + threadIdx.x;
-  const int64_t ic = min(i, items - 1);
-  f32x4 v[TW_MAX_SLABS];
-#pragma unroll
-  for (int s = 0; s < TW_MAX_SLABS; ++s)      // (all in flight together; a slab that does not exist: the last one again)
-    v[s] = *reinterpret_cast<const f32x4*>(slabs + ((int64_t)min(s, nslabs - 1) * items + ic) * 4);
-  const int col = (int)(ic % r4) * 4;
-  f32x4 sum = v[0];
-#pragma unroll
-  for (int s = 1; s < TW_MAX_SLABS; ++s)
-    if (s < nslabs) sum += v[s];
-  if (i < items) {
-    u32x2_tw o = {EL::pack2(sum[0] * sa[col], sum[1] * sa[col + 1]), EL::pack2(sum[2] * sa[col + 2], sum[3] * sa[col + 3])};
-    *reinterpret_cast<u32x2_tw*>(h + i * 4) = o;
-  }
-}
-
-// --------------------------------------------------------------------------------------------------------- the host
-
-// The tile shapes.  The class of T comes first (128 tokens from T = 128 on, 64 above 32, else 32): a token tile wider
-// than the batch multiplies nothing.  From there the product takes the largest shape whose grid -- tiles, times the
-// slabs the first product may cut (smax) -- gives every CU a workgroup.  Where none does, the smallest shape has the
-// most workgroups and is taken if it covers a quarter of the chip; a problem too small even for that is bound by launch
-// latency whatever the tiles are, and keeps the shape of its T class.  The choice changes no bit of the result.
-constexpr int TW_SHAPES = 3;
-constexpr int TW_BN[TW_SHAPES] = {128, 64, 32};
-constexpr int TW_BT[TW_SHAPES] = {128, 64, 32};
-
-int64_t tile_w8_tiles(int s, int64_t T, int64_t N) { return ceil_div(N, TW_BN[s]) * ceil_div(T, TW_BT[s]); }
-
-int tile_w8_shape(int64_t T, int64_t N, int64_t smax) {
-  const int cls = T >= 128 ? 0 : T > 32 ? 1 : 2;
-  for (int s = cls; s < TW_SHAPES; ++s)
-    if (tile_w8_tiles(s, T, N) * smax >= TW_FILL) return s;
-  return tile_w8_tiles(TW_SHAPES - 1, T, N) * smax >= TW_FILL / 4 ? TW_SHAPES - 1 : cls;
-}
-
-// the first product's K slabs: as many as give every CU a workgroup, at most TW_MAX_SLABS, none shorter than
-// TW_MIN_KSLAB; whole K steps.  A pure function of (T, n_i, r)
-void tile_w8_split(int64_t T, int64_t n_i, int64_t r, int& shape, int& nslabs, int& kslab) {
-  const int64_t smax = std::max<int64_t>(1, std::min<int64_t>(TW_MAX_SLABS, n_i / TW_MIN_KSLAB));
-  shape = tile_w8_shape(T, r, smax);
-  const int64_t s = std::min<int64_t>(smax, ceil_div(TW_FILL, tile_w8_tiles(shape, T, r)));
-  kslab = (int)align_up((size_t)ceil_div(n_i, s), (size_t)W8_KSTEP);
-  nslabs = (int)ceil_div(n_i, kslab);
-}
-
-struct W8TileWorkspace {
-  size_t slabs, h, total;
-};
-
-W8TileWorkspace tile_w8_workspace(int64_t T, int64_t n_i, int64_t r) {
-  int shape, nslabs, kslab;
-  tile_w8_split(T, n_i, r, shape, nslabs, kslab);
-  W8TileWorkspace w;
-  w.slabs = 0;
-  w.h = nslabs > 1 ? align_up((size_t)nslabs * (size_t)T * (size_t)r * sizeof(float), 256) : 0;
-  w.total = w.h + align_up((size_t)T * (size_t)r * 2, 256);
-  return w;
+  tw_combine<EL>(slabs, nslabs, items, sa, r4, h, (int64_t)blockIdx.x * TW_THREADS + threadIdx.x);
 }
 
 #define TW_LABELS(prefix) {prefix "128x128)", prefix "64x64)", prefix "32x32)"}
@@ -324,17 +90,6 @@ int launch_product(const W8Tile& q, int shape, int nslabs, const char* const* wh
   hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles_n * tiles_t), (unsigned)nslabs), dim3(TW_THREADS), 0, st, p);
   PTD_CHECK_LAUNCH(what[shape]);
   return PTD_OK;
-}
-
-W8Tile w8_tile(const void* x, int64_t ldx, int64_t T, int64_t K, const void* wq, int64_t ldw, const float* scale, int64_t N,
-               const void* bias, void* out, int64_t ldo) {
-  W8Tile p;
-  p.x = static_cast<const unsigned char*>(x), p.wq = static_cast<const unsigned char*>(wq);
-  p.scale = scale, p.bias = static_cast<const elem*>(bias), p.out = static_cast<elem*>(out), p.slabs = nullptr;
-  p.ldx = ldx, p.ldw = ldw, p.ldo = ldo, p.T = T, p.N = N, p.K = (int)K, p.kslab = (int)align_up((size_t)K, W8_KSTEP);
-  p.tiles_t = 1;
-  p.vec = (out && ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0) ? 1 : 0;
-  return p;
 }
 
 template <typename EL>

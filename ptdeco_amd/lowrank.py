@@ -288,7 +288,7 @@ class LowRankLinearW4(_LowRankLinearMX):
     codes (ptd_lowrank_a8_w4).  That changes numerics: THE TOKEN COUNTS THAT TAKE THIS PATH AND THE
     OTHERS (decode among them) THEN DIFFER BY THE ACTIVATION NOISE (a noise-to-signal ratio near 2e-3 on Gaussian
     data, an order of magnitude below the weight format's own).  ``lowrank_group`` and ``lowrank_gated(quantized="fused")``
-    ignore the option: they serve 1 to 16 and 32 to 96 tokens only, so nothing collides.
+    ignore the option: they serve 1 to 16 and 32 to 96 tokens, and fp8 members alone elsewhere, so nothing collides.
 
     ``activations="mxfp8_prefill"`` (opt-in in the same places) does everything "mxfp8" does and in addition sends the
     cells of ``ops.lowrank_a8_tile_takes`` -- token counts above the skinny cap on the shapes measured as won
@@ -600,8 +600,11 @@ def lowrank_group(x: torch.Tensor, pairs, *, quantized: str = "members", small_b
     default: each runs as it does alone and the outputs are concatenated.  "fused": when all members are of ONE
     quantised class with equal in_features and activation dtype, x is a ROCm tensor of that dtype and no gradient is
     wanted, the group runs on ``torch.ops.ptdeco_amd.lowrank_forward_group_q`` -- at 1 to 16 tokens two launches for
-    the group, at 32 to 96 tokens three, every member's columns bit for bit what the member returns alone; at other
-    token counts each member as it runs alone.  A mix of formats, or a quantised member beside a 16-bit one, is the "members" path.  16-bit members
+    the group, at 32 to 96 tokens three, every member's columns bit for bit what the member returns alone; fp8 members at
+    17 to 31 and above 96 tokens (prompt processing) on the tiled kernels of ptd_lowrank_tile_group_q, three launches for
+    the group (two where no member's first product is cut into slabs), the same bits again, where every member is in the
+    classes ``LowRankLinearW8`` itself sends to ptd_lowrank_tile_w8 and every out_features is a multiple of 4; MX members at those token counts each as it runs
+    alone.  A mix of formats, or a quantised member beside a 16-bit one, is the "members" path.  16-bit members
     ignore the keyword; any other value raises ``ValueError``.
 
     ``small_batches`` says what happens to 16-bit members (``LowRankLinear``) between the decode shapes and the tile
@@ -644,8 +647,10 @@ def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu", *, quantized: st
     equal in_features, out_features and activation dtype, x is a ROCm tensor of that dtype and no gradient is wanted,
     ``torch.ops.ptdeco_amd.lowrank_forward_gated_q`` -- at 1 to 16 tokens two launches, at 32 to 96 tokens three, the
     activation evaluated by the kernel on gate's own bits: with "relu" the result is the expression's bit for bit, with "silu" and "gelu_tanh" it is
-    within the gated bound of it (the kernel's f32 activation against torch's, each rounded once), not its bits.  At
-    other token counts the members run as they do alone and torch applies the activation.  Anything else is the
+    within the gated bound of it (the kernel's f32 activation against torch's, each rounded once), not its bits.  fp8
+    members at 17 to 31 and above 96 tokens run on ptd_lowrank_tile_gated_q under the same contract: three launches
+    (two where neither first product is cut into slabs), both second products in one workgroup and no [T, n_ff]
+    intermediate (out_features a multiple of 4).  MX members at those token counts run as they do alone and torch applies the activation.  Anything else is the
     "members" path; 16-bit members ignore the keyword; any other value raises ``ValueError``."""
     if act not in _torch_ops.GATE_ACTS:
         raise ValueError(f"act must be one of {sorted(_torch_ops.GATE_ACTS)}, got {act!r}")
@@ -672,7 +677,8 @@ def lowrank_mlp(x: torch.Tensor, gate, up, down, act: str = "silu", *, quantized
     ``down`` as it is called alone -- at decode shapes four kernel launches in all, at 32 to 96 tokens six.
     ``quantized`` is passed to ``lowrank_gated`` (with "fused", quantised gate and up of one format run in two
     launches at decode shapes: bit for bit the module expression with "relu", within the gated bound of it with "silu"
-    and "gelu_tanh"); ``down`` runs as it does alone."""
+    and "gelu_tanh"; fp8 gate and up at prompt sizes in three on ptd_lowrank_tile_gated_q, likewise); ``down`` runs as
+    it does alone."""
     return down(lowrank_gated(x, gate, up, act, quantized=quantized))
 
 

@@ -847,6 +847,19 @@ def _q_group_rule(fmt: _QFormat, regime: str, x: _Facts, members: Sequence[Seque
     format's entry of that regime on the common x (which makes every member's n_i that of x)."""
     if not 1 <= len(members) <= _GROUP_MAX:
         return False
+    if regime == "tile":
+        # (fp8 alone: the MX formats have no product kernel of their own at these T.  Every member in the measured
+        # classes of ``_tile_w8_takes`` -- a member left to the expression rounds elsewhere -- and the grids laid end
+        # to end below 2^31 workgroups, the bounds of lowrank_tile_group_q_serves.  Every width a multiple of 4: each
+        # member then takes the 8-byte store form in the group as it does alone -- for f16 the two store forms of the
+        # tile epilogue do not round by the same instructions, so a member on another form has other bits)
+        if fmt is not _FP8 or not all(_q_rule(fmt, regime, x, *m) for m in members):
+            return False
+        if any(m[2].shape[0] % 4 for m in members):
+            return False
+        T = x.shape[0]
+        return (T * sum(m[0].shape[0] for m in members) < 1 << 34
+                and T * sum(max(m[2].shape[0], 16) for m in members) < 1 << 38)
     return all(_q_rule(fmt, regime, x, *m) for m in members)
 
 
@@ -1309,6 +1322,75 @@ def lowrank_tile_w8_plan(T: int, n_i: int, r: int, n_o: int, dtype: torch.dtype 
     rc = _hip.load().ptd_lowrank_tile_w8_plan(T, n_i, r, n_o, _DT[dtype], out, len(out))
     _hip.check(rc, "ptd_lowrank_tile_w8_plan")
     return dict(zip(_TILE_W8_PLAN_FIELDS, out))
+
+
+# fp8 pairs that read one input at these token counts (q / k / v, gate / up at prompt sizes) run on
+# ptd_lowrank_tile_group_q and ptd_lowrank_tile_gated_q (csrc/lowrank_tile_group_q.hip): every member's first product in
+# one grid, one slab sum, every member's second product in one grid stored straight into the [T, sum n_o] result -- or,
+# gated, both second products in one workgroup with act(g) * u in the epilogue.  Three launches, two where no member
+# has slabs; every member's bits are those of ``lowrank_tile_w8`` on it alone.  No switch of their own:
+# PTD_LOWRANK_GROUP_Q=0 or PTD_LOWRANK_TILE_W8=0 turns both off.  A group is taken only when EVERY member is in the
+# measured classes of ``_tile_w8_takes`` and every width is a multiple of 4; the MX formats are never taken.  Which classes the measurement admits:
+# profiles/pair_tile_group_w8.json.
+_TILE_GROUP_PLAN_FIELDS = ("xa_bn", "xa_bt", "hb_bn", "hb_bt", "gated_bn", "gated_bt", "xa_grid", "hb_grid", "launches")
+_TILE_GROUP_PLAN_MEMBER_FIELDS = ("nslabs", "kslab", "xa_first", "hb_first")
+
+
+def lowrank_tile_group_q_serves(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], sas: Sequence[torch.Tensor],
+                                Bqs: Sequence[torch.Tensor], sbs: Sequence[torch.Tensor],
+                                biases: Sequence[Optional[torch.Tensor]]) -> bool:
+    """Whether ``lowrank_tile_group_q`` takes these operands as they lie (without loading the library): ``fmt`` "fp8",
+    1 to 4 members, each served by ``lowrank_tile_w8`` on the common x2d (its measured classes included), every n_o a
+    multiple of 4."""
+    return _q_group_serves(fmt, "tile", x2d, Aqs, sas, Bqs, sbs, biases)
+
+
+def lowrank_tile_group_q(fmt, x2d: torch.Tensor, Aqs: Sequence[torch.Tensor], sas: Sequence[torch.Tensor],
+                         Bqs: Sequence[torch.Tensor], sbs: Sequence[torch.Tensor],
+                         biases: Sequence[Optional[torch.Tensor]]) -> torch.Tensor:
+    """[the tile pair of member m on x2d for m] side by side: y [T, sum n_o] contiguous, member m in columns
+    [off_m, off_m + n_o_m), for T >= 17 rows of x2d and 1 to 4 fp8 members (operands of ``lowrank_tile_w8``):
+    ptd_lowrank_tile_group_q, three launches (two where no member's first product has slabs), safe under graph capture.
+    Every member's columns hold the bits ``lowrank_tile_w8`` gives.  A group the C entry does not serve raises."""
+    return _q_group_call(fmt, "tile", x2d, Aqs, sas, Bqs, sbs, biases)
+
+
+def lowrank_tile_gated_q_serves(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: torch.Tensor, Bq_g: torch.Tensor,
+                                sb_g: torch.Tensor, bias_g: Optional[torch.Tensor], Aq_u: torch.Tensor,
+                                sa_u: torch.Tensor, Bq_u: torch.Tensor, sb_u: torch.Tensor,
+                                bias_u: Optional[torch.Tensor], act: str) -> bool:
+    """Whether ``lowrank_tile_gated_q`` takes these operands as they lie (without loading the library): a known
+    activation, (gate, up) a group ``lowrank_tile_group_q_serves`` takes, and the same number of output rows."""
+    return _q_gated_serves(fmt, "tile", x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g, Aq_u, sa_u, Bq_u, sb_u, bias_u, act)
+
+
+def lowrank_tile_gated_q(fmt, x2d: torch.Tensor, Aq_g: torch.Tensor, sa_g: torch.Tensor, Bq_g: torch.Tensor,
+                         sb_g: torch.Tensor, bias_g: Optional[torch.Tensor], Aq_u: torch.Tensor, sa_u: torch.Tensor,
+                         Bq_u: torch.Tensor, sb_u: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> torch.Tensor:
+    """round(round(act(g)) * u) with g and u the tile pairs of the fp8 gate and up on T >= 17 rows of x2d, act one of
+    ``GATED_ACTS``: ptd_lowrank_tile_gated_q, three launches (two where neither first product has slabs), y [T, n_ff]
+    contiguous.  g and u are the bits ``lowrank_tile_w8`` gives.  Operands the C entry does not serve raise."""
+    return _q_gated_call(fmt, "tile", x2d, Aq_g, sa_g, Bq_g, sb_g, bias_g, Aq_u, sa_u, Bq_u, sb_u, bias_u, act)
+
+
+def lowrank_tile_group_q_plan(T: int, n_i: int, ranks: Sequence[int], widths: Sequence[int],
+                              dtype: torch.dtype = torch.bfloat16) -> dict:
+    """What ``lowrank_tile_group_q`` would launch for members (ranks[m], widths[m]) on a common n_i
+    (ptd_lowrank_tile_group_q_plan; host only, no GPU): the tile shapes and grids of the first (``xa_``) and the last
+    (``hb_``) launch, the shape of the gated kernel on n_ff = widths[0], ``launches`` (3, or 2 where every member has
+    S = 1) and, under ``members``, each member's ``nslabs``, ``kslab`` and first workgroup in both grids.  A group the
+    entry does not serve raises."""
+    count = len(ranks)
+    assert len(widths) == count
+    i64s = ctypes.c_int64 * max(count, 1)
+    out = (ctypes.c_int32 * (len(_TILE_GROUP_PLAN_FIELDS) + len(_TILE_GROUP_PLAN_MEMBER_FIELDS) * _GROUP_MAX))()
+    rc = _hip.load().ptd_lowrank_tile_group_q_plan(count, T, n_i, i64s(*ranks), i64s(*widths), _DT[dtype], out, len(out))
+    _hip.check(rc, "ptd_lowrank_tile_group_q_plan")
+    plan = dict(zip(_TILE_GROUP_PLAN_FIELDS, out))
+    base, step = len(_TILE_GROUP_PLAN_FIELDS), len(_TILE_GROUP_PLAN_MEMBER_FIELDS)
+    plan["members"] = [dict(zip(_TILE_GROUP_PLAN_MEMBER_FIELDS, out[base + m * step:base + (m + 1) * step]))
+                       for m in range(count)]
+    return plan
 
 
 # MXFP8 activations on the block-scaled MFMA (csrc/lowrank_a8.hip).  OPT-IN (``activations="mxfp8"`` on a LowRankLinearW4 /
