@@ -69,7 +69,9 @@ extern "C" {
                              *    ptd_lowrank_tile_w8_workspace_bytes, ptd_lowrank_tile_w8, ptd_lowrank_tile_w8_plan,
                              *    ptd_lowrank_tile_group_q_workspace_bytes, ptd_lowrank_tile_group_q,
                              *    ptd_lowrank_tile_gated_q_workspace_bytes, ptd_lowrank_tile_gated_q,
-                             *    ptd_lowrank_tile_group_q_plan) */
+                             *    ptd_lowrank_tile_group_q_plan,
+                             *    ptd_fp8_quantize_rows, ptd_w8a8_product_workspace_bytes, ptd_w8a8_product,
+                             *    ptd_lowrank_w8a8_workspace_bytes, ptd_lowrank_w8a8, ptd_lowrank_w8a8_plan) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -715,6 +717,54 @@ int ptd_lowrank_tile_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                         const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o, const void* bias,
                         void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
 int ptd_lowrank_tile_w8_plan(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap);
+
+/* The fp8 pair with dynamic per-token fp8 ACTIVATIONS (W8A8; csrc/lowrank_w8a8.hip): both products on the fp8 matrix
+ * cores (v_mfma_scale_f32_16x16x128_f8f6f4, both operands e4m3, scale bytes 127).  OPT-IN: quantising the activations
+ * changes numerics.  With D the activation dtype (bf16 / f16):
+ *   Q(v), a row v of D values: amax = max |v_k| in f32 (a NaN is left out, an Inf counts as the largest finite f32),
+ *     s = amax / 448 (IEEE f32 division), 1 where amax == 0; code_k = e4m3fn, round to nearest even, of
+ *     clamp(f32(v_k) / s, -448, 448), the sign of -0 kept (an Inf becomes +-448, a NaN -448: a bad row touches no other)
+ *   h[t, j] = round_D(((sum_k Q(x)[t, k] Aq[j, k]) * s_x[t]) * scale_a[j])
+ *   y[t, o] = round_D(((sum_j Q(h)[t, j] Bq[o, j]) * s_h[t]) * scale_b[o] + bias[o])
+ * f32 sums, K ascending, one accumulator per output and K slab; the multiplies, the addition and the division are the
+ * IEEE operations in the order written (no contraction).  Row t of y depends on row t of x alone; equal S gives equal
+ * bits for equal rows; no atomics, no host read, no allocation: capturable in a graph.
+ *
+ * ptd_fp8_quantize_rows: Q of the T rows of x [T, n] (pitch ldx elements) -> codes [T, n] (pitch ldc bytes) and scales
+ * [T] f32.  One wave per row; rows of up to 8192 elements are read once.  Served: bf16 / f16, 1 <= T <= 2^24, n a
+ * multiple of 16 below 2^30, ldx a multiple of 8, ldc of 16, x and codes 16-byte aligned.
+ *
+ * ptd_w8a8_product: out[t, n] = round_D(((sum_k xq[t, k] Wq[n, k]) * sx[t]) * scale_w[n] + bias[n]) from e4m3 codes xq
+ * [T, K] (pitch ldxq bytes) and Wq [N, K] (pitch ldw bytes).  K is cut into S <= 16 slabs of f32 sums (a pure function
+ * of (T, K, N): as many as give each of the 256 CUs a workgroup, none shorter than 512, whole steps of 128; S = 1 where
+ * N is no multiple of 16 or above PTD_W8A8_MAX_R, and under PTD_W8A8_NO_SPLIT, which is how the pair runs its second
+ * product), added in ascending order.  flags & PTD_W8A8_QUANT: instead of out, Q of the rounded rows -- outq [T, N]
+ * (pitch ldoq bytes) and sout [T]; out is not written; N a multiple of 16, at most PTD_W8A8_MAX_R.  The workspace
+ * (ptd_w8a8_product_workspace_bytes) holds the slabs: none for S = 1 without PTD_W8A8_QUANT.  Served: bf16 / f16,
+ * 1 <= T <= 2^24, K a multiple of 16, K and N below 2^30, T max(K, N) < 2^40, ldxq and ldw multiples of 16, xq and Wq
+ * 16-byte aligned, sx and scale_w 4-byte aligned.
+ *
+ * ptd_lowrank_w8a8: the pair (arguments of ptd_lowrank_tile_w8) in four launches: Q(x); the first product into slabs;
+ * slab sum, scales, rounding and Q(h) with the row in registers (h never exists in D in memory); the second product.
+ * Bit for bit ptd_fp8_quantize_rows, ptd_w8a8_product, ptd_fp8_quantize_rows, ptd_w8a8_product (PTD_W8A8_NO_SPLIT)
+ * composed.  Served: the operands of ptd_lowrank_tile_w8 with r <= PTD_W8A8_MAX_R.  Errors as ptd_lowrank_tile_w8.
+ * ptd_lowrank_w8a8_plan: as ptd_lowrank_tile_w8_plan (same fields; the slab length is a multiple of 128).
+ * No reference counterpart. */
+#define PTD_W8A8_MAX_R 4096
+#define PTD_W8A8_QUANT 1
+#define PTD_W8A8_NO_SPLIT 2
+int ptd_fp8_quantize_rows(const void* x, int64_t ldx, int64_t T, int64_t n, void* codes, int64_t ldc, float* scales,
+                          int dtype, void* stream);
+size_t ptd_w8a8_product_workspace_bytes(int64_t T, int64_t K, int64_t N, int flags);
+int ptd_w8a8_product(const void* xq, int64_t ldxq, const float* sx, int64_t T, int64_t K, const void* Wq, int64_t ldw,
+                     const float* scale_w, int64_t N, const void* bias, void* out, int64_t ldo, void* outq, int64_t ldoq,
+                     float* sout, void* ws, size_t ws_bytes, int dtype, int flags, void* stream);
+size_t ptd_lowrank_w8a8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype);
+int ptd_lowrank_w8a8(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                     const void* Aq, int64_t lda, const float* scale_a, int64_t r,
+                     const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o, const void* bias,
+                     void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format, void* stream);
+int ptd_lowrank_w8a8_plan(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap);
 
 /* 1 <= count <= PTD_LOWRANK_GROUP_MAX fp8 pairs that read the same x at the token counts of ptd_lowrank_tile_w8 (the
  * q / k / v or gate / up projections of a block at prompt sizes; arguments of ptd_lowrank_skinny_group_q, q_format

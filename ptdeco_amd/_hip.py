@@ -155,6 +155,15 @@ SIGNATURES = {
     "ptd_lowrank_tile_w8_workspace_bytes": _TILE_WS,
     "ptd_lowrank_tile_w8": _PAIR_FP8,
     "ptd_lowrank_tile_w8_plan": (c_int, [c_int64, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),
+    "ptd_fp8_quantize_rows": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "ptd_w8a8_product_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
+    # xq, ldxq, sx, T, K, Wq, ldw, scale_w, N, bias, out, ldo, outq, ldoq, sout, ws, ws_bytes, dtype, flags, stream
+    "ptd_w8a8_product": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                 c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_int, c_int,
+                                 c_void_p]),
+    "ptd_lowrank_w8a8_workspace_bytes": _TILE_WS,
+    "ptd_lowrank_w8a8": _PAIR_FP8,
+    "ptd_lowrank_w8a8_plan": (c_int, [c_int64, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),
     "ptd_lowrank_tile_group_q_workspace_bytes": _GROUP_Q_WS,
     "ptd_lowrank_tile_group_q": _GROUP_Q,
     "ptd_lowrank_tile_gated_q_workspace_bytes": _GATED_Q_WS,

@@ -250,6 +250,59 @@ def _(x2d, Aq, sa, Bq, sb, bias):
     return _w8_fake("lowrank_forward_w8", x2d, Aq, sa, Bq, sb, bias)
 
 
+# Dynamic per-token fp8 activations for the fp8 pair (W8A8): the definition the kernels of csrc/lowrank_w8a8.hip are
+# tested against.
+_FP8_MAX = 448.0
+_F32_MAX = torch.finfo(torch.float32).max
+
+
+def fp8_quantize_rows_reference(x: torch.Tensor):
+    """Q of the rows of x [T, n] (bf16 / f16 values): (codes [T, n] float8_e4m3fn, scales [T] f32).  Per row, in f32:
+    amax = max |x_k|, s = amax / 448 (1 where amax == 0), code_k the round-to-nearest-even e4m3fn of
+    clamp(x_k / s, -448, 448), the sign of -0 kept; the value of a code is e4m3(code) * s.  Non-finite inputs are not
+    propagated (the convention of ``mxfp8_quantize_rows_reference``'s kernel): a NaN is left out of the maximum and
+    becomes -448, an Inf counts as the largest finite f32 in the maximum and becomes +-448 -- within its own row only."""
+    v = x.detach().to(torch.float32)
+    amax = torch.nan_to_num(v.abs(), nan=0.0, posinf=_F32_MAX).amax(dim=1)
+    s = torch.where(amax == 0, torch.ones_like(amax), amax / _FP8_MAX)
+    q = v / s[:, None]
+    q = torch.where(q > _FP8_MAX, torch.full_like(q, _FP8_MAX), q)      # (compares: a NaN falls through to -448)
+    q = torch.where(q >= -_FP8_MAX, q, torch.full_like(q, -_FP8_MAX))
+    return q.to(torch.float8_e4m3fn), s
+
+
+def lowrank_w8a8_expression(x: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                            bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The semantics of the fp8 pair with fp8 activations in torch, D = x.dtype:
+    h = round_D(((Q(x) Aq^T) * s_x) * sa), y = round_D(((Q(h) Bq^T) * s_h) * sb + bias) -- codes as f32 values (exact),
+    f32 sums, the two multiplies in that order, h and y rounded once each."""
+    linear = torch.nn.functional.linear
+    xq, sx = fp8_quantize_rows_reference(x)
+    h = ((linear(xq.float(), Aq.float()) * sx[:, None]) * sa).to(x.dtype)
+    hq, sh = fp8_quantize_rows_reference(h)
+    y = (linear(hq.float(), Bq.float()) * sh[:, None]) * sb
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(x.dtype)
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_w8a8", mutates_args=())
+def lowrank_forward_w8a8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                         bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The fp8 pair (operands of lowrank_forward_w8) with dynamic per-token fp8 activations -- other numerics than
+    lowrank_forward_w8, by the activation noise.  Where ops.lowrank_w8a8_serves (T >= 17, r <= 4096) on ptd_lowrank_w8a8
+    (both products on the fp8 MFMA, four launches, capturable), elsewhere ``lowrank_w8a8_expression``.  Inference only:
+    no autograd formula."""
+    if ops.lowrank_w8a8_serves(x2d, Aq, sa, Bq, sb, bias):
+        return ops.lowrank_w8a8(x2d, Aq, sa, Bq, sb, bias)
+    return lowrank_w8a8_expression(x2d, Aq, sa, Bq, sb, bias).contiguous()
+
+
+@lowrank_forward_w8a8.register_fake
+def _(x2d, Aq, sa, Bq, sb, bias):
+    return _w8_fake("lowrank_forward_w8a8", x2d, Aq, sa, Bq, sb, bias)
+
+
 # e2m1: sign, two exponent bits, one mantissa bit -- the value of code c is (c & 8 ? -1 : 1) * _E2M1[c & 7]
 _E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 W4_BLOCK = 32                  # weights per e8m0 scale byte

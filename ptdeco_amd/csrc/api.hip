@@ -958,6 +958,85 @@ int ptd_lowrank_tile_w8_plan(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int
   return PTD_OK;
 }
 
+// fp8 activations for the fp8 pair (lowrank_w8a8.hip)
+int ptd_fp8_quantize_rows(const void* x, int64_t ldx, int64_t T, int64_t n, void* codes, int64_t ldc, float* scales,
+                          int dtype, void* stream) {
+  PTD_REQUIRE(x && codes && scales, "ptd_fp8_quantize_rows: null pointer");
+  PTD_REQUIRE(T >= 1, "ptd_fp8_quantize_rows: T must be positive");
+  PTD_REQUIRE(ldx >= n && ldc >= n, "ptd_fp8_quantize_rows: bad leading dimension");
+  if (!fp8_quantize_rows_serves(x, ldx, T, n, codes, ldc, dtype) || (reinterpret_cast<uintptr_t>(scales) & 3)) {
+    set_error("ptd_fp8_quantize_rows: not served (T=%lld n=%lld dtype=%d: bf16 / f16, n a positive multiple of 16, ldx a "
+              "multiple of 8, ldc of 16, 16-byte aligned rows)", (long long)T, (long long)n, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  return fp8_quantize_rows(x, ldx, T, n, codes, ldc, scales, dtype, static_cast<hipStream_t>(stream));
+}
+
+size_t ptd_w8a8_product_workspace_bytes(int64_t T, int64_t K, int64_t N, int flags) {
+  return w8a8_product_workspace_bytes(T, K, N, flags);
+}
+
+int ptd_w8a8_product(const void* xq, int64_t ldxq, const float* sx, int64_t T, int64_t K, const void* Wq, int64_t ldw,
+                     const float* scale_w, int64_t N, const void* bias, void* out, int64_t ldo, void* outq, int64_t ldoq,
+                     float* sout, void* ws, size_t ws_bytes, int dtype, int flags, void* stream) {
+  const bool quant = (flags & PTD_W8A8_QUANT) != 0;
+  PTD_REQUIRE(xq && sx && Wq && scale_w, "ptd_w8a8_product: null pointer");
+  PTD_REQUIRE(quant ? (outq && sout) : out != nullptr, "ptd_w8a8_product: null output");
+  PTD_REQUIRE(T >= 1, "ptd_w8a8_product: T must be positive");
+  PTD_REQUIRE(ldxq >= K && ldw >= K && (quant ? ldoq >= N : ldo >= N), "ptd_w8a8_product: bad leading dimension");
+  if (!w8a8_product_serves(xq, ldxq, sx, T, K, Wq, ldw, scale_w, N, bias, outq, ldoq, dtype, flags) ||
+      (quant && (reinterpret_cast<uintptr_t>(sout) & 3))) {
+    set_error("ptd_w8a8_product: not served (T=%lld K=%lld N=%lld dtype=%d flags=%d: bf16 / f16, K a multiple of 16, "
+              "16-byte aligned code rows; PTD_W8A8_QUANT: N a multiple of 16, at most " PTD_STR(PTD_W8A8_MAX_R) ")",
+              (long long)T, (long long)K, (long long)N, dtype, flags);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  const size_t need = w8a8_product_workspace_bytes(T, K, N, flags);
+  PTD_REQUIRE(need == 0 || (ws && aligned16(ws)), "ptd_w8a8_product: the workspace must be 16-byte aligned");
+  if (ws_bytes < need) {
+    set_error("ptd_w8a8_product: workspace %zu < required %zu bytes", ws_bytes, need);
+    return PTD_ERR_WORKSPACE;
+  }
+  return w8a8_product(xq, ldxq, sx, T, K, Wq, ldw, scale_w, N, bias, out, ldo, outq, ldoq, sout, ws, dtype, flags,
+                      static_cast<hipStream_t>(stream));
+}
+
+size_t ptd_lowrank_w8a8_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype) {
+  (void)n_o;
+  (void)dtype;
+  return lowrank_w8a8_workspace_bytes(T, n_i, r);
+}
+
+int ptd_lowrank_w8a8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda,
+                     const float* scale_a, int64_t r, const void* Bq, int64_t ldb, const float* scale_b, int64_t n_o,
+                     const void* bias, void* y, int64_t ldy, void* ws, size_t ws_bytes, int dtype, int w_format,
+                     void* stream) {
+  const int rc = q_entry_checks("ptd_lowrank_w8a8", x, ldx, T, n_i, Aq, lda, scale_a, 0, r, Bq, ldb, scale_b, 0, n_o, y, ldy,
+                                ws, ws_bytes, dtype, w_format, n_i, r, false,
+                                lowrank_w8a8_serves(T, n_i, r, n_o, dtype, w_format, x, ldx, Aq, lda, scale_a, Bq, ldb,
+                                                    scale_b, bias),
+                                "PTD_W8_FP8_E4M3, T >= " PTD_STR(PTD_LOWRANK_TILE_W8_MIN_T) ", 16 <= r <= "
+                                PTD_STR(PTD_W8A8_MAX_R) ", n_i and r multiples of 16, 16-byte aligned rows",
+                                lowrank_w8a8_workspace_bytes(T, n_i, r));
+  if (rc != PTD_OK) return rc;
+  return lowrank_w8a8(x, ldx, T, n_i, Aq, lda, scale_a, r, Bq, ldb, scale_b, n_o, bias, y, ldy, ws, dtype,
+                      static_cast<hipStream_t>(stream));
+}
+
+int ptd_lowrank_w8a8_plan(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out, int cap) {
+  PTD_REQUIRE(out, "ptd_lowrank_w8a8_plan: null pointer");
+  PTD_REQUIRE(cap >= PTD_TILE_W8_PLAN_LEN, "ptd_lowrank_w8a8_plan: out holds %d values, the plan has %d", cap,
+              PTD_TILE_W8_PLAN_LEN);
+  if (!lowrank_w8a8_serves(T, n_i, r, n_o, dtype, PTD_W8_FP8_E4M3, nullptr, n_i, nullptr, n_i, nullptr, nullptr, r, nullptr,
+                           nullptr)) {
+    set_error("ptd_lowrank_w8a8_plan: not served (T=%lld n_i=%lld r=%lld n_o=%lld dtype=%d)", (long long)T, (long long)n_i,
+              (long long)r, (long long)n_o, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  lowrank_w8a8_plan(T, n_i, r, n_o, out);
+  return PTD_OK;
+}
+
 size_t ptd_lowrank_tile_group_q_workspace_bytes(int q_format, int count, int64_t T, int64_t n_i, const int64_t* r,
                                                 int dtype) {
   if (!r || count < 1 || count > PTD_LOWRANK_GROUP_MAX) return 0;

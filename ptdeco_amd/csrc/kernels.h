@@ -331,6 +331,28 @@ int lowrank_tile_w8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const vo
                     int64_t r, const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y,
                     int64_t ldy, void* ws, int dtype, hipStream_t st);
 
+// lowrank_w8a8.hip: the fp8 pair with per-token fp8 activations on the fp8 MFMA: the row quantiser
+// (ptd_fp8_quantize_rows), one product from codes and scales, in D or quantised (ptd_w8a8_product), and the pair in four
+// launches (ptd_lowrank_w8a8).  lowrank_w8a8_plan: out[PTD_TILE_W8_PLAN_*] of a served shape
+bool fp8_quantize_rows_serves(const void* x, int64_t ldx, int64_t T, int64_t n, const void* codes, int64_t ldc, int dtype);
+int fp8_quantize_rows(const void* x, int64_t ldx, int64_t T, int64_t n, void* codes, int64_t ldc, float* scales, int dtype,
+                      hipStream_t st);
+bool w8a8_product_serves(const void* xq, int64_t ldxq, const float* sx, int64_t T, int64_t K, const void* wq, int64_t ldw,
+                         const float* scale, int64_t N, const void* bias, const void* outq, int64_t ldoq, int dtype,
+                         int flags);
+size_t w8a8_product_workspace_bytes(int64_t T, int64_t K, int64_t N, int flags);
+int w8a8_product(const void* xq, int64_t ldxq, const float* sx, int64_t T, int64_t K, const void* wq, int64_t ldw,
+                 const float* scale, int64_t N, const void* bias, void* out, int64_t ldo, void* outq, int64_t ldoq,
+                 float* sout, void* ws, int dtype, int flags, hipStream_t st);
+bool lowrank_w8a8_serves(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int w_format, const void* x, int64_t ldx,
+                         const void* Aq, int64_t lda, const float* sa, const void* Bq, int64_t ldb, const float* sb,
+                         const void* bias);
+size_t lowrank_w8a8_workspace_bytes(int64_t T, int64_t n_i, int64_t r);
+void lowrank_w8a8_plan(int64_t T, int64_t n_i, int64_t r, int64_t n_o, int32_t* out);
+int lowrank_w8a8(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Aq, int64_t lda, const float* sa, int64_t r,
+                 const void* Bq, int64_t ldb, const float* sb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws,
+                 int dtype, hipStream_t st);
+
 // lowrank_tile_group_q.hip: 1 .. PTD_LOWRANK_GROUP_MAX fp8 pairs on one input at the token counts of lowrank_tile_w8 in
 // three launches (two where no member has slabs), every member's bits those of lowrank_tile_w8 on that member alone
 // (ptd_lowrank_tile_group_q), and act(gate x) * up x for two of them with both second products in one workgroup

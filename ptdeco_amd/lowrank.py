@@ -28,6 +28,7 @@ _lowrank_forward_group = torch.ops.ptdeco_amd.lowrank_forward_group.default
 _lowrank_forward_group_fused = torch.ops.ptdeco_amd.lowrank_forward_group_fused.default
 _lowrank_forward_gated = torch.ops.ptdeco_amd.lowrank_forward_gated.default
 _lowrank_forward_w8 = torch.ops.ptdeco_amd.lowrank_forward_w8.default
+_lowrank_forward_w8a8 = torch.ops.ptdeco_amd.lowrank_forward_w8a8.default
 _lowrank_forward_w4 = torch.ops.ptdeco_amd.lowrank_forward_w4.default
 _lowrank_forward_w6 = torch.ops.ptdeco_amd.lowrank_forward_w6.default
 _lowrank_forward_w4a8 = torch.ops.ptdeco_amd.lowrank_forward_w4a8.default
@@ -117,6 +118,15 @@ class _QuantizedPair(torch.nn.Module):
                 f"bias={self.bias is not None}, dtype={self._dtype}")
 
 
+_W8_ACTIVATIONS = ("16bit", "fp8")      # what an fp8 pair feeds the matrix cores beside its weights
+
+
+def _check_w8_activations(who: str, activations) -> str:
+    if activations not in _W8_ACTIVATIONS:
+        raise ValueError(f"{who}: activations must be one of {_W8_ACTIVATIONS}, got {activations!r}")
+    return activations
+
+
 class LowRankLinearW8(_QuantizedPair):
     """A rank-r pair with 8-bit factors (weight-only quantisation): ``weight_a_q`` [rank, in_features] and ``weight_b_q``
     [out_features, rank] in float8_e4m3fn, one f32 scale per factor row (``scale_a`` [rank], ``scale_b`` [out_features])
@@ -134,11 +144,18 @@ class LowRankLinearW8(_QuantizedPair):
     which rounds once more per product.  Anything else (a CPU copy, another input dtype, ``x.requires_grad``) evaluates that
     expression directly and says so once, at WARNING.  ``.to(device)`` moves the module; a dtype cast (``.half()``,
     ``.to(torch.bfloat16)``) changes the bias and the activation dtype and leaves the quantised factors and their
-    scales as they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place``, or empty for ``load_state_dict``."""
+    scales as they are.  Built by ``quantize_pair`` / ``quantize_pairs_in_place``, or empty for ``load_state_dict``.
+
+    ``activations`` ("16bit", the default, or "fp8") is a plain attribute, not a buffer: it adds no ``state_dict`` key.
+    With "fp8" the cells of ``ops.lowrank_w8a8_takes`` (the measured class that is won) call
+    ``torch.ops.ptdeco_amd.lowrank_forward_w8a8``: x and h quantised on the fly to e4m3 with one f32 scale per token
+    (``_torch_ops.fp8_quantize_rows_reference``), both products on the fp8 matrix cores -- other numerics, by the
+    activation noise.  Every other cell runs exactly what "16bit" runs."""
 
     def __init__(self, in_features: int, rank: int, out_features: int, bias: bool = True,
-                 dtype: torch.dtype = torch.bfloat16, device=None) -> None:
+                 dtype: torch.dtype = torch.bfloat16, device=None, activations: str = "16bit") -> None:
         super().__init__()
+        self.activations = _check_w8_activations("LowRankLinearW8", activations)
         if dtype not in _W8_DTYPES:
             raise ValueError(f"LowRankLinearW8: the activation dtype must be bfloat16 or float16, got {dtype}")
         self.in_features, self.rank, self.out_features = int(in_features), int(rank), int(out_features)
@@ -171,8 +188,16 @@ class LowRankLinearW8(_QuantizedPair):
                                                 "on 16-bit copies of the factors instead")
             return _torch_ops.lowrank_w8_expression(x, *operands)
         x2d = x.reshape(-1, self.in_features)
-        y = _lowrank_forward_w8(x2d, *operands)
+        if self.activations == "fp8" and ops.lowrank_w8a8_takes(x2d.shape[0], self.in_features, self.rank,
+                                                                self.out_features):
+            y = _lowrank_forward_w8a8(x2d, *operands)
+        else:
+            y = _lowrank_forward_w8(x2d, *operands)
         return y.reshape(*x.shape[:-1], self.out_features)
+
+    def extra_repr(self) -> str:
+        shown = "" if self.activations == "16bit" else f", activations={self.activations}"
+        return super().extra_repr() + shown
 
 
 _W4_FORMAT = "mxfp4"
@@ -187,6 +212,19 @@ def _check_activations(who: str, activations) -> str:
     if activations not in _ACTIVATIONS:
         raise ValueError(f"{who}: activations must be one of {_ACTIVATIONS}, got {activations!r}")
     return activations
+
+
+def _check_fmt_activations(who: str, fmt: str, activations) -> None:
+    """"fp8" (per-token fp8 activations) goes with the fp8 factors alone, the MXFP8 options with the MX formats alone."""
+    if activations == "fp8":
+        if fmt not in _W8_FORMATS:
+            raise ValueError(f"{who}: activations='fp8' needs fmt='fp8_e4m3' (the MX pairs take 'mxfp8' / "
+                             f"'mxfp8_prefill'), got {fmt!r}")
+        return
+    _check_activations(who, activations)
+    if activations != "16bit" and fmt not in (_W4_FORMAT, _W6_FORMAT):
+        raise ValueError(f"{who}: activations={activations!r} needs an MX format ({_W4_FORMAT!r} or "
+                         f"{_W6_FORMAT!r}), got {fmt!r}")
 
 
 class _LowRankLinearMX(_QuantizedPair):
@@ -481,13 +519,12 @@ def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3", *, activations: st
     bytes at a noise-to-signal ratio near 1.6e-3, fp8's class.  ``activations="mxfp8"`` (MX formats only; the fp8
     pair's f32 row scales have no place in the block-scaled instruction) opts the new module into MXFP8 activations
     at 17 to 31 tokens, ``activations="mxfp8_prefill"`` also at the prefill cells measured as won (``LowRankLinearW4``;
-    token counts on those paths differ from the others by the activation noise).  The pair itself is not modified."""
+    token counts on those paths differ from the others by the activation noise).  ``activations="fp8"``
+    (``fmt="fp8_e4m3"`` only) opts the new ``LowRankLinearW8`` into per-token fp8 activations at the cells of
+    ``ops.lowrank_w8a8_takes``.  The pair itself is not modified."""
     if fmt not in _QUANT_FORMATS:
         raise ValueError(f"quantize_pair: fmt must be one of {sorted(_QUANT_FORMATS)}, got {fmt!r}")
-    _check_activations("quantize_pair", activations)
-    if activations != "16bit" and fmt not in (_W4_FORMAT, _W6_FORMAT):
-        raise ValueError(f"quantize_pair: activations={activations!r} needs an MX format ({_W4_FORMAT!r} or "
-                         f"{_W6_FORMAT!r}), got {fmt!r}")
+    _check_fmt_activations("quantize_pair", fmt, activations)
     if not isinstance(pair, LowRankLinear):
         raise TypeError(f"quantize_pair: expected an installed LowRankLinear, got {type(pair).__name__}")
     first, second = pair[0], pair[1]
@@ -502,7 +539,7 @@ def quantize_pair(pair: LowRankLinear, fmt: str = "fp8_e4m3", *, activations: st
         return out.train(pair.training)
     qdtype, qmax = _W8_FORMATS[fmt]
     out = LowRankLinearW8(first.in_features, first.out_features, second.out_features, bias=second.bias is not None,
-                          dtype=dtype, device=first.weight.device)
+                          dtype=dtype, device=first.weight.device, activations=activations)
     out.weight_a_q, out.scale_a = _quantize_rows(first.weight, qdtype, qmax)
     out.weight_b_q, out.scale_b = _quantize_rows(second.weight, qdtype, qmax)
     if second.bias is not None:
@@ -520,9 +557,7 @@ def quantize_pairs_in_place(model: torch.nn.Module, fmt: str = "fp8_e4m3", names
     that is not such a pair raises.  ``activations`` is handed to ``quantize_pair``."""
     if fmt not in _QUANT_FORMATS:
         raise ValueError(f"quantize_pairs_in_place: fmt must be one of {sorted(_QUANT_FORMATS)}, got {fmt!r}")
-    _check_activations("quantize_pairs_in_place", activations)
-    if activations != "16bit" and fmt not in (_W4_FORMAT, _W6_FORMAT):
-        raise ValueError(f"quantize_pairs_in_place: activations={activations!r} needs an MX format, got {fmt!r}")
+    _check_fmt_activations("quantize_pairs_in_place", fmt, activations)
     modules = dict(model.named_modules())
     if names is not None:
         names = list(names)
@@ -545,17 +580,29 @@ def set_pair_activations(model: torch.nn.Module, activations: str, names=None) -
     """Set ``activations`` ("mxfp8", "mxfp8_prefill" or "16bit") on the ``LowRankLinearW4`` / ``LowRankLinearW6`` modules of ``model`` --
     all of them (``model`` itself included), or those listed in ``names`` -- and return their names in module order: the
     way to opt an already built or loaded model in or out (the choice is an attribute, not a buffer; a state dict does
-    not carry it).  A name in ``names`` that is not such a module raises."""
-    _check_activations("set_pair_activations", activations)
+    not carry it).  A name in ``names`` that is not such a module raises.  ``"fp8"`` sets the ``LowRankLinearW8``
+    modules instead; ``"16bit"`` also resets the ``LowRankLinearW8`` modules that had been opted in, and with ``names`` may
+    name modules of either family."""
+    if activations == "fp8":
+        kinds, what = (LowRankLinearW8,), "LowRankLinearW8"
+    else:
+        _check_activations("set_pair_activations", activations)
+        kinds, what = (_LowRankLinearMX,), "LowRankLinearW4 / LowRankLinearW6"
     modules = dict(model.named_modules())
+    if activations == "fp8" and not any(isinstance(mod, LowRankLinearW8) for mod in modules.values()):
+        raise ValueError("set_pair_activations: activations='fp8' is for LowRankLinearW8 modules and the model has none "
+                         "(the MX pairs take 'mxfp8' / 'mxfp8_prefill')")
     if names is not None:
         names = list(names)
+        if activations == "16bit":
+            kinds = (_LowRankLinearMX, LowRankLinearW8)
         for name in names:
-            if not isinstance(modules.get(name), _LowRankLinearMX):
-                raise ValueError(f"set_pair_activations: {name!r} is not a LowRankLinearW4 / LowRankLinearW6 of the model")
+            if not isinstance(modules.get(name), kinds):
+                raise ValueError(f"set_pair_activations: {name!r} is not a {what} of the model")
     done = []
     for name, mod in modules.items():
-        if isinstance(mod, _LowRankLinearMX) and (names is None or name in names):
+        opted_w8 = activations == "16bit" and isinstance(mod, LowRankLinearW8) and mod.activations != "16bit"
+        if (isinstance(mod, kinds) or opted_w8) and (names is None or name in names):
             mod.activations = activations
             done.append(name)
     return done

@@ -643,8 +643,8 @@ def _q_call(fmt: _QFormat, regime: str, x2d, Aq, ea, Bq, eb, bias) -> torch.Tens
     r, n_o = Aq.shape[0], Bq.shape[0]
     y = torch.empty((T, n_o), dtype=x2d.dtype, device=x2d.device)
     lib = _hip.load()
-    entry = f"ptd_lowrank_{regime}_{fmt.tag}"
-    shape = (T, n_i, r, n_o) if regime in ("tile", "a8", "a8_tile") else (T, n_i, r)      # (the tile entry holds both factors too)
+    entry = "ptd_lowrank_w8a8" if regime == "w8a8" else f"ptd_lowrank_{regime}_{fmt.tag}"
+    shape = (T, n_i, r, n_o) if regime in ("tile", "a8", "a8_tile", "w8a8") else (T, n_i, r)      # (the tile entry holds both factors too)
     ws_bytes = getattr(lib, entry + "_workspace_bytes")(*shape, _code(x2d))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x2d.device)
     a = (Aq.data_ptr(), Aq.stride(0), ea.data_ptr()) + ((ea.stride(0),) if fmt.scale_rank == 2 else ())
@@ -1321,6 +1321,121 @@ def lowrank_tile_w8_plan(T: int, n_i: int, r: int, n_o: int, dtype: torch.dtype 
     out = (ctypes.c_int32 * len(_TILE_W8_PLAN_FIELDS))()
     rc = _hip.load().ptd_lowrank_tile_w8_plan(T, n_i, r, n_o, _DT[dtype], out, len(out))
     _hip.check(rc, "ptd_lowrank_tile_w8_plan")
+    return dict(zip(_TILE_W8_PLAN_FIELDS, out))
+
+
+# fp8 ACTIVATIONS for the fp8 pair (csrc/lowrank_w8a8.hip).  OPT-IN (``activations="fp8"`` on a LowRankLinearW8,
+# ``torch.ops.ptdeco_amd.lowrank_forward_w8a8``): x and h are quantised on the fly to e4m3 codes with one f32 scale per
+# token row (``_torch_ops.fp8_quantize_rows_reference``) and both products run on the fp8 MFMA from the stored codes; the
+# token scale and the weight row scale multiply the finished f32 sum.  ptd_lowrank_w8a8 serves the operands of the tile
+# entry with r <= 4096 at every T >= 17; the Python rule sends it the cells measured as won against what the module runs
+# without the option (profiles/pair_w8a8.json, ``lowrank_w8a8_takes``).  PTD_LOWRANK_W8A8=0 sends the operator's calls
+# through the torch expression of the semantics instead.
+_W8A8 = os.environ.get("PTD_LOWRANK_W8A8", "1") != "0"
+_W8A8_MAX_R = 4096
+_W8A8_QUANT, _W8A8_NO_SPLIT = 1, 2
+
+
+def lowrank_w8a8_takes(T: int, n_i: int, r: int, n_o: int) -> bool:
+    """The cells an ``activations="fp8"`` module sends to the W8A8 operator: the measured class that is won against what
+    the module runs without the option -- ptd_lowrank_tile_w8, or the torch expression where T r n_i > 2^33 -- in every
+    round against every round (profiles/pair_w8a8.json: bf16, the Llama-3-8B-width layers, r in {256, 1024}, T in {24,
+    128, 512, 2048, 4096, 8192}).  Won: 8 cells of 36, all at r = 1024 -- 4096 -> 4096 at T = 2048 and 4096 (0.90 and
+    0.94 of today's time), 4096 -> 14336 at T = 2048, 4096 and 8192 (0.94, 0.87, 0.98), 14336 -> 4096 at T = 512 and
+    2048 (0.985, 0.89); n_o and T between those neighbours are taken with them.  LOST: every r = 256 cell (1.25-2.3
+    times today's time: four launches and the f32 slab round trip against two or three, on products too small to
+    repay them), r = 1024 up to 512 tokens on n_i = 4096 (1.12-1.36), and the largest cells, 4096 -> 4096 at T = 8192
+    (1.08) and 14336 -> 4096 at T = 4096 and 8192 (1.11, 1.36), where the products level off near 440-500 TFLOP/s
+    and torch's 16-bit GEMMs on dequantised copies are faster.  So of the nine cells above 2^33, which ran the
+    expression, four are won and five are not.  (The C entry and the operator serve every T >= 17 all the same.)
+    Plain comparisons on integers: the modules call this under torch.compile."""
+    if r != 1024:
+        return False
+    if n_i == 4096 and 4096 <= n_o <= 14336:
+        return 2048 <= T <= (8192 if n_o == 14336 else 4096)
+    if n_i == 14336 and n_o == 4096:
+        return 512 <= T <= 2048
+    return False
+
+
+def _w8a8_operands(f) -> bool:
+    if f is None or not _q_operands(_FP8, "skinny", *f):
+        return False
+    (T, n_i), r, n_o = f[0].shape, f[1].shape[0], f[3].shape[0]
+    return _TILE_W8_MIN_T <= T <= _A8_MAX_T and r <= _W8A8_MAX_R and T * max(n_i, r, n_o) < _A8_MAX_CELLS
+
+
+def lowrank_w8a8_serves(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                        bias: Optional[torch.Tensor]) -> bool:
+    """Whether the W8A8 operator runs ``lowrank_w8a8`` on these operands as they lie (without loading the library): the
+    operands of ``lowrank_skinny_w8_serves`` at T >= 17 with r <= 4096, and PTD_LOWRANK_W8A8 not 0.  By the operands
+    alone: which cells a module sends is ``lowrank_w8a8_takes``."""
+    return _W8A8 and _w8a8_operands(_facts(x2d, Aq, sa, Bq, sb, bias))
+
+
+def fp8_quantize_rows(x: torch.Tensor):
+    """Q of the rows of x [T, n] (bf16 / f16 on a ROCm device, n a multiple of 16): (codes [T, n] float8_e4m3fn, scales
+    [T] f32) -- per row s = amax / 448 (1 for an all-zero row) and the e4m3fn codes of x / s, round to nearest even,
+    clamped to +-448: ptd_fp8_quantize_rows, bit for bit ``_torch_ops.fp8_quantize_rows_reference``."""
+    _dev(x)
+    x = _rows2d(x)
+    assert x.dtype in (torch.bfloat16, torch.float16) and x.shape[0] >= 1 and x.shape[1] >= 16 and x.shape[1] % 16 == 0
+    T, n = x.shape
+    codes = torch.empty((T, n), dtype=torch.float8_e4m3fn, device=x.device)
+    scales = torch.empty((T,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _hip.load().ptd_fp8_quantize_rows(x.data_ptr(), x.stride(0), T, n, codes.data_ptr(), n, scales.data_ptr(),
+                                               _code(x), _stream(x))
+    _hip.check(rc, "ptd_fp8_quantize_rows")
+    return codes, scales
+
+
+def w8a8_product(xq: torch.Tensor, sx: torch.Tensor, Wq: torch.Tensor, sw: torch.Tensor, bias: Optional[torch.Tensor],
+                 dtype: torch.dtype, quantize: bool = False, split: bool = True):
+    """round_D(((xq Wq^T) * sx[:, None]) * sw + bias) [T, N] in D = ``dtype`` (bf16 / f16) from e4m3 codes xq [T, K] and
+    Wq [N, K], token scales sx [T] and row scales sw [N] (f32): ptd_w8a8_product on the fp8 MFMA, sums in f32, K cut into
+    the slabs of ``lowrank_w8a8_plan``'s rule (``split=False``: one slab, as the pair runs its second product), rounded
+    once.  ``quantize=True`` (N a multiple of 16, at most 4096) returns ``fp8_quantize_rows`` of that result instead,
+    (codes [T, N], scales [T]), without the D values touching memory."""
+    _dev(xq, sx, Wq, sw, bias)
+    xq, Wq = _rows2d(xq), _rows2d(Wq)
+    sx, sw = sx.contiguous(), sw.contiguous()
+    assert xq.dtype == Wq.dtype == torch.float8_e4m3fn and sx.dtype == sw.dtype == torch.float32
+    assert dtype in (torch.bfloat16, torch.float16)
+    (T, K), N = xq.shape, Wq.shape[0]
+    assert T >= 1 and Wq.shape[1] == K and sx.shape == (T,) and sw.shape == (N,)
+    bias = None if bias is None else bias.to(dtype).contiguous()
+    flags = (_W8A8_QUANT if quantize else 0) | (0 if split else _W8A8_NO_SPLIT)
+    lib = _hip.load()
+    ws_bytes = lib.ptd_w8a8_product_workspace_bytes(T, K, N, flags)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=xq.device)
+    out = None if quantize else torch.empty((T, N), dtype=dtype, device=xq.device)
+    codes = torch.empty((T, N), dtype=torch.float8_e4m3fn, device=xq.device) if quantize else None
+    scales = torch.empty((T,), dtype=torch.float32, device=xq.device) if quantize else None
+    with torch.cuda.device(xq.device):
+        rc = lib.ptd_w8a8_product(xq.data_ptr(), xq.stride(0), sx.data_ptr(), T, K, Wq.data_ptr(), Wq.stride(0), sw.data_ptr(),
+                                  N, _ptr(bias), _ptr(out), N, _ptr(codes), N, _ptr(scales), ws.data_ptr(), ws_bytes,
+                                  _DT[dtype], flags, _stream(xq))
+    _hip.check(rc, "ptd_w8a8_product")
+    return (codes, scales) if quantize else out
+
+
+def lowrank_w8a8(x2d: torch.Tensor, Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+                 bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The fp8 pair with per-token fp8 activations for T >= 17 rows of x2d (bf16 / f16), the factors of
+    ``lowrank_tile_w8`` with r <= 4096: y = round((Q(h) Bq^T * s_h) * sb + bias), h = round((Q(x2d) Aq^T * s_x) * sa) --
+    ptd_lowrank_w8a8, four launches on x2d's stream and no host read (safe under graph capture), bit for bit
+    ``fp8_quantize_rows`` and ``w8a8_product`` composed.  Row t of the result depends on row t of x2d alone.  Operands
+    the C entry does not serve raise."""
+    return _q_call(_FP8, "w8a8", x2d, Aq, sa, Bq, sb, bias)
+
+
+def lowrank_w8a8_plan(T: int, n_i: int, r: int, n_o: int, dtype: torch.dtype = torch.bfloat16) -> dict:
+    """What ``lowrank_w8a8`` would launch for a shape (ptd_lowrank_w8a8_plan; host only, no GPU): the fields of
+    ``lowrank_tile_w8_plan``; ``kslab`` is a multiple of 128.  A shape the entry does not serve raises."""
+    out = (ctypes.c_int32 * len(_TILE_W8_PLAN_FIELDS))()
+    rc = _hip.load().ptd_lowrank_w8a8_plan(T, n_i, r, n_o, _DT[dtype], out, len(out))
+    _hip.check(rc, "ptd_lowrank_w8a8_plan")
     return dict(zip(_TILE_W8_PLAN_FIELDS, out))
 
 
