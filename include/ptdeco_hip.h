@@ -71,7 +71,9 @@ extern "C" {
                              *    ptd_lowrank_tile_gated_q_workspace_bytes, ptd_lowrank_tile_gated_q,
                              *    ptd_lowrank_tile_group_q_plan,
                              *    ptd_fp8_quantize_rows, ptd_w8a8_product_workspace_bytes, ptd_w8a8_product,
-                             *    ptd_lowrank_w8a8_workspace_bytes, ptd_lowrank_w8a8, ptd_lowrank_w8a8_plan) */
+                             *    ptd_lowrank_w8a8_workspace_bytes, ptd_lowrank_w8a8, ptd_lowrank_w8a8_plan,
+                             *    ptd_lowrank_gated_product, ptd_lowrank_tile_gated_workspace_bytes,
+                             *    ptd_lowrank_tile_gated, ptd_lowrank_tile_gated_plan) */
 
 typedef enum { PTD_F32 = 0, PTD_F64 = 1, PTD_BF16 = 2, PTD_F16 = 3 } ptd_dtype;
 
@@ -935,6 +937,40 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
                              const void* Au, int64_t lda_u, int64_t r_u, const void* Bu, int64_t ldb_u, const void* bias_u,
                              int64_t n_ff, int act, void* y, int64_t ldy,
                              void* ws, size_t ws_bytes, int dtype, void* stream);
+
+/* The gated pair in bf16 / f16 at the token counts the two entries above leave (17 <= T < 32 and T > 96).
+ * ptd_lowrank_gated_product: y = round(round(act(g)) u) with g = round(h_g B_g^T + bias_g), u = round(h_u B_u^T + bias_u)
+ * in ONE launch (lowrank_tile_gated.hip).  h_m is [T, r_m] with row pitch ldh_m, B_m [n_ff, r_m] with row pitch ldb_m (the
+ * nn.Linear layout), y [T, n_ff] with row pitch ldy; either bias may be NULL.  A workgroup holds both f32 sums of its
+ * outputs; each sum has one accumulator and ascends in K, so its order depends on r_m alone: the tile shape, which the
+ * host picks from (T, n_ff), changes no bit, and row t of y depends on row t of h_g and h_u alone.  Served for T >= 1,
+ * n_ff >= 1, both r >= 8 and multiples of 8, pitches multiples of 8, 16-byte aligned h and B, act one of PTD_ACT_*;
+ * anything else, f32 included, returns PTD_ERR_UNSUPPORTED before a kernel is launched.  y takes 8-byte stores where it is
+ * 8-byte aligned and ldy a multiple of 4, 2-byte stores otherwise.
+ * ptd_lowrank_tile_gated: y = act(gate(x)) * up(x) (arguments of ptd_lowrank_skinny_gated): each member's first product
+ * exactly as ptd_lowrank_forward runs it (the padded rank and the K split included: the bits of h are the same), into
+ * the member's region of the workspace, then the launch above on h_g and h_u.  Served for T >= 17 under the operand rule
+ * of ptd_lowrank_skinny for both members; anything else PTD_ERR_UNSUPPORTED with nothing launched.  The workspace is
+ * the sum of the members' ptd_lowrank_forward workspaces, each rounded up to 256 bytes.
+ * ptd_lowrank_tile_gated_plan: what a served call launches, from the shapes alone (host only): out[PTD_TILE_GATED_PLAN_*],
+ * cap >= PTD_TILE_GATED_PLAN_LEN. */
+#define PTD_TILE_GATED_PLAN_BT 0         /* tokens of a tile of the gated launch */
+#define PTD_TILE_GATED_PLAN_BN 1         /* ... its outputs */
+#define PTD_TILE_GATED_PLAN_GRID 2       /* its workgroups */
+#define PTD_TILE_GATED_PLAN_LAUNCHES 3   /* 3: the members' first products (a product's own reduce pass not counted) + 1 */
+#define PTD_TILE_GATED_PLAN_LEN 4
+#define PTD_LOWRANK_TILE_GATED_MIN_T 17
+int ptd_lowrank_gated_product(const void* h_g, int64_t ldh_g, int64_t r_g, const void* B_g, int64_t ldb_g, const void* bias_g,
+                              const void* h_u, int64_t ldh_u, int64_t r_u, const void* B_u, int64_t ldb_u, const void* bias_u,
+                              int64_t T, int64_t n_ff, int act, void* y, int64_t ldy, int dtype, void* stream);
+size_t ptd_lowrank_tile_gated_workspace_bytes(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype);
+int ptd_lowrank_tile_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
+                           const void* Ag, int64_t lda_g, int64_t r_g, const void* Bg, int64_t ldb_g, const void* bias_g,
+                           const void* Au, int64_t lda_u, int64_t r_u, const void* Bu, int64_t ldb_u, const void* bias_u,
+                           int64_t n_ff, int act, void* y, int64_t ldy,
+                           void* ws, size_t ws_bytes, int dtype, void* stream);
+int ptd_lowrank_tile_gated_plan(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int64_t n_ff, int dtype, int32_t* out,
+                                int cap);
 
 /* 1 <= count <= PTD_LOWRANK_GROUP_MAX bf16 / f16 pairs that read the same x at the same 32 <= T <= 96 tokens (arguments of
  * ptd_lowrank_decode_group; operands and semantics per member those of ptd_lowrank_skinny), in THREE launches on the

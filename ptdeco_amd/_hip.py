@@ -184,6 +184,15 @@ SIGNATURES = {
     "ptd_lowrank_a8_tile_w6": _PAIR_MX,
     "ptd_lowrank_skinny_gated_workspace_bytes": _GATED_WS,
     "ptd_lowrank_skinny_gated": _GATED16,
+    # h_g, ldh_g, r_g, B_g, ldb_g, bias_g, h_u, ldh_u, r_u, B_u, ldb_u, bias_u, T, n_ff, act, y, ldy, dtype, stream
+    "ptd_lowrank_gated_product": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                          c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64,
+                                          c_int, c_void_p]),
+    "ptd_lowrank_tile_gated_workspace_bytes": _GATED_WS,
+    "ptd_lowrank_tile_gated": _GATED16,
+    # T, n_i, r_g, r_u, n_ff, dtype, out, cap
+    "ptd_lowrank_tile_gated_plan": (c_int, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int,
+                                            ctypes.POINTER(ctypes.c_int32), c_int]),
     "ptd_lowrank_skinny_group_workspace_bytes": _GROUP16_WS,
     "ptd_lowrank_skinny_group": _GROUP16,
     "ptd_lowrank_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),

@@ -18,6 +18,10 @@ FakeTensor / meta shape propagation and CUDA-graph capture see of a decomposed l
                                                              ops.lowrank_skinny_gated_serves (32 ... 96), else g and u
                                                              as lowrank_forward_group forms them and torch's
                                                              activation and product
+    lowrank_forward_gated_tile(same operands) -> Tensor      the same, with ops.lowrank_tile_gated where
+                                                             ops.lowrank_tile_gated_serves (bf16 / f16, 17 ... 31 and
+                                                             above 96, where measured to win) between the skinny
+                                                             kernels and the member expression
     lowrank_forward_w8(Tensor x2d, Tensor Aq, Tensor sa, Tensor Bq, Tensor sb, Tensor? bias) -> Tensor
                                                              the pair with fp8 (e4m3fn) factors and f32 row scales:
                                                              ops.lowrank_decode_w8 where ops.lowrank_decode_w8_serves
@@ -166,12 +170,19 @@ def lowrank_forward_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor,
     (ops.lowrank_decode_gated_serves: ptd_lowrank_decode_gated), at small batches three (32 <= T <= 96, bf16 / f16:
     ops.lowrank_skinny_gated_serves, ptd_lowrank_skinny_gated); otherwise g and u as lowrank_forward_group forms them
     and torch's own activation and product.  Inference only: no autograd formula."""
+    return _gated(False, x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
+
+
+def _gated(tile, x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
+    """The body of lowrank_forward_gated and, with ``tile``, of lowrank_forward_gated_tile."""
     if act not in GATE_ACTS:
         raise ValueError(f"act must be one of {sorted(GATE_ACTS)}, got {act!r}")
     if ops.lowrank_decode_gated_serves(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
         return ops.lowrank_decode_gated(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
     if ops.lowrank_skinny_gated_serves(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
         return ops.lowrank_skinny_gated(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
+    if tile and ops.lowrank_tile_gated_serves(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
+        return ops.lowrank_tile_gated(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
     As, Bs, biases = [Ag, Au], [Bg, Bu], [bias_g, bias_u]
     if ops.lowrank_decode_group_serves(x2d, As, Bs, biases):
         g, u = ops.lowrank_decode_group(x2d, As, Bs, biases).split([Bg.shape[0], Bu.shape[0]], 1)
@@ -181,7 +192,7 @@ def lowrank_forward_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor,
 
 
 @lowrank_forward_gated.register_fake
-def _(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
+def _gated_fake(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
     torch._check(act in GATE_ACTS, lambda: f"lowrank_forward_gated: act must be one of {sorted(GATE_ACTS)}")
     torch._check(x2d.dim() == 2, lambda: "lowrank_forward_gated: x2d must be 2-D")
     for A, B, bias in ((Ag, Bg, bias_g), (Au, Bu, bias_u)):
@@ -193,6 +204,22 @@ def _(x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act):
         torch._check(bias is None or tuple(bias.shape) == (B.shape[0],), lambda: "lowrank_forward_gated: bias must be [n_ff]")
     torch._check(Bg.shape[0] == Bu.shape[0], lambda: "lowrank_forward_gated: gate and up must have the same out_features")
     return x2d.new_empty((x2d.shape[0], Bg.shape[0]))
+
+
+@torch.library.custom_op("ptdeco_amd::lowrank_forward_gated_tile", mutates_args=())
+def lowrank_forward_gated_tile(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
+                               Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> torch.Tensor:
+    """``lowrank_forward_gated`` with the dual product of the prefill sizes as well (the operator behind
+    ``lowrank_gated(..., prefill="fused")``): the decode kernels, the skinny kernels, then, where
+    ops.lowrank_tile_gated_serves (bf16 / f16, T >= 17, the measured class of ops.lowrank_tile_gated_takes), the members'
+    first products and ONE launch for both second products, the activation and the product (ptd_lowrank_tile_gated);
+    otherwise exactly what lowrank_forward_gated does.  With "relu" the bits of that operator; with "silu" and
+    "gelu_tanh" within the gated bound of it (the activation is evaluated in f32 by the kernel's own formula).
+    Inference only: no autograd formula."""
+    return _gated(True, x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
+
+
+lowrank_forward_gated_tile.register_fake(_gated_fake)
 
 
 def _route_q(tag, regimes, expression, x2d, *w):

@@ -452,12 +452,17 @@ size_t ptd_lowrank_forward_workspace_bytes(int64_t T, int64_t n_i, int64_t r, in
   return b;
 }
 
-int ptd_lowrank_forward(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r,
-                        const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws,
-                        size_t ws_bytes, int dtype, void* stream) {
-  PTD_REQUIRE(x && A && B && y && ws, "ptd_lowrank_forward: null pointer");
-  PTD_REQUIRE(ldx >= n_i && lda >= n_i && ldb >= r && ldy >= n_o, "ptd_lowrank_forward: bad leading dimension");
-  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16 || dtype == PTD_F16, "ptd_lowrank_forward: dtype must be f32, bf16 or f16");
+// The first product of ptd_lowrank_forward, h = x A^T, into the workspace: on the padded rank where lowrank_pad128 and
+// the operands allow (h [T, rp] with exact zeros behind column r), else on r with the rest of the workspace for the
+// K split.  ptd_lowrank_forward and ptd_lowrank_tile_gated both form h here, so its bits are the same behind either.
+struct LowrankH {
+  void* h;
+  int64_t ldh;
+  bool padded;
+};
+
+static int lowrank_first_product(const char* name, const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A,
+                                 int64_t lda, int64_t r, void* ws, size_t ws_bytes, int dtype, void* stream, LowrankH* out) {
   const int64_t rp = lowrank_pad128(r, dtype);
   if (rp != r && n_i % 8 == 0 && lda % 8 == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
       ws_bytes >= ptd_lowrank_forward_workspace_bytes(T, n_i, r, dtype)) {
@@ -479,37 +484,50 @@ int ptd_lowrank_forward(const void* x, int64_t ldx, int64_t T, int64_t n_i, cons
       rc = gemm16(static_cast<const u16*>(x), ldx, 1, Ap, 1, n_i, hp, rp, T, rp, n_i, true, 1.0, nullptr, rest,
                   ws_bytes - hp_bytes - ap_bytes, st, 0, 0);
     }
-    if (rc != PTD_OK) return rc;
-    // y = h B^T + bias with K padded to whole 64-deep steps where a short-K kernel serves the shape, else with K = r
-    const int64_t k64 = (int64_t)align_up((size_t)r, 64);
-    if (k64 != r && k64 <= 256) {
-      rc = gemm16(hp, rp, 1, static_cast<const u16*>(B), 1, ldb, y, ldy, T, n_o, k64, true, 1.0,
-                  static_cast<const u16*>(bias), nullptr, 0, st, r, 0);
-      if (rc != PTD_ERR_UNSUPPORTED) return rc;
-    }
-    return ptd_gemm(hp, rp, 1, B, 1, ldb, y, ldy, T, n_o, r, dtype, dtype, 1.0, bias, stream);
+    *out = LowrankH{hp, rp, true};
+    return rc;
   }
   const size_t h_bytes = align_up((size_t)T * (size_t)r * elt_bytes(dtype), 256);
   if (ws_bytes < h_bytes) {
-    set_error("ptd_lowrank_forward: workspace %zu < required %zu bytes", ws_bytes, h_bytes);
+    set_error("%s: workspace %zu < required %zu bytes", name, ws_bytes, h_bytes);
     return PTD_ERR_WORKSPACE;
   }
   void* h = ws;
-  // h = x A^T : A(m,k) = x[m*ldx + k], B(k,n) = A[n*lda + k];   y = h B^T + bias
-  int rc;
+  *out = LowrankH{h, r, false};
+  // h = x A^T : A(m,k) = x[m*ldx + k], B(k,n) = A[n*lda + k]
   if (dtype == PTD_F32) {
     // a small rank leaves the first product with few output tiles: its K range is split over
     // workgroups through the rest of the workspace (deterministic two-pass reduction)
-    rc = gemm_f32(static_cast<const float*>(x), ldx, 1, static_cast<const float*>(A), 1, lda, static_cast<float*>(h), r,
-                  T, r, n_i, 1.0, nullptr, static_cast<char*>(ws) + h_bytes, ws_bytes - h_bytes,
-                  static_cast<hipStream_t>(stream));
-  } else {
-    rc = gemm16_of(dtype)(static_cast<const unsigned short*>(x), ldx, 1, static_cast<const unsigned short*>(A), 1, lda,
+    return gemm_f32(static_cast<const float*>(x), ldx, 1, static_cast<const float*>(A), 1, lda, static_cast<float*>(h), r,
+                    T, r, n_i, 1.0, nullptr, static_cast<char*>(ws) + h_bytes, ws_bytes - h_bytes,
+                    static_cast<hipStream_t>(stream));
+  }
+  return gemm16_of(dtype)(static_cast<const unsigned short*>(x), ldx, 1, static_cast<const unsigned short*>(A), 1, lda,
                           h, r, T, r, n_i, true, 1.0, nullptr, static_cast<char*>(ws) + h_bytes, ws_bytes - h_bytes,
                           static_cast<hipStream_t>(stream), 0, 0);
-  }
+}
+
+int ptd_lowrank_forward(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* A, int64_t lda, int64_t r,
+                        const void* B, int64_t ldb, int64_t n_o, const void* bias, void* y, int64_t ldy, void* ws,
+                        size_t ws_bytes, int dtype, void* stream) {
+  PTD_REQUIRE(x && A && B && y && ws, "ptd_lowrank_forward: null pointer");
+  PTD_REQUIRE(ldx >= n_i && lda >= n_i && ldb >= r && ldy >= n_o, "ptd_lowrank_forward: bad leading dimension");
+  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16 || dtype == PTD_F16, "ptd_lowrank_forward: dtype must be f32, bf16 or f16");
+  LowrankH h;
+  int rc = lowrank_first_product("ptd_lowrank_forward", x, ldx, T, n_i, A, lda, r, ws, ws_bytes, dtype, stream, &h);
   if (rc != PTD_OK) return rc;
-  return ptd_gemm(h, r, 1, B, 1, ldb, y, ldy, T, n_o, r, dtype, dtype, 1.0, bias, stream);
+  if (h.padded) {
+    // y = h B^T + bias with K padded to whole 64-deep steps where a short-K kernel serves the shape, else with K = r
+    typedef unsigned short u16;
+    const int64_t k64 = (int64_t)align_up((size_t)r, 64);
+    if (k64 != r && k64 <= 256) {
+      rc = gemm16_of(dtype)(static_cast<const u16*>(h.h), h.ldh, 1, static_cast<const u16*>(B), 1, ldb, y, ldy, T, n_o, k64,
+                            true, 1.0, static_cast<const u16*>(bias), nullptr, 0, static_cast<hipStream_t>(stream), r, 0);
+      if (rc != PTD_ERR_UNSUPPORTED) return rc;
+    }
+  }
+  // y = h B^T + bias
+  return ptd_gemm(h.h, h.ldh, 1, B, 1, ldb, y, ldy, T, n_o, r, dtype, dtype, 1.0, bias, stream);
 }
 
 size_t ptd_lowrank_decode_workspace_bytes(int64_t T, int64_t n_i, int64_t r, int dtype) {
@@ -1403,6 +1421,100 @@ int ptd_lowrank_skinny_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i,
   }
   return lowrank_skinny_gated(x, ldx, T, n_i, Ag, lda_g, r_g, Bg, ldb_g, bias_g, Au, lda_u, r_u, Bu, ldb_u, bias_u, n_ff,
                               act, y, ldy, ws, dtype, static_cast<hipStream_t>(stream));
+}
+
+// The gated pair at the token counts the decode and skinny gated entries leave (lowrank_tile_gated.hip)
+int ptd_lowrank_gated_product(const void* h_g, int64_t ldh_g, int64_t r_g, const void* B_g, int64_t ldb_g, const void* bias_g,
+                              const void* h_u, int64_t ldh_u, int64_t r_u, const void* B_u, int64_t ldb_u, const void* bias_u,
+                              int64_t T, int64_t n_ff, int act, void* y, int64_t ldy, int dtype, void* stream) {
+  PTD_REQUIRE(h_g && B_g && h_u && B_u && y, "ptd_lowrank_gated_product: null pointer");
+  PTD_REQUIRE(ldh_g >= r_g && ldb_g >= r_g && ldh_u >= r_u && ldb_u >= r_u && ldy >= n_ff,
+              "ptd_lowrank_gated_product: bad leading dimension");
+  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16 || dtype == PTD_F16,
+              "ptd_lowrank_gated_product: dtype must be f32, bf16 or f16");
+  if (!lowrank_gated_product_serves(T, n_ff, r_g, r_u, act, dtype, h_g, ldh_g, B_g, ldb_g, h_u, ldh_u, B_u, ldb_u)) {
+    set_error("ptd_lowrank_gated_product: not served (T=%lld n_ff=%lld r_g=%lld r_u=%lld act=%d dtype=%d: bf16 or f16, "
+              "both r >= 8 and multiples of 8, pitches multiples of 8, 16-byte aligned rows, act 0 (silu), 1 (gelu_tanh) or "
+              "2 (relu))", (long long)T, (long long)n_ff, (long long)r_g, (long long)r_u, act, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  return lowrank_gated_product(h_g, ldh_g, r_g, B_g, ldb_g, bias_g, h_u, ldh_u, r_u, B_u, ldb_u, bias_u, T, n_ff, act, y, ldy,
+                               dtype, static_cast<hipStream_t>(stream));
+}
+
+// T >= 17 and the operand rule of ptd_lowrank_skinny for both members (h lies in the workspace: aligned, pitch r or the
+// padded rank, both multiples of 8)
+static bool lowrank_tile_gated_serves(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int64_t n_ff, int act, int dtype,
+                                      const void* x, int64_t ldx, const void* Ag, int64_t lda_g, const void* Bg,
+                                      int64_t ldb_g, const void* Au, int64_t lda_u, const void* Bu, int64_t ldb_u) {
+  if (T < PTD_LOWRANK_TILE_GATED_MIN_T || n_i < 8 || n_i % 8 || ldx % 8 || lda_g % 8 || lda_u % 8) return false;
+  if (n_i >= (1ll << 30) || !aligned16(x) || !aligned16(Ag) || !aligned16(Au)) return false;
+  return lowrank_gated_product_serves(T, n_ff, r_g, r_u, act, dtype, nullptr, 8, Bg, ldb_g, nullptr, 8, Bu, ldb_u);
+}
+
+static size_t lowrank_tile_gated_region(int64_t T, int64_t n_i, int64_t r, int dtype) {
+  return align_up(ptd_lowrank_forward_workspace_bytes(T, n_i, r, dtype), 256);
+}
+
+size_t ptd_lowrank_tile_gated_workspace_bytes(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int dtype) {
+  if (T < 1 || n_i < 1 || r_g < 1 || r_u < 1) return 0;
+  return lowrank_tile_gated_region(T, n_i, r_g, dtype) + lowrank_tile_gated_region(T, n_i, r_u, dtype);
+}
+
+int ptd_lowrank_tile_gated(const void* x, int64_t ldx, int64_t T, int64_t n_i, const void* Ag, int64_t lda_g, int64_t r_g,
+                           const void* Bg, int64_t ldb_g, const void* bias_g, const void* Au, int64_t lda_u, int64_t r_u,
+                           const void* Bu, int64_t ldb_u, const void* bias_u, int64_t n_ff, int act, void* y, int64_t ldy,
+                           void* ws, size_t ws_bytes, int dtype, void* stream) {
+  PTD_REQUIRE(x && Ag && Bg && Au && Bu && y && ws, "ptd_lowrank_tile_gated: null pointer");
+  PTD_REQUIRE(ldx >= n_i && lda_g >= n_i && lda_u >= n_i && ldb_g >= r_g && ldb_u >= r_u && ldy >= n_ff,
+              "ptd_lowrank_tile_gated: bad leading dimension");
+  PTD_REQUIRE(dtype == PTD_F32 || dtype == PTD_BF16 || dtype == PTD_F16,
+              "ptd_lowrank_tile_gated: dtype must be f32, bf16 or f16");
+  PTD_REQUIRE(aligned16(ws), "ptd_lowrank_tile_gated: the workspace must be 16-byte aligned");
+  // (nothing is launched for what the entry does not serve: the caller forms g and u and applies the activation itself)
+  if (!lowrank_tile_gated_serves(T, n_i, r_g, r_u, n_ff, act, dtype, x, ldx, Ag, lda_g, Bg, ldb_g, Au, lda_u, Bu, ldb_u)) {
+    set_error("ptd_lowrank_tile_gated: not served (T=%lld n_i=%lld r_g=%lld r_u=%lld n_ff=%lld act=%d dtype=%d: "
+              "bf16 or f16, T >= " PTD_STR(PTD_LOWRANK_TILE_GATED_MIN_T) ", both r >= 8, n_i and both r multiples of 8, "
+              "16-byte aligned rows, act 0 (silu), 1 (gelu_tanh) or 2 (relu))", (long long)T, (long long)n_i,
+              (long long)r_g, (long long)r_u, (long long)n_ff, act, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  const size_t need = ptd_lowrank_tile_gated_workspace_bytes(T, n_i, r_g, r_u, dtype);
+  if (ws_bytes < need) {
+    set_error("ptd_lowrank_tile_gated: workspace %zu < required %zu bytes", ws_bytes, need);
+    return PTD_ERR_WORKSPACE;
+  }
+  // each member's h as ptd_lowrank_forward forms it, on the workspace that entry would have asked for
+  LowrankH hg, hu;
+  int rc = lowrank_first_product("ptd_lowrank_tile_gated", x, ldx, T, n_i, Ag, lda_g, r_g, ws,
+                                 ptd_lowrank_forward_workspace_bytes(T, n_i, r_g, dtype), dtype, stream, &hg);
+  if (rc != PTD_OK) return rc;
+  rc = lowrank_first_product("ptd_lowrank_tile_gated", x, ldx, T, n_i, Au, lda_u, r_u,
+                             static_cast<char*>(ws) + lowrank_tile_gated_region(T, n_i, r_g, dtype),
+                             ptd_lowrank_forward_workspace_bytes(T, n_i, r_u, dtype), dtype, stream, &hu);
+  if (rc != PTD_OK) return rc;
+  return lowrank_gated_product(hg.h, hg.ldh, r_g, Bg, ldb_g, bias_g, hu.h, hu.ldh, r_u, Bu, ldb_u, bias_u, T, n_ff, act, y,
+                               ldy, dtype, static_cast<hipStream_t>(stream));
+}
+
+int ptd_lowrank_tile_gated_plan(int64_t T, int64_t n_i, int64_t r_g, int64_t r_u, int64_t n_ff, int dtype, int32_t* out,
+                                int cap) {
+  PTD_REQUIRE(out, "ptd_lowrank_tile_gated_plan: null pointer");
+  PTD_REQUIRE(cap >= PTD_TILE_GATED_PLAN_LEN, "ptd_lowrank_tile_gated_plan: out holds %d values, the plan has %d", cap,
+              PTD_TILE_GATED_PLAN_LEN);
+  // (the operands of a plan are contiguous and aligned: address 0 passes every alignment test of the serving rule)
+  if (!lowrank_tile_gated_serves(T, n_i, r_g, r_u, n_ff, PTD_ACT_SILU, dtype, nullptr, n_i, nullptr, n_i, nullptr, r_g,
+                                 nullptr, n_i, nullptr, r_u)) {
+    set_error("ptd_lowrank_tile_gated_plan: not served (T=%lld n_i=%lld r_g=%lld r_u=%lld n_ff=%lld dtype=%d)", (long long)T,
+              (long long)n_i, (long long)r_g, (long long)r_u, (long long)n_ff, dtype);
+    return PTD_ERR_UNSUPPORTED;
+  }
+  int bt, bn;
+  int64_t grid;
+  lowrank_tile_gated_shape(T, n_ff, &bt, &bn, &grid);
+  out[PTD_TILE_GATED_PLAN_BT] = bt, out[PTD_TILE_GATED_PLAN_BN] = bn;
+  out[PTD_TILE_GATED_PLAN_GRID] = (int32_t)grid, out[PTD_TILE_GATED_PLAN_LAUNCHES] = 3;
+  return PTD_OK;
 }
 
 size_t ptd_lowrank_skinny_group_workspace_bytes(int count, int64_t T, int64_t n_i, const int64_t* r, int dtype) {

@@ -381,6 +381,17 @@ int lowrank_tile_gated_q(const void* x, int64_t ldx, int64_t T, int64_t n_i, con
                          const void* bias_u, int64_t n_o, int act, void* y, int64_t ldy, void* ws, int dtype,
                          hipStream_t st);
 
+// lowrank_tile_gated.hip: y = round(round(act(g)) u) with g = round(h_g B_g^T + bias_g), u = round(h_u B_u^T + bias_u) in
+// bf16 / f16, one launch with both sums of an output in one lane (ptd_lowrank_gated_product; behind the members' first
+// products ptd_lowrank_tile_gated).  lowrank_tile_gated_shape: the tile (tokens x outputs) and the grid of a call
+bool lowrank_gated_product_serves(int64_t T, int64_t n_ff, int64_t r_g, int64_t r_u, int act, int dtype, const void* h_g,
+                                  int64_t ldh_g, const void* B_g, int64_t ldb_g, const void* h_u, int64_t ldh_u,
+                                  const void* B_u, int64_t ldb_u);
+void lowrank_tile_gated_shape(int64_t T, int64_t n_ff, int* bt, int* bn, int64_t* grid);
+int lowrank_gated_product(const void* h_g, int64_t ldh_g, int64_t r_g, const void* B_g, int64_t ldb_g, const void* bias_g,
+                          const void* h_u, int64_t ldh_u, int64_t r_u, const void* B_u, int64_t ldb_u, const void* bias_u,
+                          int64_t T, int64_t n_ff, int act, void* y, int64_t ldy, int dtype, hipStream_t st);
+
 // lowrank_plan.hip: what a launch of one serving family would do, from the host rules the launchers call (ptd_lowrank_plan);
 // fills out[PTD_PLAN_*], PTD_OK or PTD_ERR_UNSUPPORTED
 int lowrank_plan(int family, int64_t T, int64_t n_i, int64_t r, int64_t n_o, int dtype, int32_t* out);

@@ -27,6 +27,7 @@ _lowrank_forward_nchw = torch.ops.ptdeco_amd.lowrank_forward_nchw.default
 _lowrank_forward_group = torch.ops.ptdeco_amd.lowrank_forward_group.default
 _lowrank_forward_group_fused = torch.ops.ptdeco_amd.lowrank_forward_group_fused.default
 _lowrank_forward_gated = torch.ops.ptdeco_amd.lowrank_forward_gated.default
+_lowrank_forward_gated_tile = torch.ops.ptdeco_amd.lowrank_forward_gated_tile.default
 _lowrank_forward_w8 = torch.ops.ptdeco_amd.lowrank_forward_w8.default
 _lowrank_forward_w8a8 = torch.ops.ptdeco_amd.lowrank_forward_w8a8.default
 _lowrank_forward_w4 = torch.ops.ptdeco_amd.lowrank_forward_w4.default
@@ -610,6 +611,7 @@ def set_pair_activations(model: torch.nn.Module, activations: str, names=None) -
 
 _QUANTIZED_MODES = ("members", "fused")
 _SMALL_BATCH_MODES = ("members", "fused")
+_PREFILL_MODES = ("members", "fused")
 
 
 def _fused_format(x: torch.Tensor, pairs, quantized: str):
@@ -681,7 +683,8 @@ def lowrank_group(x: torch.Tensor, pairs, *, quantized: str = "members", small_b
     return y.reshape(*x.shape[:-1], y.shape[1])
 
 
-def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu", *, quantized: str = "members") -> torch.Tensor:
+def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu", *, quantized: str = "members",
+                  prefill: str = "members") -> torch.Tensor:
     """``act(gate(x)) * up(x)`` for the gate and up projections of a decomposed gated MLP (SwiGLU: "silu", GeGLU:
     "gelu_tanh", ReGLU: "relu"): [..., out_features].  For installed ``LowRankLinear`` modules with equal in_features and
     out_features at decode shapes (1 to 16 tokens) the whole expression runs in two kernel launches, at small batches
@@ -698,9 +701,20 @@ def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu", *, quantized: st
     members at 17 to 31 and above 96 tokens run on ptd_lowrank_tile_gated_q under the same contract: three launches
     (two where neither first product is cut into slabs), both second products in one workgroup and no [T, n_ff]
     intermediate (out_features a multiple of 4).  MX members at those token counts run as they do alone and torch applies the activation.  Anything else is the
-    "members" path; 16-bit members ignore the keyword; any other value raises ``ValueError``."""
+    "members" path; 16-bit members ignore the keyword; any other value raises ``ValueError``.
+
+    ``prefill`` says what happens to 16-bit members (``LowRankLinear``, the conditions of the fused decode route above)
+    at 17 to 31 and above 96 tokens (prompt processing).  "members", the default: g and u as the modules form them and
+    torch's activation and product.  "fused": ``torch.ops.ptdeco_amd.lowrank_forward_gated_tile`` -- in the measured
+    classes of ``ops.lowrank_tile_gated_takes`` (bf16 / f16) the members' first products as the modules run them and ONE
+    launch for both second products, the activation and the product (ptd_lowrank_tile_gated): no [T, n_ff]
+    intermediate, no elementwise launch; with "relu" the expression's bits, with "silu" and "gelu_tanh" within the
+    gated bound of it.  At every other token count and shape what the default does.  Quantised members ignore the
+    keyword; any other value raises ``ValueError``."""
     if act not in _torch_ops.GATE_ACTS:
         raise ValueError(f"act must be one of {sorted(_torch_ops.GATE_ACTS)}, got {act!r}")
+    if prefill not in _PREFILL_MODES:
+        raise ValueError(f"prefill must be one of {_PREFILL_MODES}, got {prefill!r}")
     fmt = _fused_format(x, [gate, up], quantized)
     if fmt is not None and gate.out_features == up.out_features:
         x2d = x.reshape(-1, gate.in_features)
@@ -714,19 +728,21 @@ def lowrank_gated(x: torch.Tensor, gate, up, act: str = "silu", *, quantized: st
     if not fused:
         return _torch_ops.GATE_ACTS[act](gate(x)) * up(x)
     x2d = x.reshape(-1, gate[0].in_features)
-    y = _lowrank_forward_gated(x2d, gate[0].weight, gate[1].weight, gate[1].bias, up[0].weight, up[1].weight,
-                               up[1].bias, act)
+    gated = _lowrank_forward_gated_tile if prefill == "fused" else _lowrank_forward_gated
+    y = gated(x2d, gate[0].weight, gate[1].weight, gate[1].bias, up[0].weight, up[1].weight, up[1].bias, act)
     return y.reshape(*x.shape[:-1], y.shape[1])
 
 
-def lowrank_mlp(x: torch.Tensor, gate, up, down, act: str = "silu", *, quantized: str = "members") -> torch.Tensor:
+def lowrank_mlp(x: torch.Tensor, gate, up, down, act: str = "silu", *, quantized: str = "members",
+                prefill: str = "members") -> torch.Tensor:
     """``down(act(gate(x)) * up(x))``, the MLP of a decomposed Llama / Mistral / Qwen block: ``lowrank_gated`` and then
     ``down`` as it is called alone -- at decode shapes four kernel launches in all, at 32 to 96 tokens six.
     ``quantized`` is passed to ``lowrank_gated`` (with "fused", quantised gate and up of one format run in two
     launches at decode shapes: bit for bit the module expression with "relu", within the gated bound of it with "silu"
     and "gelu_tanh"; fp8 gate and up at prompt sizes in three on ptd_lowrank_tile_gated_q, likewise); ``down`` runs as
-    it does alone."""
-    return down(lowrank_gated(x, gate, up, act, quantized=quantized))
+    it does alone.  ``prefill`` is passed to ``lowrank_gated`` too (with "fused", 16-bit gate and up at prompt sizes on
+    ptd_lowrank_tile_gated where measured to win)."""
+    return down(lowrank_gated(x, gate, up, act, quantized=quantized, prefill=prefill))
 
 
 def _is_plain_1x1(m: torch.nn.Module) -> bool:

@@ -441,11 +441,14 @@ def _facts(*ts: Optional[torch.Tensor]) -> Optional[list]:
 
 
 def _pair16_rule(regime: str, x: _Facts, A: _Facts, B: _Facts, bias: Optional[_Facts]) -> bool:
-    """The rule of ptd_lowrank_decode (``regime`` "decode") / ptd_lowrank_skinny ("skinny") on plain facts."""
+    """The rule of ptd_lowrank_decode (``regime`` "decode") / ptd_lowrank_skinny ("skinny") / a member of
+    ptd_lowrank_tile_gated ("tile") on plain facts."""
     if len(x.shape) != 2 or len(A.shape) != 2 or len(B.shape) != 2 or not (x.dtype == A.dtype == B.dtype):
         return False
     if regime == "decode":
         dtypes, lo, hi = (torch.float32, torch.bfloat16, torch.float16), 1, _DECODE_MAX_T
+    elif regime == "tile":      # (a member of ptd_lowrank_tile_gated: skinny's operands at every T >= 17)
+        dtypes, lo, hi = (torch.bfloat16, torch.float16), _DECODE_MAX_T + 1, (1 << 30) - 1
     else:
         dtypes, lo, hi = (torch.bfloat16, torch.float16), _SKINNY_MIN_T, _SKINNY_MAX_T
     if x.dtype not in dtypes:
@@ -454,7 +457,7 @@ def _pair16_rule(regime: str, x: _Facts, A: _Facts, B: _Facts, bias: Optional[_F
     (T, n_i), r, n_o = x.shape, A.shape[0], B.shape[0]
     if A.shape[1] != n_i or B.shape[1] != r or not lo <= T <= hi or n_o < 1 or r < 8 or n_i % vec or r % vec:
         return False
-    if regime == "skinny" and n_i < 8:
+    if regime != "decode" and n_i < 8:
         return False
     if bias is not None and (len(bias.shape) != 1 or bias.shape[0] != n_o):      # (the bias dtype is not looked at)
         return False
@@ -1736,6 +1739,93 @@ def lowrank_skinny_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, 
     ptd_lowrank_skinny_gated, y [T, n_ff] contiguous.  Operands the entry does not serve
     (``lowrank_skinny_gated_serves``) raise; row t of the result depends on row t of x2d alone."""
     return _gated16_call("skinny", x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
+
+
+# The gated pair of a 16-bit MLP at the T the two gated entries above leave (17 ... 31 and above 96: prompt processing) runs,
+# OPT-IN (``prefill="fused"`` on lowrank_gated / lowrank_mlp, ``torch.ops.ptdeco_amd.lowrank_forward_gated_tile``), on
+# ptd_lowrank_tile_gated: each member's first product as ptd_lowrank_forward runs it, then ONE launch that forms both
+# second products for a tile of tokens x outputs and applies the activation and the product in the lanes that hold both
+# sums (csrc/lowrank_tile_gated.hip) -- where the member expression writes g and u, reads g and writes act(g), reads both
+# and writes y.  The C entries serve every operand of the rule at every T >= 17; the Python rule admits the cells
+# measured as won (profiles/pair_tile_gated.json, ``lowrank_tile_gated_takes``).  PTD_LOWRANK_TILE_GATED=0 switches the
+# route off.
+_TILE_GATED = os.environ.get("PTD_LOWRANK_TILE_GATED", "1") != "0"
+_TILE_GATED_PLAN_FIELDS = ("bt", "bn", "grid", "launches")      # PTD_TILE_GATED_PLAN_*
+_TILE_GATED_SMALL_T_RANKS, _TILE_GATED_RANKS, _TILE_GATED_MAX_T = 2048, 512, 512
+
+
+def lowrank_tile_gated_takes(T: int, n_i: int, r_g: int, r_u: int, n_ff: int) -> bool:
+    """The cells of ptd_lowrank_tile_gated measured as won -- every fused round below every members round in
+    profiles/pair_tile_gated.json (gate / up 4096 -> r -> 14336): 17 to 31 tokens up to r_g + r_u = 2048 (0.89 - 0.93 of
+    the members' time), 97 to 512 tokens up to r_g + r_u = 512 (0.82 - 0.89).  Lost, and left to the members: ranks of
+    1024 from 128 tokens on (1.23 - 1.70) and every rank from 2048 tokens on (1.11 - 1.14 at r = 256), where the members'
+    second products run on the tuned wide-tile kernels; what lies between the measured cells stays with the members."""
+    if T <= _DECODE_MAX_T or _SKINNY_MIN_T <= T <= _SKINNY_MAX_T:
+        return False
+    return r_g + r_u <= (_TILE_GATED_SMALL_T_RANKS if T < _SKINNY_MIN_T else _TILE_GATED_RANKS if T <= _TILE_GATED_MAX_T else 0)
+
+
+def lowrank_tile_gated_serves(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
+                              Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> bool:
+    """Whether the operator sends these operands to ``lowrank_tile_gated`` (without loading the library): the switch, a
+    known activation, both members bf16 / f16 under the operand rule of ``lowrank_skinny`` at T >= 17 with the same
+    n_ff, and the measured class ``lowrank_tile_gated_takes``."""
+    if not _TILE_GATED or act not in GATED_ACTS:
+        return False
+    f = _facts(x2d, Ag, Bg, bias_g, Au, Bu, bias_u)
+    if f is None:
+        return False
+    x, ag, bg, fb_g, au, bu, fb_u = f
+    if not (_pair16_rule("tile", x, ag, bg, fb_g) and _pair16_rule("tile", x, au, bu, fb_u)) or bg.shape[0] != bu.shape[0]:
+        return False
+    return lowrank_tile_gated_takes(x.shape[0], x.shape[1], ag.shape[0], au.shape[0], bg.shape[0])
+
+
+def lowrank_tile_gated(x2d: torch.Tensor, Ag: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor],
+                       Au: torch.Tensor, Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str) -> torch.Tensor:
+    """act((x2d @ Ag^T) @ Bg^T + bias_g) * ((x2d @ Au^T) @ Bu^T + bias_u) for T >= 17 rows of x2d, the operands of
+    ``lowrank_skinny_gated``: ptd_lowrank_tile_gated, y [T, n_ff] contiguous.  h_g and h_u are the bits
+    ``lowrank_forward`` forms; g, act(g) and the product are each rounded once to x2d's dtype.  Plain launches on x2d's
+    stream and no host read: safe under graph capture.  Operands the C entry does not serve raise; row t of the result
+    depends on row t of x2d alone."""
+    return _gated16_call("tile", x2d, Ag, Bg, bias_g, Au, Bu, bias_u, act)
+
+
+def lowrank_gated_product(h_g: torch.Tensor, Bg: torch.Tensor, bias_g: Optional[torch.Tensor], h_u: torch.Tensor,
+                          Bu: torch.Tensor, bias_u: Optional[torch.Tensor], act: str,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """round(round(act(g)) * u) with g = round(h_g @ Bg^T + bias_g), u = round(h_u @ Bu^T + bias_u): the one launch of
+    ptd_lowrank_gated_product on h_g [T, r_g], Bg [n_ff, r_g], h_u [T, r_u], Bu [n_ff, r_u] (bf16 / f16, unit inner
+    strides, any row pitch the entry serves), into ``out`` ([T, n_ff], any row pitch) or a new contiguous tensor."""
+    if act not in GATED_ACTS:
+        raise ValueError(f"act must be one of {sorted(GATED_ACTS)}, got {act!r}")
+    _dev(h_g, Bg, bias_g, h_u, Bu, bias_u, out)
+    h_g, Bg, h_u, Bu = (_rows2d(t) for t in (h_g, Bg, h_u, Bu))
+    (T, r_g), r_u, n_ff = h_g.shape, h_u.shape[1], Bg.shape[0]
+    assert h_u.shape[0] == T and Bg.shape[1] == r_g and Bu.shape == (n_ff, r_u)
+    assert h_g.dtype == Bg.dtype == h_u.dtype == Bu.dtype
+    y = torch.empty((T, n_ff), dtype=h_g.dtype, device=h_g.device) if out is None else out
+    assert y.shape == (T, n_ff) and y.dtype == h_g.dtype and y.stride(1) == 1
+    bias_g = None if bias_g is None else bias_g.to(h_g.dtype).contiguous()
+    bias_u = None if bias_u is None else bias_u.to(h_g.dtype).contiguous()
+    with torch.cuda.device(h_g.device):
+        rc = _hip.load().ptd_lowrank_gated_product(
+            h_g.data_ptr(), h_g.stride(0), r_g, Bg.data_ptr(), Bg.stride(0), _ptr(bias_g), h_u.data_ptr(), h_u.stride(0),
+            r_u, Bu.data_ptr(), Bu.stride(0), _ptr(bias_u), T, n_ff, GATED_ACTS[act], y.data_ptr(), y.stride(0),
+            _code(h_g), _stream(h_g))
+    _hip.check(rc, "ptd_lowrank_gated_product")
+    return y
+
+
+def lowrank_tile_gated_plan(T: int, n_i: int, r_g: int, r_u: int, n_ff: int, dtype: torch.dtype = torch.bfloat16) -> dict:
+    """What ``lowrank_tile_gated`` would launch for a shape (ptd_lowrank_tile_gated_plan; host only, no GPU): the tile of
+    the gated launch (tokens ``bt`` x outputs ``bn``), its ``grid`` and the call's ``launches`` (the members' first
+    products and the gated launch; a first product's own reduce pass is not counted).  A shape the entry does not serve
+    raises."""
+    out = (ctypes.c_int32 * len(_TILE_GATED_PLAN_FIELDS))()
+    rc = _hip.load().ptd_lowrank_tile_gated_plan(T, n_i, r_g, r_u, n_ff, _DT[dtype], out, len(out))
+    _hip.check(rc, "ptd_lowrank_tile_gated_plan")
+    return dict(zip(_TILE_GATED_PLAN_FIELDS, out))
 
 
 def lowrank_forward_nchw(x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
